@@ -10,8 +10,16 @@ synthetic batch of 32 molecules x 32 atoms per GPU (BASELINE.json configs[1]), f
 
   --mode train   times the full training step instead (fwd + force + loss.backward + RCCL gradient
                  all-reduce + AdamW), reported under the same JSON keys with metric suffix.
+  --dump-outputs DIR
+                 after the timed steps, writes what the timed path computed in its last step as DIR/<name>.npy (float32):
+                 forward+force: E (molecules x 1) and F (atoms x 3) of this rank's batch; training step: loss, the flat
+                 gradient buffer and the updated parameters.  Inputs and weights are seeded: the same arguments give the
+                 same inputs in every run, so two builds can be compared output for output.
+  --full         everything below as well.  A plain run only sets up, warms up, times the steps (and dumps the
+                 outputs): `roofline`, `cpu_baseline` and `extra` stay null / empty (--mode train: extra.train_step holds
+                 the timed step itself, without its roofline).
 
-Besides the headline, the same JSON line carries `extra` (never part of `value`):
+With --full, besides the headline, the same JSON line carries `extra` (never part of `value`):
   extra.train_step                 the full training step (with N > 1 GPUs: including the RCCL gradient all-reduce)
   extra.interaction_block_fwd_bwd  ONE InteractionBlock forward+backward, isolated: step/s and roofline fractions
   extra.gemnet_q                   BASELINE configs[2]: GemNet-Q forward+force with its own roofline, and extra.gemnet_q.train_step:
@@ -22,7 +30,7 @@ Besides the headline, the same JSON line carries `extra` (never part of `value`;
   extra.config4_shard              BASELINE configs[4], one GPU's shard: GemNet-Q, 64 molecules x 64 atoms, default and
                                    peak memory, roofline of the dominant family (--no-config4 skips)
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      dominant kernel family of the step, measured live with HIP events around every launch
                 in one instrumented (eager) pass over the same batch
   cpu_baseline  the oracle (plain-PyTorch CPU restatement, kind "port") timed on the host cores,
@@ -497,6 +505,31 @@ def time_steps(run, steps, warmup, world=1):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` (name -> tensor) as out_dir/<name>.npy in float32 (float64 stays float64).  Past DUMP_LIMIT_BYTES in all, an
+    array keeps a fixed, seeded sample of its leading-dimension rows (the same rows in every run), stored with their
+    indices as <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.nbytes > DUMP_LIMIT_BYTES // (2 * len(host)):
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // (2 * len(host)) // a.nbytes))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"[bench] outputs of the last timed step -> {out_dir}: "
+        + ", ".join(f"{k} {tuple(v.shape)}" for k, v in host.items()))
+
+
 def family_roofline(step, mode="T"):
     """Instrument one eager pass of `step` and return (roofline of the dominant family, per-family table).
     `mode` names the workload ("T", "Q", "train") for the committed-counter lookups."""
@@ -525,10 +558,11 @@ def log_families(title, fam):
 
 # ------------------------------------------------------------------------------------------------ extra measurements
 def extra_train_step(cfg, model_seed, inputs, targets, world, batch, steps=10, warmup=3, want_roofline=True, graph=True,
-                     roof_mode="train"):
+                     roof_mode="train", want_allreduce_alone=True, outputs=None):
     """The full training step (trainer.py:325-360): forward + force + loss + loss.backward() through the
     force + ONE flat-buffer RCCL all-reduce (world > 1) + shared-gradient rescale + global-norm clip + AdamW(amsgrad) + EMA.
-    fwd/force/backward are one hipGraph; collective and optimizer launches follow it."""
+    fwd/force/backward are one hipGraph; collective and optimizer launches follow it.  `outputs` (a dict): receives copies
+    of what the last timed step computed (loss, flat gradient buffer, updated parameters)."""
     from gemnet_pytorch_amd.model.gemnet import GemNet
     from gemnet_pytorch_amd.training.ddp import TrainStep
     torch.manual_seed(model_seed)
@@ -544,6 +578,9 @@ def extra_train_step(cfg, model_seed, inputs, targets, world, batch, steps=10, w
         log(f"[bench] training-step capture unavailable ({type(ex).__name__}: {ex}); eager")
         ts._graph, graphed = None, False
     elapsed = time_steps(lambda: ts(inputs, targets), steps, warmup, world)
+    if outputs is not None:
+        outputs.update(loss=torch.as_tensor(ts.last_loss).detach().clone(), grad=ts.buf.flat.detach().clone(),
+                       params=torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
     out = dict(ms_per_step=round(elapsed / steps * 1e3, 3), molecules_per_s=round(world * batch * steps / elapsed, 1),
                steps=steps, warmup=warmup, hipgraph=graphed, rccl_world_size=world,
                collective=("all_reduce(sum) of one flat %.1f MB fp32 gradient buffer per step over RCCL"
@@ -553,7 +590,7 @@ def extra_train_step(cfg, model_seed, inputs, targets, world, batch, steps=10, w
                # peak of the timed steps (capture + replays); the instrumented pass below holds every intermediate of a step
                # alive through its launch records and is not part of it
                peak_memory_gib=round(torch.cuda.max_memory_allocated(inputs["R"].device) / 2**30, 1))
-    if world > 1:
+    if world > 1 and want_allreduce_alone:
         # the collective alone: the flat gradient buffer through RCCL, back to back between two syncs (max over ranks)
         import torch.distributed as dist
         reps = 20
@@ -957,6 +994,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: launch the ranks, shard the global batch, run one gloo all-reduce and print the JSON "
                          "skeleton (proves the N-rank launch path on a machine without GPUs; tests/test_bench_cpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the CPU baseline and the `extra` object (each still subject to its "
+                         "--no-* switch); without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1021,13 +1063,17 @@ def main():
     log(f"[bench] rank {rank}/{world}: {n_local} molecules, {sizes}, Dense-stack arithmetic {K.DEFAULT_CHAIN_MODE}")
 
     extra = {}
+    outputs = {}
     if args.mode == "train":   # explicit request: the training step IS the timed region
         tr = extra_train_step(cfg, 1234, inputs, targets, world, args.batch, steps=args.steps, warmup=args.warmup,
-                              want_roofline=not args.no_roofline and rank == 0, graph=not args.no_graph,
-                              roof_mode="Qtrain" if args.model == "Q" else "train")
+                              want_roofline=args.full and not args.no_roofline and rank == 0, graph=not args.no_graph,
+                              roof_mode="Qtrain" if args.model == "Q" else "train", want_allreduce_alone=args.full,
+                              outputs=outputs if args.dump_outputs else None)
         elapsed = tr["ms_per_step"] * 1e-3 * args.steps
         graph, roof = tr["hipgraph"], tr.pop("roofline", None)
         extra["train_step"] = tr
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     else:
         model.eval()
         model.requires_grad_(False)  # inference: only dE/dR is needed, no parameter-gradient graph
@@ -1047,9 +1093,18 @@ def main():
                 log(f"[bench] hipGraph capture unavailable ({type(ex).__name__}: {ex}); timing eager launches")
                 graph = None
                 torch.cuda.synchronize()
-        elapsed = time_steps(graph.replay if graph is not None else step, args.steps, args.warmup, world)
+        last = [None]
+        if graph is not None:
+            run = graph.replay           # every replay rewrites g_out, the graph's static outputs
+        else:
+            def run():
+                last[0] = step()
+        elapsed = time_steps(run, args.steps, args.warmup, world)
+        if args.dump_outputs and rank == 0:
+            E_out, F_out = g_out if graph is not None else last[0]
+            dump_outputs(args.dump_outputs, {"E": E_out, "F": F_out})
         roof = None
-        if not args.no_roofline and rank == 0:
+        if args.full and not args.no_roofline and rank == 0:
             roof, fam = family_roofline(step, mode=args.model)      # (the committed counter passes are per workload: T | Q)
             log_families("forward+force", fam)
             # the WHOLE step against the same roof: algorithmic flops of every launcher family of one step / the timed step
@@ -1058,7 +1113,7 @@ def main():
             roof["step_frac"] = round(step_flops / (elapsed / args.steps) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)
 
     # ---- the numbers SURVEY.md 8(d) asks for besides the headline (never part of `value`)
-    if not args.no_extras and args.mode == "force":
+    if args.full and not args.no_extras and args.mode == "force":
         def guarded(name, fn):
             try:
                 t0 = time.time()
@@ -1086,7 +1141,7 @@ def main():
                 guarded("config4_shard", lambda: extra_config4_shard(rank))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "force":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "force":
         # the full configs[1] batch (the workload `value` is quoted on) is the baseline; an 8-molecule sample rides along
         cpu = cpu_baseline(cfg, args.atoms, budget_s=14.0, n_mol=args.batch)
         try:
@@ -1109,7 +1164,7 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"GemNet-{args.model} full (4 blocks, emb 128), batch {args.batch} molecules x "
                                    f"{args.atoms} atoms per GPU, forward+force, fp32 (BASELINE.json configs[{1 if args.model == 'T' else 2}])",
-                       "mode": args.mode, "hipgraph": bool(graph), "per_gpu": sizes,
+                       "mode": args.mode, "full": args.full, "hipgraph": bool(graph), "per_gpu": sizes,
                        "runtime_env": {k: os.environ[k] for k in ("DEBUG_HIP_FORCE_GRAPH_QUEUES",) if k in os.environ},
                        "dense_stack_arithmetic": {"f32": "v_mfma_f32_16x16x4_f32",
                                                   "split6": "fp32 operands as 3 bf16 planes, 6 products on v_mfma_f32_16x16x32_bf16, fp32 accumulate (fp32-equivalent: dropped terms < 2^-24)",

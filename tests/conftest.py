@@ -1,3 +1,4 @@
+import gc
 import os
 import sys
 
@@ -27,6 +28,16 @@ def pytest_collection_modifyitems(config, items):
     for item in items:
         if "gpu" in item.keywords:
             item.add_marker(skip)
+
+
+@pytest.fixture(autouse=True)
+def _collect_garbage_before_gpu_tests(request):
+    """torch.cuda.graph no longer runs the cyclic collector before a capture begins, so a dead reference cycle left by an
+    earlier test (runners, train steps, recorders and the captured graphs and memory they hold) could be collected in the
+    middle of this test's capture, and releasing those resources there aborts the process.  Collect it between tests."""
+    if "gpu" in request.keywords:
+        gc.collect()
+    yield
 
 
 @pytest.fixture(scope="session")

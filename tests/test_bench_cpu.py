@@ -34,3 +34,29 @@ def test_single_rank_dry_run_needs_no_launcher():
     line, err = _run(["--gpus", "1", "--dry-run", "--batch", "4", "--atoms", "12"])
     assert "re-executing" not in err
     assert line["n_gpus"] == 1 and line["shard_sizes"] == [4]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: float32 arrays (float64 kept), and past the size limit a fixed seeded sample of rows that is
+    the same in every run, stored with its row numbers."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"E": torch.randn(8, 1, generator=g), "F": torch.randn(256, 3, generator=g, dtype=torch.float64),
+              "loss": torch.tensor(0.5), "params": torch.randn(20000, generator=g)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and a.shape == tuple(t.shape)
+        assert np.array_equal(a, t.numpy().astype(a.dtype))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 65536)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert files == ["E.npy", "F.npy", "loss.npy", "params.npy", "params_rows.npy"]
+    assert sum((tmp_path / "b" / f).stat().st_size for f in files) <= 65536
+    rows = np.load(tmp_path / "b" / "params_rows.npy").astype(np.int64)
+    assert len(rows) > 0 and np.array_equal(np.load(tmp_path / "b" / "params.npy"), arrays["params"].numpy()[rows])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))

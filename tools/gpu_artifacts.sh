@@ -35,7 +35,7 @@ fi
 pmc() {  # mode, family-dump title, bench args...
   m=$1; title=$2; shift; shift
   # algorithmic bytes / flops per launch of every launcher family of this workload (bench.py's own accounting)
-  GEMNET_DUMP_FAMILIES=$R/$OUT/fam_$m timeout 900 python bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/fam_$m.json 2> $OUT/fam_$m.log
+  GEMNET_DUMP_FAMILIES=$R/$OUT/fam_$m timeout 900 python bench.py "$@" --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $OUT/fam_$m.json 2> $OUT/fam_$m.log
   for c in FETCH_SIZE WRITE_SIZE; do
     ( cd /tmp && timeout 600 rocprofv3 --pmc $c --output-format csv -d $R/$OUT/pmc_${m}_$c -o p -- python $R/bench.py "$@" --no-graph --steps 2 --warmup 1 $B --no-extras > $R/$OUT/pmc_${m}_$c.log 2>&1 )
   done
@@ -60,10 +60,10 @@ fi
 cp profiles/${RND}_pmc_* profiles/${RND}_traffic_* profiles/${RND}_mfma_busy.json $OUT/profiles/ 2>/dev/null
 if has bench; then
   echo "== bench (default command of the driver; reads profiles/${RND}_traffic_* written above)"
-  timeout 1800 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log; cut -c1-300 $OUT/bench_default.json
-  timeout 600 python bench.py --mode train --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_T_train.json 2> $OUT/bench_T_train.log; cut -c1-200 $OUT/bench_T_train.json
-  timeout 600 python bench.py --model Q --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_Q_force.json 2> $OUT/bench_Q_force.log; cut -c1-200 $OUT/bench_Q_force.json
-  timeout 600 python bench.py --model Q --mode train --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_Q_train.json 2> $OUT/bench_Q_train.log; cut -c1-200 $OUT/bench_Q_train.json
+  timeout 1800 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log; cut -c1-300 $OUT/bench_default.json
+  timeout 600 python bench.py --full --mode train --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_T_train.json 2> $OUT/bench_T_train.log; cut -c1-200 $OUT/bench_T_train.json
+  timeout 600 python bench.py --full --model Q --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $OUT/bench_Q_force.json 2> $OUT/bench_Q_force.log; cut -c1-200 $OUT/bench_Q_force.json
+  timeout 600 python bench.py --full --model Q --mode train --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_Q_train.json 2> $OUT/bench_Q_train.log; cut -c1-200 $OUT/bench_Q_train.json
   for f in default T_train Q_force Q_train; do cp $OUT/bench_$f.json $OUT/profiles/${RND}_bench_$f.json; done
 fi
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*.db" -delete; find $OUT -name "*agent_info.csv" -delete
