@@ -145,6 +145,17 @@ SIGNATURES = {
     "gn_quad_basis_bwd_ld_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp],
     "gn_ssilu_f32": [_vp, _vp, _i64, _i, _vp],
     "gn_dact_mul_f32": [_vp, _vp, _i, _vp, _f, _vp, _vp, _i64, _vp],
+    # periodic cells (csrc/pbc.hip)
+    "gn_pbc_index_count": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_double, _vp, _vp, _vp],
+    "gn_pbc_index_fill": [_vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                          _vp, _vp],
+    "gn_pbc_index_trip": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gn_pbc_edge_vec_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "gn_edge_basis_vec_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
+    "gn_edge_basis_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
+    "gn_trip_basis_vec_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
+    "gn_trip_basis_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
+    "gn_pbc_stress_f32": [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp],
 }
 
 _lib = None

@@ -293,6 +293,10 @@ class GraphPlan:
         else:
             self.atoms_per_mol = torch.bincount(inputs["batch_seg"], minlength=self.n_mol).to(torch.float32)
         self.triplets_only = triplets_only
+        # periodic batches (pbc.py): the image of every edge's source atom, int32 (E,3); None for molecules
+        offs = inputs.get("cell_offsets")
+        self.cell_offsets = None if offs is None else offs.to(torch.int32).contiguous()
+        self._edge_mol = None
         if not triplets_only:
             i_a, i_b = inputs["id4_int_a"], inputs["id4_int_b"]
             self.n_int = int(i_a.shape[0])

@@ -36,11 +36,16 @@ class MoleculeInputs(dict):
 class DeviceMolecule:
     """Drop-in for the reference's `Molecule(R, Z, cutoff, int_cutoff, triplets_only)` (ase_calculator.py:23-104)."""
 
-    def __init__(self, R, Z, cutoff, int_cutoff, triplets_only=False):
+    def __init__(self, R, Z, cutoff, int_cutoff, triplets_only=False, cell=None, pbc=None):
+        """cell (3,3) rows = lattice vectors, pbc (3,) bool (default all periodic): a periodic structure (pbc.py; GemNet-T)."""
         R = np.asarray(R)
         Z = np.asarray(Z)
         assert R.shape == (len(Z), 3)
         self.cutoff, self.int_cutoff, self.triplets_only = cutoff, int_cutoff, triplets_only
+        self.cell = None if cell is None else np.asarray(cell, dtype=np.float64).reshape(3, 3)
+        self.pbc = np.ones(3, dtype=bool) if pbc is None else np.asarray(pbc, dtype=bool).reshape(3)
+        if self.cell is not None and not triplets_only:
+            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
         self.R = R
         self.Z = Z
         self.N = np.array([len(Z)], dtype=np.int32)
@@ -64,8 +69,32 @@ class DeviceMolecule:
             self._Z_dev = torch.as_tensor(np.asarray(self.Z), dtype=torch.int64).to(self.device)
             self._N_dev = torch.as_tensor(self.N, dtype=torch.int64).to(self.device)
         R = self.R if torch.is_tensor(self.R) else torch.as_tensor(np.asarray(self.R, dtype=np.float32))
-        return MoleculeInputs(dict(R=R.to(self.device, dtype=torch.float32), Z=self._Z_dev, N=self._N_dev),
-                              self.cutoff, self.int_cutoff, self.triplets_only, layout_key=self._key)
+        data = dict(R=R.to(self.device, dtype=torch.float32), Z=self._Z_dev, N=self._N_dev)
+        if self.cell is not None:
+            data["cell"] = torch.as_tensor(self.cell, dtype=torch.float32).reshape(1, 3, 3).to(self.device)
+            data["pbc"] = torch.as_tensor(self.pbc).reshape(1, 3)
+        return MoleculeInputs(data, self.cutoff, self.int_cutoff, self.triplets_only, layout_key=self._key)
+
+
+def predict_periodic(model, inputs, stress=False, to_host=False):
+    """A periodic `MoleculeInputs`: the device image neighbour list (rebuilt per call, as the reference rebuilds its graph every
+    MD step) + one eager forward -> (E, F) or (E, F, S)."""
+    from .pbc import PeriodicGraphBuilder
+    R, Z, N, cell = inputs["R"], inputs["Z"], inputs["N"], inputs["cell"]
+    if not R.is_cuda:
+        raise RuntimeError("periodic structures run on a HIP device only (no CPU fallback); DeviceMolecule.to('cuda')")
+    if not model.triplets_only:
+        raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+    was_training = model.training
+    try:
+        model.eval()
+        b = PeriodicGraphBuilder(N.cpu().numpy(), inputs.cutoff, pbc=inputs["pbc"].cpu().numpy(), device=R.device)
+        idx = b(R, cell, dtype=torch.int32)
+        out = model(dict(R=R, Z=Z, N=N, cell=cell, **idx), stress=True)
+    finally:
+        model.train(was_training)
+    out = out if stress else out[:2]
+    return tuple(t.detach().cpu() for t in out) if to_host else out
 
 
 def predict_molecule(model, inputs, to_host=False):
@@ -74,6 +103,8 @@ def predict_molecule(model, inputs, to_host=False):
     R, Z, N = inputs["R"], inputs["Z"], inputs["N"]
     if inputs.triplets_only != model.triplets_only:
         raise ValueError("DeviceMolecule(triplets_only=...) does not match the model")
+    if inputs.get("cell") is not None:
+        return predict_periodic(model, inputs, to_host=to_host)
     if not R.is_cuda:
         # host tensors: the host index builder (include/gemnet_index.h) + the ordinary forward (raises without a device,
         # like every other entry point: there is no CPU compute path)

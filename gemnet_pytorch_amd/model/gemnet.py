@@ -201,7 +201,8 @@ class GemNet(torch.nn.Module):
         return angle_cab, angle_abd, angle_cabd
 
     # ---------------------------------------------------------------------------------- forward
-    def _energy(self, R, plan):
+    def _energy(self, R, plan, V=None):
+        """V: the (E,3) edge vectors of a periodic batch (pbc.edge_vectors; the leaf the force and stress are taken from)."""
         T = self.triplets_only
         b3 = self.cbf_basis3
         # Output blocks on a side stream (all model kinds, inference and force training; the round-3 restrictions are gone,
@@ -222,15 +223,20 @@ class GemNet(torch.nn.Module):
             if fork:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    sph3 = ops.share_gradient(ops.trip_basis(R, plan.t_c, plan.t_a, plan.t_b, self.num_spherical))
+                    sph3 = ops.share_gradient(self._trip_basis3(R, plan, V))
                     h = self.atom_emb(plan.z_rows)
                     terms = self.edge_emb.atom_terms(h)
                     ev_a = torch.cuda.Event()
                     ev_a.record(side)
             # one launch: distances + Bessel rbf + spherical-Bessel radial basis; one launch: angles + Y_l0
-            D_ca, V_ca, rbf, rad3 = ops.edge_basis(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a,
-                                                   b3.z_ln, b3.n_ln, b3.cutoff, b3.p,
-                                                   want_V=self.direct_forces)
+            if V is not None:
+                from .. import pbc
+                D_ca, rbf, rad3 = pbc.edge_basis(V, self.rbf_basis.frequencies, b3.z_ln, b3.n_ln, b3.cutoff, b3.p)
+                V_ca = None
+            else:
+                D_ca, V_ca, rbf, rad3 = ops.edge_basis(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a,
+                                                       b3.z_ln, b3.n_ln, b3.cutoff, b3.p,
+                                                       want_V=self.direct_forces)
             if fork:
                 ev_1 = torch.cuda.Event()
                 ev_1.record(main)
@@ -253,7 +259,7 @@ class GemNet(torch.nn.Module):
                 for t in (sph3, h) + tuple(terms):
                     t.record_stream(main)
             else:
-                sph3 = ops.share_gradient(ops.trip_basis(R, plan.t_c, plan.t_a, plan.t_b, self.num_spherical))
+                sph3 = ops.share_gradient(self._trip_basis3(R, plan, V))
         elif ops.train2_enabled() and not self.direct_forces:
             # force training: distances and triplet angles as twice-differentiable kernels (ops_train._Dist2 / _Angle2),
             # the bases on their closed derivative kernels
@@ -393,8 +399,16 @@ class GemNet(torch.nn.Module):
             E_mol = E_mol / plan.atoms_per_mol.clamp(min=1)[:, None]
         return E_mol, F_ca, V_ca
 
-    def forward(self, inputs):
+    def _trip_basis3(self, R, plan, V):
+        if V is not None:
+            from .. import pbc
+            return pbc.trip_basis(V, plan.trip, self.num_spherical)
+        return ops.trip_basis(R, plan.t_c, plan.t_a, plan.t_b, self.num_spherical)
+
+    def forward(self, inputs, stress=False):
         """E, F as the reference's `GemNet.forward` (gemnet.py:453-615).
+        Periodic batches (`cell` (B,3,3) + `cell_offsets` (E,3), pbc.py; GemNet-T, eval-mode forces by autograd): the edge
+        vectors carry the image shift; `stress=True` returns (E, F, S) with S (B,3,3) = dE/d(strain) / |det cell| (eV/A^3).
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
         value beyond 65 504 becomes inf — fitted scale factors keep activations O(1), a model with
         unfitted ones (the starting state of fit_scaling.py, foreign checkpoints) need not.  A non-finite result of an eager
@@ -402,9 +416,15 @@ class GemNet(torch.nn.Module):
         repeats the pass.  (One host read-back per eager forward.  A hipGraph cannot read back: a runner hands its
         `runtime.RangeFlag` in as `inputs["_range_flag"]`, the captured pass ends with the device-side check of the same rows,
         and the runner polls the flag — PaddedGraphRunner, DynamicForceField, ForceGraphs, TrainStep.)"""
+        periodic = inputs.get("cell") is not None
+        if stress and not periodic:
+            raise ValueError("stress=True needs a periodic batch (inputs['cell'])")
+        if periodic and "cell_offsets" not in inputs:
+            raise ValueError("a periodic batch needs its neighbour list with 'cell_offsets' (pbc.PeriodicGraphBuilder)")
         inputs = self.with_indices(inputs)
         with ops.exclusive():
-            return self._forward_guarded(inputs)
+            out = self._forward_guarded(inputs)
+        return out if (stress or not periodic) else out[:2]
 
     def with_indices(self, inputs):
         """`inputs` with the index arrays: as given when it has them, else (a `DataContainer(indices="device")` batch: Z, R, N
@@ -432,7 +452,7 @@ class GemNet(torch.nn.Module):
         if flag is not None and R.is_cuda:
             # a runner's device-side range check (runtime.RangeFlag): two tiny launches + a copy of one word to pinned host
             # memory at the end of the pass — what a REPLAYED graph has instead of the read-back below
-            E, F = out
+            E, F = out[0], out[1]
             flag.watch(E.detach()[:rows[0]] if rows is not None else E.detach(),
                        F.detach()[:rows[1]] if rows is not None else F.detach())
         if _H3_GUARD and h3 and not torch.cuda.is_current_stream_capturing():
@@ -461,6 +481,9 @@ class GemNet(torch.nn.Module):
             raise ValueError(f"matmul_precision must be one of {self.PRECISIONS}; got {self.matmul_precision!r} (reduced-precision "
                              "operand modes are kernel-level experiments, not a model option: slower AND 4e-2 eV/A off on "
                              "BASELINE configs[4], docs/HISTORY.md section 14)")
+        cell = inputs.get("cell")
+        if cell is not None:
+            self._check_periodic(inputs)
         plan = GraphPlan.from_inputs(inputs, self.triplets_only)
         late = None
         pos_graph = False
@@ -503,6 +526,14 @@ class GemNet(torch.nn.Module):
         # (one target: with several, each target's force pass would need its own record of the S2 / S3 sweeps per stack and
         #  one source term per target in S4 — those models train on the composite closure)
         t2 = bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
+        if cell is not None:
+            if graph:
+                raise NotImplementedError("periodic cells: forces by autograd on the first-order (eval) path only; training "
+                                          "with a cell (a second-order force graph) is not supported")
+            out = self._forward_periodic(R, plan, cell)
+            if late is not None:
+                plan.join_late()
+            return out
         with ops.weight_cache(self._wcache), ops.fused_first_order(fused), ops.param_grads(not const_w), \
                 ops.train2(t2, self._packs if (t2 and R.is_cuda) else None), \
                 ops.chain_mode(self.matmul_precision), ops.position_graph(pos_graph), \
@@ -529,6 +560,36 @@ class GemNet(torch.nn.Module):
         if late is not None:
             plan.join_late()
         return E_mol, F_j
+
+    def _check_periodic(self, inputs):
+        """What a cell is not supported with raises (no silent molecular result)."""
+        if not self.triplets_only:
+            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
+        if self.direct_forces:
+            raise NotImplementedError("periodic cells: forces by autograd only, not direct_forces")
+        if self.num_targets != 1:
+            raise NotImplementedError("periodic cells: one target only")
+        if AutomaticFit.fitting_mode:
+            raise NotImplementedError("periodic cells: no scale-factor fitting with a cell")
+        if inputs.get("_guard_rows") is not None or inputs.get("max_in_degree") is not None:
+            raise NotImplementedError("periodic cells: no padded batches")
+        if inputs["R"].requires_grad:
+            raise NotImplementedError("periodic cells: positions that take part in an autograd graph are not supported")
+
+    def _forward_periodic(self, R, plan, cell):
+        """E, F, S of a periodic batch.  Everything depends on R through the edge vectors V (the shift is constant), so the
+        force and the stress come from ONE gradient, G = -dE/dV per edge: F = segsum(G, id_a) - segsum(G, id_c) and
+        S_b = -1/|det cell_b| sum_{e of b} V_e (x) G_e."""
+        from .. import pbc
+        V = pbc.edge_vectors(R, plan, cell).requires_grad_(True)
+        with ops.weight_cache(self._wcache), ops.fused_first_order(True), ops.param_grads(False), \
+                ops.train2(False, None), ops.chain_mode(self.matmul_precision), ops.position_graph(False), \
+                torch.enable_grad():
+            E_mol, _, _ = self._energy(R.detach(), plan, V=V)
+            G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0))[0]
+        F = pbc.forces(G, plan)
+        S = pbc.stress(V.detach(), G, plan, cell)
+        return E_mol.detach(), F, S
 
     def _cotangent(self, E_mol, target):
         """Constant -1 in column `target` (zeros elsewhere) shaped like E_mol, cached per (shape, device)."""
@@ -609,15 +670,20 @@ class GemNet(torch.nn.Module):
             raise TypeError("gemnet_pytorch_amd.GemNet computes in fp32; got R of dtype %s" % R.dtype)
 
     # ----------------------------------------------------------------------------------- misc
-    def predict(self, inputs):
+    def predict(self, inputs, stress=False):
         """(E, F) detached on the host, as the reference (gemnet.py:780-784).  Inputs from `md.DeviceMolecule.get()` (the MD
         loop of ase_calculator.py:148-170) carry no index arrays: they are served by the device index builder + one
-        replayed hipGraph (md.predict_molecule)."""
-        from ..md import MoleculeInputs, predict_molecule
+        replayed hipGraph (md.predict_molecule).  A periodic structure (`DeviceMolecule(..., cell=...)` or a batch with
+        `cell`): `stress=True` -> (E, F, S)."""
+        from ..md import MoleculeInputs, predict_molecule, predict_periodic
         if isinstance(inputs, MoleculeInputs):
+            if stress:
+                if inputs.get("cell") is None:
+                    raise ValueError("stress=True needs a periodic structure")
+                return predict_periodic(self, inputs, stress=True, to_host=True)
             return predict_molecule(self, inputs, to_host=True)
-        E, F = self(inputs)
-        return E.detach().cpu(), F.detach().cpu()
+        out = self(inputs, stress=stress)
+        return tuple(t.detach().cpu() for t in out)
 
     def load_weights(self, path):
         self.load_state_dict(torch.load(path))

@@ -138,6 +138,9 @@ class ForceGraphs:
         self.batches = [dict(b, R=b["R"].detach().clone()) for b in batches]
         for b in self.batches:
             b.pop("_plan", None)
+            if b.get("cell") is not None:     # periodic batch (pbc.py): fixed neighbour list, private cell buffer
+                b["cell"] = b["cell"].detach().float().clone()
+        self.periodic = [b.get("cell") is not None for b in self.batches]
         dev = self.batches[0]["R"].device
         if dev.type != "cuda":
             raise RuntimeError("ForceGraphs needs a HIP device (no CPU fallback)")
@@ -156,19 +159,31 @@ class ForceGraphs:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 for _ in range(warmup):
-                    model(inputs)
+                    model(inputs, stress=inputs.get("cell") is not None)
             cur.wait_stream(st)
         torch.cuda.synchronize(dev)
         for inputs, st in zip(self.batches, self.streams):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=st):
-                out = model(dict(inputs, _range_flag=self.flag))
+                out = model(dict(inputs, _range_flag=self.flag), stress=inputs.get("cell") is not None)
             self.graphs.append(g)
             self.outputs.append(out)
         torch.cuda.synchronize(dev)
 
     def set_positions(self, i, R):
         self.batches[i]["R"].detach().copy_(R)
+
+    def set_cell(self, i, cell):
+        """New cell of periodic sub-batch i (in place; the neighbour list and its offsets stay as captured)."""
+        if not self.periodic[i]:
+            raise ValueError("sub-batch %d has no cell" % i)
+        self.batches[i]["cell"].copy_(cell)
+
+    def stress(self):
+        """Concatenated stress (nStructures, 3, 3) of the last replay (periodic sub-batches only, sub-batch order)."""
+        if not all(self.periodic):
+            raise ValueError("stress needs every sub-batch to be periodic")
+        return torch.cat([o[2] for o in self.outputs])
 
     def replay(self):
         """Enqueue one step (all sub-batches); the calling stream waits for all of them.  A non-finite result of an EARLIER

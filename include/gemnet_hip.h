@@ -630,6 +630,54 @@ int gn_cbf_project_bwd_f32(const float* g, const float* rad, const int32_t* seg_
 int gn_force_loss_f32(const float* E, const float* Et, int64_t nE, const float* F, const float* Ft, int64_t A, const float* mask,
                       float w_e, float w_f, const float* w_f_dev, float* loss, float* gE, float* gF, void* stream);
 
+/* ---- periodic cells, GemNet-T first-order path (csrc/pbc.hip; additive, ABI 15) -------------------------------------------
+ * Edge vector with the image of the source atom:  V_e = R[id_a[e]] - (R[id_c[e]] + cell_offsets[e] cell[b(e)]),
+ * cell (B,3,3) rows = lattice vectors, cell_offsets (E,3) int32, b(e) = batch_seg[id_a[e]].
+ *
+ * Neighbour list.  Forward half: pairs (i, j, n) with i < j, or i == j and n lexicographically positive (first non-zero
+ * component > 0), |R_i - (R_j + n cell)| <= cutoff, ordered by (i, j, n) with n lexicographic (n0 outermost); forward edge e:
+ * id_a = i, id_c = j, offset n; edge e + H: id_a = j, id_c = i, offset -n; id_swap = e +- H, id_undir = e mod H.  Without
+ * images this is the molecular builder's order, array for array.  Image range per pair and periodic axis k from the
+ * fractional difference f and the perpendicular height h_k: n_k in [floor(-f_k - c/h_k), ceil(-f_k + c/h_k)]; pbc (B,3) uint8,
+ * non-periodic axes use n_k = 0.  Positions are not wrapped.  Triplets: reduce edge r = (c -> a), expand edges x = (b -> a)
+ * with x != r (edge identity), ascending x inside each reduce segment (reduce edges ascending).  R / cell: float32 or float64
+ * (is_f64); distances rounded in that dtype like gn_index_gpu_stage1.
+ *   gn_pbc_index_count: cnt (A) int64 forward pairs per atom, off_half (A+1) their exclusive scan (H = off_half[A]).
+ *   gn_pbc_index_fill:  batch_seg (A), the 2H edge arrays + cell_offsets (2H,3); workspace deg (A), in_ptr (A+1), in_edge (2H),
+ *                       cnt3 (2H) int64; off3 (2H+1) int64 = exclusive scan of the triplets per reduce edge (T = off3[2H]).
+ *   gn_pbc_index_trip:  id3_reduce_ca, id3_expand_ba, Kidx3 (T) (Kidx3 may be NULL).
+ * Counts are int64; hipErrorInvalidValue when 2H does not fit int32. */
+int gn_pbc_index_count(const void* R, int is_f64, const void* cell, const uint8_t* pbc, const int32_t* mol_off,
+                       const int32_t* atom_mol, int B, int A, double cutoff, int64_t* cnt, int64_t* off_half, void* stream);
+int gn_pbc_index_fill(const void* R, int is_f64, const void* cell, const uint8_t* pbc, const int32_t* mol_off,
+                      const int32_t* atom_mol, int A, double cutoff, const int64_t* off_half, int64_t H, int32_t* batch_seg,
+                      int32_t* id_a, int32_t* id_c, int32_t* id_undir, int32_t* id_swap, int32_t* cell_offsets, int64_t* deg,
+                      int64_t* in_ptr, int32_t* in_edge, int64_t* cnt3, int64_t* off3, void* stream);
+int gn_pbc_index_trip(const int32_t* id_a, int64_t E, const int64_t* in_ptr, const int32_t* in_edge, const int64_t* off3,
+                      int32_t* id3_reduce_ca, int32_t* id3_expand_ba, int32_t* Kidx3, void* stream);
+/* Geometry from edge vectors.  V (E,3) = gn_pbc_edge_vec_f32 (once per evaluation; the shift is constant in R).
+ *   gn_edge_basis_vec_fwd_f32: D = |V|, rbf (E,NR) (may be NULL), rad (E,S,NR) — gn_edge_basis_fwd_f32 on V.
+ *   gn_edge_basis_vec_bwd_f32: W = dE/dV (E,3) — gn_edge_basis_bwd_f32 on V.
+ *   gn_trip_basis_vec_fwd_f32: Y_l0 of the angle between u = -V[red[t]] and v = -V[exp[t]] (the image-aware c <- a -> b).
+ *   gn_trip_basis_vec_bwd_f32: Gu = dE/du, Gv = dE/dv (T,3); dE/dV = -segsum(Gu by reduce edge) - segsum(Gv by expand edge).
+ * Forces F = segsum(G, id_a) - segsum(G, id_c) with G = -dE/dV (gn_segsum_multi_f32).
+ *   gn_pbc_stress_f32: S[b] = scale / |det cell_b| sum_{e of b} V_e (x) G_e (3x3 row-major), edges grouped by structure by the
+ *   CSR (perm or NULL, seg_off (B+1)) of gn_csr_build_i32; one workgroup per structure, fixed order of addition.  With
+ *   G = -dE/dV and scale = -1: the stress dE/d(strain) / volume (eV/A^3 for eV, A), ASE's sign convention. */
+int gn_pbc_edge_vec_f32(const float* R, const int32_t* id_c, const int32_t* id_a, const int32_t* batch_seg, const float* cell,
+                        const int32_t* cell_offsets, float* V, int64_t E, void* stream);
+int gn_edge_basis_vec_fwd_f32(const float* V, const float* freq, const float* z, const double* nrm, float* D, float* rbf,
+                              float* rad, int64_t E, int NR, int S, float cutoff, int p, void* stream);
+int gn_edge_basis_vec_bwd_f32(const float* g_D, const float* g_rbf, const float* g_rad, const float* V, const float* freq,
+                              const float* z, const double* nrm, float* W, int64_t E, int NR, int S, float cutoff, int p,
+                              void* stream);
+int gn_trip_basis_vec_fwd_f32(const float* V, const int32_t* red, const int32_t* exp, float* Y, float* theta, int64_t T, int S,
+                              void* stream);
+int gn_trip_basis_vec_bwd_f32(const float* gY, const float* V, const int32_t* red, const int32_t* exp, float* Gu, float* Gv,
+                              int64_t T, int S, void* stream);
+int gn_pbc_stress_f32(const float* V, const float* G, const int32_t* perm, const int32_t* seg_off, const float* cell, int B,
+                      float scale, float* S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

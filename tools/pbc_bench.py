@@ -1,0 +1,98 @@
+#!/usr/bin/env python
+"""Periodic forward + force + stress of GemNet-T on a water-like box, eager and replayed from a captured graph (runtime.
+ForceGraphs), against the molecular forward + force on the same positions (no cell; fewer edges: no image pairs).
+Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
+(kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def water_box(n_side, seed=0):
+    """n_side^3 H2O molecules on a jittered grid, 3.1 A apart (about liquid density)."""
+    rs = np.random.RandomState(seed)
+    a = 3.1
+    O = np.array([[i, j, k] for i in range(n_side) for j in range(n_side) for k in range(n_side)], np.float64) * a
+    O += rs.uniform(-0.2, 0.2, O.shape)
+    R, Z = [], []
+    for o in O:
+        d1 = rs.normal(size=3); d1 /= np.linalg.norm(d1)
+        d2 = rs.normal(size=3); d2 -= d2.dot(d1) * d1; d2 /= np.linalg.norm(d2)
+        h1 = o + 0.96 * d1
+        h2 = o + 0.96 * (np.cos(1.82) * d1 + np.sin(1.82) * d2)
+        R += [o, h1, h2]
+        Z += [8, 1, 1]
+    return np.array(R), np.array(Z), np.eye(3) * a * n_side
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--side", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--cutoff", type=float, default=5.0)
+    args = ap.parse_args()
+    import __graft_entry__ as ge
+    ge.build()
+    from gemnet_pytorch_amd.index_device import build_indices_device
+    from gemnet_pytorch_amd.model.gemnet import GemNet
+    from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
+    from gemnet_pytorch_amd.runtime import ForceGraphs
+    from oracle import gemnet_oracle as GO
+
+    cfg = dict(num_spherical=7, num_radial=6, num_blocks=4, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
+               emb_size_quad=32, emb_size_rbf=16, emb_size_cbf=16, emb_size_sbf=32, emb_size_bil_quad=32, emb_size_bil_trip=64,
+               num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True, cutoff=args.cutoff)
+    scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
+    params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
+    model = GemNet(**cfg, scale_file=scale_file)
+    model.load_state_dict(GO.expand_to_reference_state_dict(params))
+    model = model.to("cuda").eval()
+
+    R, Z, cell = water_box(args.side)
+    A = len(R)
+    Rd = torch.tensor(R, dtype=torch.float32, device="cuda")
+    Zd = torch.tensor(Z, device="cuda").long()
+    Nd = torch.tensor([A], device="cuda")
+    celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
+    idx = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
+    per = dict(R=Rd, Z=Zd, N=Nd, cell=celld, **idx)
+    mol = dict(R=Rd, Z=Zd, N=Nd, **build_indices_device(Rd, np.array([A]), args.cutoff, 10.0, True, dtype=torch.int32))
+
+    out = {"atoms": A, "cutoff": args.cutoff, "edges_periodic": int(idx["id_a"].shape[0]),
+           "triplets_periodic": int(idx["id3_reduce_ca"].shape[0]), "edges_molecular": int(mol["id_a"].shape[0]),
+           "triplets_molecular": int(mol["id3_reduce_ca"].shape[0])}
+    out["eager_periodic_ms"] = timed(lambda: model(per, stress=True), args.steps, args.warmup)
+    out["eager_molecular_ms"] = timed(lambda: model(mol), args.steps, args.warmup)
+    fp = ForceGraphs(model, [per])
+    out["graph_periodic_ms"] = timed(fp.replay, args.steps, args.warmup)
+    fm = ForceGraphs(model, [mol])
+    out["graph_molecular_ms"] = timed(fm.replay, args.steps, args.warmup)
+    for k in ("periodic", "molecular"):
+        out[f"graph_{k}_ns_per_triplet"] = 1e6 * out[f"graph_{k}_ms"] / max(out[f"triplets_{k}"], 1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
