@@ -150,6 +150,9 @@ SIGNATURES = {
     "gn_pbc_index_fill": [_vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _vp, _vp],
     "gn_pbc_index_trip": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # capacity form (csrc/pbc_index.hip); gn_pbc_index_ws_bytes returns int64: bound in load()
+    "gn_pbc_index_padded_t": [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_double, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp],
     "gn_pbc_edge_vec_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "gn_edge_basis_vec_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
     "gn_edge_basis_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
@@ -185,6 +188,8 @@ def load():
     lib.gn_csr_ws_bytes.argtypes = [_i64, _i64]
     lib.gn_index_gpu_ws_bytes.restype = _i64
     lib.gn_index_gpu_ws_bytes.argtypes = [_i, _i64, _i]
+    lib.gn_pbc_index_ws_bytes.restype = _i64
+    lib.gn_pbc_index_ws_bytes.argtypes = [_i, _i]
     lib.gn_pack_weight_split_bytes.restype = _i64
     lib.gn_pack_weight_split_bytes.argtypes = [_i, _i]
     lib.gn_error_string.restype = ctypes.c_char_p

@@ -255,6 +255,36 @@ def index_padded_t(builder, R, e_cap, t_cap, a_cap, n_groups, deg_bound, staging
         ptr(bufs["id3_reduce_ca"]), ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_index_gpu_padded_t")
 
 
+def pbc_index_ws_bytes(n_atoms, e_cap):
+    """Bytes of the workspace gn_pbc_index_padded_t needs for `n_atoms` atoms and an edge capacity of `e_cap`."""
+    return int(_lib.load().gn_pbc_index_ws_bytes(int(n_atoms), int(e_cap)))
+
+
+def pbc_index_padded_t(builder, R, cell, e_cap, t_cap, a_cap, n_groups, deg_bound, ws, staging, bufs, state):
+    """The image neighbour list of `builder` (pbc.PeriodicGraphBuilder) for positions R (A,3) and `cell` (>= B rows of (3,3)),
+    both float32 ON THE DEVICE, straight into the capacity-sized arrays `bufs` (id_c, id_a, id_swap, id_undir, cell_offsets,
+    id3_reduce_ca, id3_expand_ba: int32) with the dummy molecule's pad rows behind the batch — no read-back, capturable
+    (gn_pbc_index_padded_t; ws: uint8 of pbc_index_ws_bytes(A, e_cap), staging: int32[7 e_cap], state: int32[8], see the
+    header)."""
+    require_device(R, cell, ws, staging, state)
+    assert R.dtype == torch.float32 and R.is_contiguous() and tuple(R.shape) == (builder.A, 3)
+    assert cell.dtype == torch.float32 and cell.is_contiguous() and cell.shape[0] >= builder.B and tuple(cell.shape[1:]) == (3, 3)
+    assert staging.dtype == torch.int32 and staging.numel() >= 7 * e_cap
+    assert state.dtype == torch.int32 and state.numel() >= 8
+    assert ws.dtype == torch.uint8 and ws.numel() >= pbc_index_ws_bytes(builder.A, e_cap)
+    for k in ("id_c", "id_a", "id_swap", "id_undir"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == e_cap and bufs[k].is_contiguous()
+    assert bufs["cell_offsets"].dtype == torch.int32 and tuple(bufs["cell_offsets"].shape) == (e_cap, 3)
+    assert bufs["cell_offsets"].is_contiguous()
+    for k in ("id3_reduce_ca", "id3_expand_ba"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == t_cap and bufs[k].is_contiguous()
+    check(_lib.load().gn_pbc_index_padded_t(
+        ptr(R), ptr(cell), ptr(builder.pbc), ptr(builder.mol_off), ptr(builder.atom_mol), builder.B, builder.A, builder.cutoff,
+        ptr(ws), int(e_cap), int(t_cap), int(a_cap), int(n_groups), int(deg_bound), ptr(staging), ptr(bufs["id_c"]),
+        ptr(bufs["id_a"]), ptr(bufs["id_swap"]), ptr(bufs["id_undir"]), ptr(bufs["cell_offsets"]), ptr(bufs["id3_reduce_ca"]),
+        ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_pbc_index_padded_t")
+
+
 PADDED_Q_KEYS = ("id_c", "id_a", "id_swap", "id_undir", "id3_reduce_ca", "id3_expand_ba", "id4_int_a", "id4_int_b",
                  "id4_reduce_intm_ca", "id4_expand_intm_db", "id4_reduce_intm_ab", "id4_expand_intm_ab",
                  "id4_reduce_ca", "id4_expand_db", "id4_reduce_cab", "id4_expand_abd")

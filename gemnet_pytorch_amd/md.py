@@ -16,6 +16,9 @@ is used unchanged:
     from gemnet_pytorch_amd.md import DeviceMolecule as Molecule          # the only edited line of an MD script
     calc = GNNCalculator(Molecule(R, Z, cutoff, int_cutoff, triplets_only), model=model, atoms=atoms)
 
+A periodic `DeviceMolecule(..., cell=, pbc=)` (GemNet-T) is served the same way: `predict_periodic`, a cached
+`DynamicForceField(cell=)` whose graph builds the image neighbour list itself; `predict(..., stress=True)` adds the stress.
+
 Triplets-only and quadruplet models alike (GemNet-Q — the model of the reference's MD example — since round 5: the padding
 scheme covers interaction edges, intermediate triplets and quadruplets, padded.py)."""
 import numpy as np
@@ -77,24 +80,43 @@ class DeviceMolecule:
 
 
 def predict_periodic(model, inputs, stress=False, to_host=False):
-    """A periodic `MoleculeInputs`: the device image neighbour list (rebuilt per call, as the reference rebuilds its graph every
-    MD step) + one eager forward -> (E, F) or (E, F, S)."""
-    from .pbc import PeriodicGraphBuilder
+    """A periodic `MoleculeInputs` -> (E, F) or (E, F, S).  Served like a molecule (predict_molecule) from a cached
+    `runtime.DynamicForceField(cell=, pbc=)`: the image neighbour list is built INSIDE the replayed graph for the positions and
+    the cell of the call, so an MD step is one replay.  The cache key is the layout, the cutoff, the periodic axes and the
+    device — the cell is data.  GEMNET_INDEX_IN_GRAPH=0: the host-sized path (device list per call, padded, one replay)."""
     R, Z, N, cell = inputs["R"], inputs["Z"], inputs["N"], inputs["cell"]
     if not R.is_cuda:
         raise RuntimeError("periodic structures run on a HIP device only (no CPU fallback); DeviceMolecule.to('cuda')")
     if not model.triplets_only:
         raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+    pbc = np.asarray(inputs["pbc"].cpu().numpy(), dtype=bool).reshape(-1, 3)
+    lk = inputs.layout_key
+    if lk is None:
+        lk = (Z.detach().cpu().numpy().astype(np.int64).tobytes(), tuple(int(n) for n in N.tolist()))
+    key = (lk, inputs.cutoff, pbc.tobytes(), R.device.index)
+    cache = model.__dict__.setdefault("_md_fields", {})
+    ff = cache.get(key)
     was_training = model.training
     try:
         model.eval()
-        b = PeriodicGraphBuilder(N.cpu().numpy(), inputs.cutoff, pbc=inputs["pbc"].cpu().numpy(), device=R.device)
-        idx = b(R, cell, dtype=torch.int32)
-        out = model(dict(R=R, Z=Z, N=N, cell=cell, **idx), stress=True)
+        if ff is None:
+            from .runtime import DynamicForceField
+            ff = DynamicForceField(model, Z, N.cpu().numpy(), inputs.cutoff, inputs.int_cutoff, cell=cell, pbc=pbc)
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            cache[key] = ff
+        E, F = ff(R, cell=cell)
+        out = (E, F, ff.stress()) if stress else (E, F)
+        if to_host:
+            host = tuple(t.detach().cpu() for t in out)      # (after this copy the replay's device-side range check is exact)
+            if ff.range_tripped():
+                E, F = ff.recover(R)
+                out = (E, F, ff.stress()) if stress else (E, F)
+                host = tuple(t.detach().cpu() for t in out)
+            return host
+        return out
     finally:
         model.train(was_training)
-    out = out if stress else out[:2]
-    return tuple(t.detach().cpu() for t in out) if to_host else out
 
 
 def predict_molecule(model, inputs, to_host=False):

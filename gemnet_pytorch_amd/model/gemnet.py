@@ -571,8 +571,8 @@ class GemNet(torch.nn.Module):
             raise NotImplementedError("periodic cells: one target only")
         if AutomaticFit.fitting_mode:
             raise NotImplementedError("periodic cells: no scale-factor fitting with a cell")
-        if inputs.get("_guard_rows") is not None or inputs.get("max_in_degree") is not None:
-            raise NotImplementedError("periodic cells: no padded batches")
+        # (padded batches — padded.PaddedGraphRunner(cell=...) — are ordinary periodic batches: the dummy molecule has a cell
+        #  row of its own and its pad edges carry offset 0; `_guard_rows` / `max_in_degree` mean what they mean for molecules)
         if inputs["R"].requires_grad:
             raise NotImplementedError("periodic cells: positions that take part in an autograd graph are not supported")
 

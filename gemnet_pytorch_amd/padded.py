@@ -29,7 +29,11 @@ capacities: interaction edges (pad: b->a / a->b of a group), intermediate triple
 sorted by interaction edge like the real ones) and quadruplets (pad: reduce edge c->a of a unit, sorted; expand row = a pad
 intermediate triplet).  A pad row only needs valid indices and a non-degenerate geometry — the real molecules never see it.
 
-Callers: `runtime.DynamicForceField` (the MD loop), `training.ddp.PaddedTrainStep` and
+Periodic structures (pbc.py; GemNet-T): a runner built with `cell=` pads `cell_offsets` with zeros, gives the dummy molecule the
+identity as its cell and returns the stress as well; `attach_builder(pbc.PeriodicGraphBuilder)` puts the image neighbour list
+(gn_pbc_index_padded_t: positions AND cell read at replay time) inside the graph.
+
+Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
 `Trainer.enable_padded_graph` (the training step in the same form), `bench.py` (`extra.dynamic_shape`,
 `extra.train_step_dynamic`).
 """
@@ -134,6 +138,9 @@ def pad_indices(idx, n_atoms, e_cap, t_cap, n_groups, dtype=torch.int64, quad_ca
     red, exp = _pad_triplets(torch.arange(tp, device=dev, dtype=torch.int64), E, ep, tp, quad)
     out["id3_reduce_ca"] = torch.cat([idx["id3_reduce_ca"].to(dtype), red.to(dtype)])
     out["id3_expand_ba"] = torch.cat([idx["id3_expand_ba"].to(dtype), exp.to(dtype)])
+    if "cell_offsets" in idx:       # periodic batch (pbc.py): the pad edges connect dummy atoms in the same image
+        offs = idx["cell_offsets"].reshape(-1, 3)
+        out["cell_offsets"] = torch.cat([offs.to(dtype), torch.zeros(ep, 3, device=dev, dtype=dtype)])
     if quad:
         eint_cap, i_cap, q_cap = quad_caps
         Eint, I, Q = int(idx["id4_int_a"].shape[0]), int(idx["id4_expand_intm_db"].shape[0]), int(idx["id4_reduce_ca"].shape[0])
@@ -194,15 +201,29 @@ class PaddedGraphRunner:
     molecules; a loader's batches): pass N (and Z) with every call; the atoms between the batch and `a_cap` are isolated
     filler atoms of the dummy molecule.  Without it the layout N is fixed and only Z / R / the index arrays change.
     A batch that does not fit raises `ValueError` — size the capacities from the first batches with a margin
-    (`suggest_capacities`)."""
+    (`suggest_capacities`).
+    Periodic structures (`cell` (n_mol,3,3), pbc.py; GemNet-T, fixed layout): the static inputs gain `cell` — one more row for
+    the dummy molecule, the identity: volume 1 — and `cell_offsets` (e_cap,3), zero on the pad edges; `runner(R, idx, cell=)`
+    returns (E, F) as for molecules and `runner.stress()` the stress of the same step.  With images an atom's in-degree is not
+    bounded by the size of its structure: `max_in_degree` is required (`in_degree_of` gives it for a few observed lists)."""
 
     def __init__(self, model, Z, N, e_cap, t_cap, max_in_degree=None, n_groups=None, a_cap=None, index_dtype=torch.int32,
-                 quad_caps=None):
+                 quad_caps=None, cell=None, pbc=None):
         """`quad_caps` = (eint_cap, i_cap, q_cap): capacities of interaction edges, intermediate triplets and quadruplets —
-        required for quadruplet models (`suggest_capacities` sizes all five from a few batches)."""
+        required for quadruplet models (`suggest_capacities` sizes all five from a few batches).  `cell` / `pbc`: the
+        structures' cells (a periodic runner) and their periodic axes (n_mol,3) — kept for `attach_builder`'s check."""
         self.quad = not model.triplets_only
         if self.quad and quad_caps is None:
             raise ValueError("quadruplet models need quad_caps = (eint_cap, i_cap, q_cap)")
+        self.periodic = cell is not None
+        if self.periodic:
+            if self.quad:
+                raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
+            if a_cap is not None:
+                raise NotImplementedError("periodic cells: fixed structure layout only (no a_cap)")
+            if max_in_degree is None:
+                raise ValueError("a periodic runner needs max_in_degree: with images an atom's in-degree is not bounded by the "
+                                 "atoms of its structure (PaddedGraphRunner.in_degree_of)")
         self.GS = 4 if self.quad else 3              # atoms per dummy group
         self.model = model
         dev = Z.device
@@ -236,6 +257,13 @@ class PaddedGraphRunner:
         # The edge / triplet arrays live in `index_dtype` (int32: what the kernels read — the plan built inside the replayed
         # graph then has no conversion launches, and the device index builder hands its int32 arrays over as they are;
         # batches given as int64 are converted by the copy into the buffers).  Values stay far below 2^31 (checked).
+        if self.periodic:
+            c = torch.as_tensor(cell).detach().to(device=dev, dtype=torch.float32).reshape(-1, 3, 3)
+            if c.shape[0] != self.n_mol:
+                raise ValueError(f"cell must have shape ({self.n_mol}, 3, 3); got {tuple(c.shape)}")
+            self.inputs["cell"] = torch.cat([c, torch.eye(3, device=dev, dtype=torch.float32)[None]]).contiguous()
+            self.inputs["cell_offsets"] = torch.zeros(self.e_cap, 3, dtype=torch.int32, device=dev)
+        self.pbc = None if pbc is None else torch.as_tensor(pbc).detach().cpu().reshape(-1, 3).bool()
         self.quad_caps = tuple(int(c) for c in quad_caps) if self.quad else None
         if max((self.e_cap, self.t_cap, self.A_tot) + (self.quad_caps or ())) >= 2 ** 31:
             index_dtype = i64
@@ -300,6 +328,12 @@ class PaddedGraphRunner:
             s += (int(idx["id4_int_a"].shape[0]), int(idx["id4_expand_intm_db"].shape[0]), int(idx["id4_reduce_ca"].shape[0]))
         return s
 
+    @staticmethod
+    def in_degree_of(idx):
+        """Largest in-degree (edges into one atom) of an index dict; 0 without edges."""
+        id_a = torch.as_tensor(idx["id_a"]).reshape(-1)
+        return int(torch.bincount(id_a.long()).max().item()) if id_a.numel() else 0
+
     def fits(self, sizes):
         """Does a batch of these sizes (sizes_of) fit the capacities with valid padding?"""
         E, T = sizes[:2]
@@ -310,9 +344,15 @@ class PaddedGraphRunner:
             ok = min(eintp, ip, qp) >= 0 and not ((ip or qp) and ep < 6) and not (ip and eintp < 1) and not (qp and ip < 1)
         return ok
 
-    def _fill(self, R, idx, Z=None, N=None):
+    def _fill(self, R, idx, Z=None, N=None, cell=None):
         """Write one batch into the static buffers: the real rows as they are, the pad rows from the patterns computed
-        once for the whole capacity (an edge's pattern only depends on its distance from the first pad edge)."""
+        once for the whole capacity (an edge's pattern only depends on its distance from the first pad edge).  Periodic
+        runners: `idx` holds `cell_offsets`; `cell` (n_mol,3,3) replaces the structures' cells when given."""
+        if self.periodic != ("cell_offsets" in idx):
+            raise ValueError("a periodic runner takes index dicts with 'cell_offsets' (pbc.PeriodicGraphBuilder), a molecular "
+                             "one those without")
+        if cell is not None and not self.periodic:
+            raise ValueError("this runner was built without a cell")
         A = int(R.shape[0])
         if A != self.A:
             if not self.variable_atoms or N is None or Z is None:
@@ -356,6 +396,11 @@ class PaddedGraphRunner:
             buf["id3_expand_ba"][T:].copy_(exp)
         if self.quad:
             self._fill_quad(idx, E, ep, tp)
+        if self.periodic:
+            buf["cell_offsets"][:E].copy_(idx["cell_offsets"].reshape(-1, 3))
+            buf["cell_offsets"][E:].zero_()
+            if cell is not None:
+                self._set_cell(cell)
         buf["R"][:self.A].copy_(R)
         self._filled = True
 
@@ -391,6 +436,21 @@ class PaddedGraphRunner:
             buf["id4_reduce_cab"][Q:].copy_(im)
             buf["id4_expand_db"][Q:].copy_(db[im - I])
 
+    def _set_cell(self, cell):
+        c = torch.as_tensor(cell).reshape(-1, 3, 3)
+        if c.shape[0] != self.n_mol:
+            raise ValueError(f"cell must have shape ({self.n_mol}, 3, 3); got {tuple(c.shape)}")
+        self.inputs["cell"][:self.n_mol].copy_(c)
+
+    def stress(self):
+        """Stress (n_mol,3,3) of the last step of a periodic runner (the graph's static output buffer)."""
+        if not self.periodic or self.out is None:
+            raise ValueError("stress needs a periodic runner that has run a step")
+        return self.out[2].detach()[:self.n_mol]
+
+    def _results(self):
+        return self.out[0].detach()[:self.n_mol], self.out[1].detach()[:self.A]
+
     def pad_degree_bound(self):
         return max(self.deg, 2)
 
@@ -400,22 +460,28 @@ class PaddedGraphRunner:
         on b (a->b, d->b): twice the units of the group."""
         if self.quad:
             return 2 * -(-(-(-ep // 6)) // self.G)
+        if self.periodic:
+            # exact: atom a takes BOTH forward edges of every quad of its group (the expression below is one too small when the
+            # quads do not divide evenly); the plan hands the bound to kernels that refuse a longer row, so a periodic
+            # runner — whose bound comes from the caller's lists, not from the molecule size — counts precisely
+            qf, rem = ep // 4, (ep // 2) % 2
+            return 2 * (qf // self.G + 1) if qf % self.G else 2 * (qf // self.G) + rem
         return -(-(ep // 2) // self.G)
 
-    def __call__(self, R, idx, Z=None, N=None):
+    def __call__(self, R, idx, Z=None, N=None, cell=None):
         """R (A, 3) float32 on the device, idx: the index dict of this batch, Z: its atomic numbers when they change from
-        batch to batch, N: its molecule sizes when those change too (runner built with `a_cap`) -> (E (n_mol, targets),
-        F (A, [targets,] 3)); the results live in the graph's static output buffers until the next call."""
+        batch to batch, N: its molecule sizes when those change too (runner built with `a_cap`), cell: the new cells of a
+        periodic runner -> (E (n_mol, targets), F (A, [targets,] 3)); the results live in the graph's static output buffers
+        until the next call (a periodic runner's stress: `stress()`)."""
         if self.flag is not None and self.flag.tripped():
             # an EARLIER replay returned non-finite energies / forces (seen without synchronising: one or two calls late;
             # a caller that waits for its results anyway checks `flag.tripped()` itself and calls `recover()` — md.py)
             self.recover()
-        self._fill(R, idx, Z, N)
+        self._fill(R, idx, Z, N, cell)
         if self.graph is None:
             self._capture()
         self.graph.replay()
-        E, F = self.out
-        return E.detach()[:self.n_mol], F.detach()[:self.A]
+        return self._results()
 
     # ---- the index build INSIDE the replayed graph (triplets-only models, fixed molecule layout) --------------------------
     def attach_builder(self, builder):
@@ -427,13 +493,23 @@ class PaddedGraphRunner:
         reports through `index_error()`."""
         if self.variable_atoms:
             raise NotImplementedError("the in-graph index build needs a fixed molecule layout (no a_cap)")
-        if builder.triplets_only == self.quad or builder.A != self.A or self.index_dtype != torch.int32:
+        from .pbc import PeriodicGraphBuilder
+        pb = isinstance(builder, PeriodicGraphBuilder)
+        if pb != self.periodic or (pb and builder.B != self.n_mol):
+            raise ValueError("builder and runner describe different systems (periodic / molecular)")
+        if pb and self.pbc is not None and not torch.equal(self.pbc.expand(self.n_mol, 3), torch.as_tensor(builder.pbc_host)):
+            raise ValueError("builder and runner differ in their periodic axes")
+        if (not pb and builder.triplets_only == self.quad) or builder.A != self.A or self.index_dtype != torch.int32:
             raise ValueError("builder and runner describe different systems")
         if not self._filled:
             raise RuntimeError("attach_builder: fill the buffers with a first batch (runner._fill / runner(R, idx)) before")
         dev = self.inputs["R"].device
         self.builder = builder
         n_stage = 4 * self.e_cap + 2 * (self.quad_caps[0] if self.quad else self.t_cap)
+        if pb:      # gn_pbc_index_padded_t: the four edge arrays + the offsets are staged, triplets go straight to the buffers
+            from . import kernels as K
+            n_stage = 7 * self.e_cap
+            self._pbc_ws = torch.zeros(K.pbc_index_ws_bytes(self.A, self.e_cap), dtype=torch.uint8, device=dev)
         # (zeros: a build whose interaction-edge count alone exceeds its capacity skips the edge kernel, and the count kernels
         # behind it must not index with uninitialised staging on the very first build)
         self._staging = torch.zeros(n_stage, dtype=torch.int32, device=dev)
@@ -444,7 +520,11 @@ class PaddedGraphRunner:
 
     def _index_in_graph(self):
         from . import kernels as K
-        if self.quad:
+        if self.periodic:
+            K.pbc_index_padded_t(self.builder, self.inputs["R"][:self.A], self.inputs["cell"], self.e_cap, self.t_cap,
+                                 self.a_cap, self.G, self.pad_degree_bound(), self._pbc_ws, self._staging, self.inputs,
+                                 self._idx_state)
+        elif self.quad:
             K.index_padded_q(self.builder, self.inputs["R"][:self.A], (self.e_cap, self.t_cap) + self.quad_caps, self.a_cap,
                              self.G, self.pad_degree_bound(), self._staging, self.inputs, self._idx_state)
         else:
@@ -456,6 +536,10 @@ class PaddedGraphRunner:
         exact after anything that waited for the last replay."""
         return int(self._idx_host[0]) if self.builder is not None else 0
 
+    def index_in_degree(self):
+        """Largest in-degree of a real atom in the last completed in-graph build of a periodic runner (state[4])."""
+        return int(self._idx_host[4]) if self.periodic else None
+
     def index_sizes(self):
         """(E, T[, Eint, I, Q]) of the last completed in-graph index build."""
         h = self._idx_host
@@ -465,8 +549,9 @@ class PaddedGraphRunner:
         self._idx_state.zero_()
         self._idx_host.zero_()
 
-    def run_positions(self, R, Z=None):
-        """One step with the index build inside the graph: R (A, 3) float32 on the device -> (E, F) as `__call__`."""
+    def run_positions(self, R, Z=None, cell=None):
+        """One step with the index build inside the graph: R (A, 3) float32 on the device -> (E, F) as `__call__`; `cell`
+        (n_mol,3,3): the new cells of a periodic runner (the list is built for them inside the replay)."""
         if self.builder is None:
             raise RuntimeError("run_positions needs attach_builder")
         if R.dtype != self.inputs["R"].dtype or tuple(R.shape) != (self.A, 3):
@@ -481,12 +566,15 @@ class PaddedGraphRunner:
                              f"{self.index_error()}, sizes {self.index_sizes()} — its outputs were NaN; build a larger runner")
         if Z is not None:
             self.inputs["Z"][:self.A].copy_(Z)
+        if cell is not None:
+            if not self.periodic:
+                raise ValueError("this runner was built without a cell")
+            self._set_cell(cell)
         self.inputs["R"][:self.A].copy_(R)
         if self.graph is None:
             self._capture()
         self.graph.replay()
-        E, F = self.out
-        return E.detach()[:self.n_mol], F.detach()[:self.A]
+        return self._results()
 
     def recover(self):
         """The range flag tripped: move the model off the fp16 planes (runtime.fall_back_to_bf16_planes: warns) and drop the
@@ -523,26 +611,29 @@ class PaddedGraphRunner:
         if self.flag is not None:
             inputs["_range_flag"] = self.flag
         inputs.pop("_plan", None)
+        kw = dict(stress=True) if self.periodic else {}       # (E, F, S): the stress of the step stays readable (stress())
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):          # warm-up off the default stream (autograd stream bookkeeping, lazy caches)
             for _ in range(2):
                 if self.builder is not None:
                     self._index_in_graph()
-                self.model(dict(inputs))
+                self.model(dict(inputs), **kw)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             cap = dict(inputs)                  # a fresh dict: the plan is built inside the capture, from the static buffers
-            if self.builder is not None:
-                self._index_in_graph()
+            def step():                         # index build (when attached) + plan + model: what a replay runs
+                if self.builder is not None:
+                    self._index_in_graph()
+                return self.model(cap, **kw)
             if getattr(self, "check", False):   # happens-before check of the capture (hbcheck.py); recorder left in self.hb
                 from . import hbcheck
                 with hbcheck.record() as self.hb:
-                    self.out = self.model(cap)
+                    self.out = step()
             else:
-                self.out = self.model(cap)
+                self.out = step()
             if self.builder is not None:
                 from . import kernels as K
                 for t in self.out:

@@ -7,6 +7,10 @@ shifted edge geometry and the stress (csrc/pbc.hip; conventions in include/gemne
 
 Input keys of a periodic batch: `cell` (B,3,3), rows = lattice vectors; `cell_offsets` (E,3) integer: edge e = (c -> a) has
 V_e = R[a] - (R[c] + cell_offsets[e] @ cell[b(e)]).  The stress is dE/d(strain) / |det cell| (ASE's sign convention, eV/A^3).
+
+The builder reads two sizes back per call.  For MD — a new list every step — the same list is built without a read-back inside a
+captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
+runtime.DynamicForceField(cell=...), md.predict_periodic.
 """
 import numpy as np
 import torch

@@ -228,17 +228,39 @@ class DynamicForceField:
     on the unpadded arrays).  The capacities start `margin` above the first call's sizes; a call that outgrows them
     captures a new graph with `margin` head room again (counted in `recaptures`).  Triplets-only AND quadruplet models (the
     latter since round 5: padded.py pads interaction edges, intermediate triplets and quadruplets as well — GemNet-Q is the
-    model of the reference's MD example, ase_example.ipynb cell 13)."""
+    model of the reference's MD example, ase_example.ipynb cell 13).
 
-    def __init__(self, model, Z, N_host, cutoff, int_cutoff, margin=0.08, max_in_degree=None):
+    Periodic structures (`cell=` (B,3,3), `pbc=`; GemNet-T): the image neighbour list of pbc.PeriodicGraphBuilder, built inside
+    the replayed graph (gn_pbc_index_padded_t) for the positions AND the cell of the step:
+
+        ff = DynamicForceField(model, Z, N_host, cutoff, int_cutoff, cell=cell, pbc=pbc)
+        E, F = ff(R)  |  ff(R, cell=new_cell);   S = ff.stress()
+
+    The first call also sizes the in-degree bound (images: not bounded by the structure's size) with `margin` head room; a step
+    that outgrows a capacity or that bound is re-sized and repeated like a molecular one, a cell the builder rejects
+    (degenerate, or more than pbc.MAX_IMAGES images per side) raises the builder's `ValueError` and the last accepted cell
+    is put back: the next `ff(R)` computes on it."""
+
+    def __init__(self, model, Z, N_host, cutoff, int_cutoff, margin=0.08, max_in_degree=None, cell=None, pbc=None):
         from .index_device import DeviceGraphBuilder
         import numpy as np
         self.model, self.Z = model, Z
         self.N_host = np.asarray(N_host, dtype=np.int64).reshape(-1)
         self.N = torch.as_tensor(self.N_host, device=Z.device)
-        self.builder = DeviceGraphBuilder(self.N_host, cutoff, int_cutoff, model.triplets_only, device=Z.device)
         self.margin = float(margin)
-        self.deg = int(max_in_degree) if max_in_degree is not None else int(self.N_host.max()) - 1
+        self.periodic = cell is not None
+        if self.periodic:
+            from .pbc import PeriodicGraphBuilder
+            if not model.triplets_only:
+                raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+            self.builder = PeriodicGraphBuilder(self.N_host, cutoff, pbc=pbc, device=Z.device)
+            # private cell buffer: the caller's tensor may change between the step and its repetition after a re-size
+            self.cell = torch.as_tensor(cell).detach().to(device=Z.device, dtype=torch.float32).reshape(-1, 3, 3).clone()
+            self._good_cell = self.cell.clone()      # the last cell a completed step accepted (restored after a rejected one)
+            self.deg = int(max_in_degree) if max_in_degree is not None else 0       # grown from the observed lists
+        else:
+            self.builder = DeviceGraphBuilder(self.N_host, cutoff, int_cutoff, model.triplets_only, device=Z.device)
+            self.deg = int(max_in_degree) if max_in_degree is not None else int(self.N_host.max()) - 1
         self.runner = None
         self.recaptures = 0
         self._bstream = None
@@ -249,54 +271,102 @@ class DynamicForceField:
             self._bstream = torch.cuda.Stream(device=R.device)
         self._bstream.wait_stream(main)          # the new positions come from work on the calling stream (the integrator)
         with torch.cuda.stream(self._bstream):
-            idx = self.builder(R, dtype=torch.int32)     # as built: the padded runner keeps its index buffers in int32
+            if self.periodic:                            # (check_cell raises the ValueErrors of a cell it cannot serve)
+                idx = self.builder(R, self.cell, dtype=torch.int32)
+                idx = {k: v for k, v in idx.items() if k not in ("batch_seg", "Kidx3")}
+            else:
+                idx = self.builder(R, dtype=torch.int32)     # as built: the padded runner keeps its index buffers in int32
         main.wait_stream(self._bstream)
         for t in idx.values():
             t.record_stream(main)
         return idx
 
-    def __call__(self, R, exact=True):
-        """`exact` (the graph builds its own neighbour list): wait for the step and look at the
+    def __call__(self, R, cell=None, exact=True):
+        """`cell` (periodic force fields): the cells of this step (kept until the next one is given).
+        `exact` (the graph builds its own neighbour list): wait for the step and look at the
         device-side report of its index build — a system that outgrew the capacities is re-sized and the step repeated, as
         on the host-sized path.  With exact=False nothing waits: such a step returns NaN energies / forces and the NEXT call
         re-sizes (for callers that keep everything on the device and check `index_failed()` themselves)."""
         from .padded import PaddedGraphRunner
+        if cell is not None:
+            if not self.periodic:
+                raise ValueError("this force field was built without a cell")
+            self.cell.copy_(torch.as_tensor(cell).reshape(-1, 3, 3))
         r = self.runner
         if r is not None and r.builder is not None:
             if not r.index_error():
-                out = r.run_positions(R)            # the whole step — index build included — is one replay
+                # the whole step — index build included — is one replay
+                out = r.run_positions(R, cell=self.cell if cell is not None else None)
                 if not exact:
                     return out
                 torch.cuda.current_stream(R.device).synchronize()
                 if not r.index_error():
+                    if cell is not None:
+                        self._good_cell.copy_(self.cell)
                     return out
+            err = r.index_error()
             r.reset_index_state()                   # this / an earlier step outgrew the capacities: size them anew below
-        idx = self._build(R)
+            if err & (32 | 64):                     # the cell itself: the builder's own check says what is wrong with it
+                bad = self._restore_cell()
+                self.builder.check_cell(bad)
+                raise ValueError(f"the in-graph neighbour list rejected the cell (index error bits {err})")
+        try:
+            idx = self._build(R)
+        except ValueError:                          # check_cell of the host-sized build: same promise as above
+            if self.periodic:
+                self._restore_cell()
+            raise
+        if self.periodic:
+            self._good_cell.copy_(self.cell)
         sizes = PaddedGraphRunner.sizes_of(idx)
         r = self.runner
+        m = self.margin
+        deg_now = PaddedGraphRunner.in_degree_of(idx) if self.periodic else 0
         # pad triplets need a complete quad (unit) of pad edges; the pad edges must fit the dummy groups' in-degree bound
-        if r is None or not r.fits(sizes):
+        if r is None or not r.fits(sizes) or deg_now > r.deg:
             E, T = sizes[:2]
-            m = self.margin
+            if self.periodic:
+                self.deg = max(self.deg, int(deg_now * (1 + m)) + 1)
             e_cap = int(E * (1 + 1.5 * m)) // 12 * 12 + 24
             t_cap = int(T * (1 + m)) // 2 * 2 + 2
             # dummy groups for the largest padding this runner may see (a later call with fewer edges pads more)
             groups = max(1, -(-int(e_cap * min(1.0, 4 * m)) // (2 * max(self.deg, 2))))
+            if self.periodic:
+                # small cells: the fixed head room of e_cap outweighs the margin, and a dummy atom a takes BOTH pad edges of a
+                # quad — groups for the padding left when the list shrinks by 4 x margin, two incoming edges per quad
+                pad_max = e_cap - int(E * (1 - min(1.0, 4 * m)))
+                groups = max(1, -(-(-(-pad_max // 4)) // max(self.deg // 2, 1)))
             quad_caps = None
             if not self.model.triplets_only:
                 Eint, I, Q = sizes[2:5]
                 quad_caps = (int(Eint * (1 + 1.5 * m)) + 4, int(I * (1 + m)) + 4, int(Q * (1 + m)) + 4)
+            pk = dict(cell=self.cell, pbc=self.builder.pbc_host) if self.periodic else {}
             self.runner = PaddedGraphRunner(self.model, self.Z, self.N, e_cap, t_cap, max_in_degree=self.deg, n_groups=groups,
-                                            quad_caps=quad_caps)
+                                            quad_caps=quad_caps, **pk)
             self.recaptures += self.runner is not r and r is not None
         if IN_GRAPH_INDEX and R.dtype == torch.float32:
             # from here on the index build is part of the graph (padded.attach_builder): this call's
             # arrays validate the buffers, every later call is  positions in -> one replay -> results out
-            self.runner._fill(R, idx)
+            self.runner._fill(R, idx, cell=self.cell if self.periodic else None)
             if self.runner.builder is None:
                 self.runner.attach_builder(self.builder)
             return self.runner.run_positions(R)
-        return self.runner(R, idx)
+        return self.runner(R, idx, cell=self.cell if self.periodic else None)
+
+    def _restore_cell(self):
+        """A cell was rejected: put the last accepted one back (here and in the graph's static buffer), so that the next
+        `ff(R)` without a cell computes on it; -> the rejected cell on the host."""
+        bad = self.cell.cpu().numpy()
+        self.cell.copy_(self._good_cell)
+        if self.runner is not None:
+            self.runner._set_cell(self.cell)
+        return bad
+
+    def stress(self):
+        """Stress (B,3,3) of the last step of a periodic force field (valid until the next call)."""
+        if not self.periodic or self.runner is None:
+            raise ValueError("stress needs a periodic force field that has run a step")
+        return self.runner.stress()
 
     def index_failed(self):
         """Did a completed step's in-graph index build outgrow the capacities (its outputs are NaN)?  Exact after the caller

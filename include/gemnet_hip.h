@@ -655,6 +655,25 @@ int gn_pbc_index_fill(const void* R, int is_f64, const void* cell, const uint8_t
                       int64_t* in_ptr, int32_t* in_edge, int64_t* cnt3, int64_t* off3, void* stream);
 int gn_pbc_index_trip(const int32_t* id_a, int64_t E, const int64_t* in_ptr, const int32_t* in_edge, const int64_t* off3,
                       int32_t* id3_reduce_ca, int32_t* id3_expand_ba, int32_t* Kidx3, void* stream);
+/* Capacity form of the periodic build (csrc/pbc_index.hip; additive, ABI 15): the periodic twin of gn_index_gpu_padded_t —
+ * image neighbour list, index arrays and model as ONE capturable graph; no read-back, every launch sized by the capacities.
+ * R (A,3), cell (>= B,3,3) float32 and pbc (B,3) uint8 on the device, read at replay time (the cell may change from step to
+ * step); mol_off (B+1), atom_mol (A) as above.  The real rows [0, E) / [0, T) are the canonical list above (float32
+ * distances), the rows behind them the pad rows of gemnet_pytorch_amd/padded.py (triplets-only layout: n_groups groups of 3
+ * dummy atoms behind atom a_cap; cell_offsets 0).  Pair search: one wavefront per atom, lanes over partner atoms, a wave-level
+ * scan placing the lanes' images in (i, j, n) order — deterministic, no atomics.  staging: 7 e_cap int32; ws:
+ * gn_pbc_index_ws_bytes(A, e_cap) bytes; e_cap, t_cap even; B <= A <= a_cap.
+ *   state (device int32[8]): [0] |= err (sticky)  [1] E  [2] T  [3] err of this call  [4] largest in-degree of a real atom
+ *   err bits: 1 E > e_cap, 2 T > t_cap, 4 pad triplets without a complete quad of pad edges, 8 more than max(deg_bound, 2)
+ *             pad edges into one dummy atom (counted exactly: both forward edges of a quad end on atom a), 16 a real atom's in-degree exceeds deg_bound, 32 a periodic axis needs more than
+ *             64 images per side (cutoff / cell height), 64 non-finite or degenerate cell (|det| < 1e-12)
+ * Every count is compared with its capacity BEFORE a kernel indexes with it; after an error the arrays keep the previous
+ * step's contents (valid indices) and gn_index_poison_f32 turns the step's outputs into NaN. */
+int64_t gn_pbc_index_ws_bytes(int A, int e_cap);
+int gn_pbc_index_padded_t(const float* R, const float* cell, const uint8_t* pbc, const int32_t* mol_off, const int32_t* atom_mol,
+                          int B, int A, double cutoff, void* ws, int e_cap, int t_cap, int a_cap, int n_groups, int deg_bound,
+                          int32_t* staging, int32_t* id_c, int32_t* id_a, int32_t* id_swap, int32_t* id_undir,
+                          int32_t* cell_offsets, int32_t* id3_reduce_ca, int32_t* id3_expand_ba, int32_t* state, void* stream);
 /* Geometry from edge vectors.  V (E,3) = gn_pbc_edge_vec_f32 (once per evaluation; the shift is constant in R).
  *   gn_edge_basis_vec_fwd_f32: D = |V|, rbf (E,NR) (may be NULL), rad (E,S,NR) — gn_edge_basis_fwd_f32 on V.
  *   gn_edge_basis_vec_bwd_f32: W = dE/dV (E,3) — gn_edge_basis_bwd_f32 on V.

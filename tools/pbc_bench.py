@@ -1,6 +1,12 @@
 #!/usr/bin/env python
 """Periodic forward + force + stress of GemNet-T on a water-like box, eager and replayed from a captured graph (runtime.
 ForceGraphs), against the molecular forward + force on the same positions (no cell; fewer edges: no image pairs).
+An MD loop on the same box — a short random walk of the positions, so that the neighbour list really changes — is timed two ways:
+`md_eager_ms`: what `md.predict_periodic` did per step before the in-graph list (a new PeriodicGraphBuilder, the list with its two
+size read-backs, ONE eager forward); `md_graph_exact_ms`: `runtime.DynamicForceField(cell=)`, list + model as one replayed graph,
+in the default mode (`exact=True`: the host waits for every step and reads the report of its index build — what `predict()`
+runs); `md_graph_ms`: the same with `exact=False` (nothing waits; comparable with `graph_periodic_ms`); `recaptures`: graphs
+captured after the first.
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -46,6 +52,30 @@ def timed(fn, steps, warmup):
     return t0.elapsed_time(t1) / steps
 
 
+def make_model(cutoff=5.0):
+    """The 4-block, 128-wide GemNet-T of this tool (seeded weights, fitted scale factors), on the host."""
+    from gemnet_pytorch_amd.model.gemnet import GemNet
+    from oracle import gemnet_oracle as GO
+    cfg = dict(num_spherical=7, num_radial=6, num_blocks=4, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
+               emb_size_quad=32, emb_size_rbf=16, emb_size_cbf=16, emb_size_sbf=32, emb_size_bil_quad=32, emb_size_bil_trip=64,
+               num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True, cutoff=cutoff)
+    scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
+    params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
+    model = GemNet(**cfg, scale_file=scale_file)
+    model.load_state_dict(GO.expand_to_reference_state_dict(params))
+    return model
+
+
+def random_walk(R, n, sigma=0.02, seed=5):
+    """n + 1 position sets (float32, on the device): R and n steps of a Gaussian walk — the neighbour list changes on the way."""
+    rs = np.random.RandomState(seed)
+    out, R = [], np.asarray(R, np.float64)
+    for _ in range(n + 1):
+        out.append(torch.tensor(R, dtype=torch.float32, device="cuda"))
+        R = R + rs.normal(0, sigma, R.shape)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=4)
@@ -56,19 +86,10 @@ def main():
     import __graft_entry__ as ge
     ge.build()
     from gemnet_pytorch_amd.index_device import build_indices_device
-    from gemnet_pytorch_amd.model.gemnet import GemNet
     from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
-    from gemnet_pytorch_amd.runtime import ForceGraphs
-    from oracle import gemnet_oracle as GO
+    from gemnet_pytorch_amd.runtime import DynamicForceField, ForceGraphs
 
-    cfg = dict(num_spherical=7, num_radial=6, num_blocks=4, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
-               emb_size_quad=32, emb_size_rbf=16, emb_size_cbf=16, emb_size_sbf=32, emb_size_bil_quad=32, emb_size_bil_trip=64,
-               num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True, cutoff=args.cutoff)
-    scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
-    params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
-    model = GemNet(**cfg, scale_file=scale_file)
-    model.load_state_dict(GO.expand_to_reference_state_dict(params))
-    model = model.to("cuda").eval()
+    model = make_model(args.cutoff).to("cuda").eval()
 
     R, Z, cell = water_box(args.side)
     A = len(R)
@@ -91,6 +112,29 @@ def main():
     out["graph_molecular_ms"] = timed(fm.replay, args.steps, args.warmup)
     for k in ("periodic", "molecular"):
         out[f"graph_{k}_ns_per_triplet"] = 1e6 * out[f"graph_{k}_ms"] / max(out[f"triplets_{k}"], 1)
+    # the MD loop: positions walk, the list is rebuilt every step
+    walk = random_walk(R, args.steps + args.warmup)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % len(walk)
+        return walk[state["i"]]
+
+    def md_eager():
+        Rs = nxt()
+        ix = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rs, celld, dtype=torch.int32)
+        return model(dict(R=Rs, Z=Zd, N=Nd, cell=celld, **ix), stress=True)
+
+    out["md_eager_ms"] = timed(md_eager, args.steps, args.warmup)
+    ff = DynamicForceField(model, Zd, [A], args.cutoff, 10.0, cell=celld)
+    ff(walk[0])
+    state["i"] = 0
+    out["md_graph_ms"] = timed(lambda: ff(nxt(), exact=False), args.steps, args.warmup)
+    torch.cuda.synchronize()
+    out["md_graph_exact_ms"] = timed(lambda: ff(nxt()), args.steps, args.warmup)
+    out["recaptures"] = int(ff.recaptures)
+    out["md_index_failed"] = bool(ff.index_failed())
+    out["md_sizes"] = list(ff.runner.index_sizes())
     print(json.dumps(out))
 
 
