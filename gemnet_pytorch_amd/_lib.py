@@ -159,6 +159,14 @@ SIGNATURES = {
     "gn_trip_basis_vec_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
     "gn_trip_basis_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp],
     "gn_pbc_stress_f32": [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp],
+    # force training on periodic batches (csrc/pbc_train.hip)
+    "gn_dist_vec_fwd_f32": [_vp, _vp, _i64, _vp],
+    "gn_dist_vec_bwd_f32": [_vp, _vp, _vp, _i64, _vp],
+    "gn_dist_vec_jvp_f32": [_vp, _vp, _vp, _i64, _vp],
+    "gn_angle_vec_fwd_f32": [_vp, _vp, _vp, _vp, _i64, _vp],
+    "gn_angle_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "gn_angle_vec_jvp_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "gn_pbc_force_stress_adj_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i64, _vp],
 }
 
 _lib = None

@@ -709,6 +709,80 @@ def angle_jvp(R, tR, g, tc, ta, tb, want_theta=True, want_H=True):
     return thd, Hc, Hb
 
 
+# --- the same geometry on the edge vectors V (E,3) of a periodic batch (csrc/pbc_train.hip): force training with a cell
+def dist_vec_fwd(V):
+    """D (E,) = |V|."""
+    require_device(V)
+    V = _f32c(V)
+    D = torch.empty(V.shape[0], device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_dist_vec_fwd_f32(ptr(V), ptr(D), V.shape[0], stream()), "gn_dist_vec_fwd_f32")
+    return D
+
+
+def dist_vec_bwd(gD, V):
+    """-> W (E,3) = gD dD/dV."""
+    require_device(gD, V)
+    gD, V = _f32c(gD), _f32c(V)
+    W = torch.empty_like(V)
+    check(_lib.load().gn_dist_vec_bwd_f32(ptr(gD), ptr(V), ptr(W), V.shape[0], stream()), "gn_dist_vec_bwd_f32")
+    return W
+
+
+def dist_vec_jvp(V, tV):
+    """-> Ddot (E,) = V / |V| . tV: the tangent of the distances along tV (E,3)."""
+    require_device(V, tV)
+    V, tV = _f32c(V), _f32c(tV)
+    assert tV.shape == V.shape
+    Dd = torch.empty(V.shape[0], device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_dist_vec_jvp_f32(ptr(V), ptr(tV), ptr(Dd), V.shape[0], stream()), "gn_dist_vec_jvp_f32")
+    return Dd
+
+
+def angle_vec_fwd(V, red, exp):
+    """theta (T,) between u = -V[red] and v = -V[exp] (the image-aware c <- a -> b)."""
+    require_device(V, red, exp)
+    V = _f32c(V)
+    th = torch.empty(red.shape[0], device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec_fwd_f32(ptr(V), ptr(red), ptr(exp), ptr(th), red.shape[0], stream()), "gn_angle_vec_fwd_f32")
+    return th
+
+
+def angle_vec_bwd(g, V, red, exp):
+    """-> Gu, Gv (T,3) = g dtheta/du, g dtheta/dv."""
+    require_device(g, V)
+    g, V = _f32c(g), _f32c(V)
+    T = red.shape[0]
+    Gu = torch.empty((T, 3), device=V.device, dtype=torch.float32)
+    Gv = torch.empty((T, 3), device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec_bwd_f32(ptr(g), ptr(V), ptr(red), ptr(exp), ptr(Gu), ptr(Gv), T, stream()),
+          "gn_angle_vec_bwd_f32")
+    return Gu, Gv
+
+
+def angle_vec_jvp(V, tV, red, exp):
+    """-> thdot (T,): the tangent of the angles along tV (E,3)."""
+    require_device(V, tV)
+    V, tV = _f32c(V), _f32c(tV)
+    assert tV.shape == V.shape
+    thd = torch.empty(red.shape[0], device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec_jvp_f32(ptr(V), ptr(tV), None, ptr(red), ptr(exp), ptr(thd), red.shape[0], stream()),
+          "gn_angle_vec_jvp_f32")
+    return thd
+
+
+def pbc_force_stress_adj(gF, gS, V, id_c, id_a, batch_seg, cell, scale=-1.0):
+    """-> gG (E,3): the adjoint of F = segsum(G, id_a) - segsum(G, id_c) and S = gn_pbc_stress_f32(V, G, scale) w.r.t. G, from
+    gF (A,3) and gS (B,3,3) or None."""
+    require_device(gF, V, cell)
+    gF, V, cell = _f32c(gF), _f32c(V), _f32c(cell)
+    gS = None if gS is None else _f32c(gS)
+    assert gS is None or gS.shape == cell.shape
+    gG = torch.empty_like(V)
+    check(_lib.load().gn_pbc_force_stress_adj_f32(ptr(gF), ptr(gS), ptr(V), ptr(id_c), ptr(id_a), ptr(batch_seg), ptr(cell),
+                                                  float(scale), ptr(gG), V.shape[0], stream()), "gn_pbc_force_stress_adj_f32")
+    return gG
+
+
 class ChainProgram:
     """A program for gn_chain_f32: ops over the three LDS slots of a row tile (see include/gemnet_hip.h).
     Operands named `mul/res/res2` are either an int (LDS slot) or a tensor (global (M,N))."""

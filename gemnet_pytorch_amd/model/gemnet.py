@@ -93,6 +93,9 @@ class GemNet(torch.nn.Module):
         self.triplets_only = triplets_only
         self.num_spherical = num_spherical
         self.force_graph = None  # None: auto (training & grad enabled); True/False: forced
+        # opt-in: a periodic batch (inputs["cell"]) with a second-order force graph returns (E, F[, S]) with an autograd graph
+        # to the parameters (_forward_periodic_train; training.periodic.PeriodicTrainStep sets it).  False: such a call raises
+        self.periodic_training = False
         # arithmetic of the LDS-resident Dense stacks: None = the package default ("h3": fp32 operands as two fp16 planes,
         # three products), "split6" = three bf16 planes / six products (fp32 exponent range), "f32" = the f32-input MFMA — all
         # three at fp32 accuracy (force MAE 1e-6 .. 4e-6 eV/A against float64).  Single-plane bf16 / three-product modes exist
@@ -264,9 +267,21 @@ class GemNet(torch.nn.Module):
             # force training: distances and triplet angles as twice-differentiable kernels (ops_train._Dist2 / _Angle2),
             # the bases on their closed derivative kernels
             from .. import ops_train
-            D_ca, V_ca = ops_train.distances(R, plan.id_c, plan.id_a), None
+            if V is not None:     # periodic batch: the same pair of kernels on the edge vectors (_DistVec2 / _AngleVec2)
+                D_ca, V_ca = ops_train.distances_vec(V), None
+                angles = ops_train.triplet_angles_vec(V, plan.trip)
+            else:
+                D_ca, V_ca = ops_train.distances(R, plan.id_c, plan.id_a), None
+                angles = ops_train.triplet_angles(R, plan.t_c, plan.t_a, plan.t_b)
             rbf = self.rbf_basis(D_ca)
-            rad3, sph3 = b3(D_ca, ops_train.triplet_angles(R, plan.t_c, plan.t_a, plan.t_b))
+            rad3, sph3 = b3(D_ca, angles)
+        elif V is not None:
+            # periodic batch on the composite closure (GEMNET_TRAIN2=0, matmul_precision="f32"): u = -V[reduce edge],
+            # v = -V[expand edge], the image-aware c <- a -> b of pbc.trip_basis
+            D_ca, V_ca = torch.sqrt(torch.sum(V ** 2, dim=1)), None
+            rbf = self.rbf_basis(D_ca)
+            rad3, sph3 = b3(D_ca, self.calculate_neighbor_angles(-ops.gather_rows(V, plan.trip.reduce),
+                                                                 -ops.gather_rows(V, plan.trip.expand)))
         else:
             D_ca, V_ca = self.calculate_interatomic_vectors(R, plan.id_c, plan.id_a)
             rbf = self.rbf_basis(D_ca)
@@ -409,6 +424,8 @@ class GemNet(torch.nn.Module):
         """E, F as the reference's `GemNet.forward` (gemnet.py:453-615).
         Periodic batches (`cell` (B,3,3) + `cell_offsets` (E,3), pbc.py; GemNet-T, eval-mode forces by autograd): the edge
         vectors carry the image shift; `stress=True` returns (E, F, S) with S (B,3,3) = dE/d(strain) / |det cell| (eV/A^3).
+        With `periodic_training = True` a call that builds the second-order force graph (training mode with grad enabled, or
+        `force_graph = True`) returns the same outputs with an autograd graph to the parameters; without it that call raises.
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
         value beyond 65 504 becomes inf — fitted scale factors keep activations O(1), a model with
         unfitted ones (the starting state of fit_scaling.py, foreign checkpoints) need not.  A non-finite result of an eager
@@ -525,12 +542,15 @@ class GemNet(torch.nn.Module):
         mode = self.matmul_precision or K_chain_mode()
         # (one target: with several, each target's force pass would need its own record of the S2 / S3 sweeps per stack and
         #  one source term per target in S4 — those models train on the composite closure)
-        t2 = bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
+        # (and widths the split-operand chain kernel takes in every sweep, see _train2_widths_ok: the CPU emulation takes any)
+        t2 = (bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
+              and (not R.is_cuda or self._train2_widths_ok()))
         if cell is not None:
-            if graph:
+            if graph and not getattr(self, "periodic_training", False):
                 raise NotImplementedError("periodic cells: forces by autograd on the first-order (eval) path only; training "
-                                          "with a cell (a second-order force graph) is not supported")
-            out = self._forward_periodic(R, plan, cell)
+                                          "with a cell (a second-order force graph) is opt-in: set "
+                                          "model.periodic_training = True (training.periodic.PeriodicTrainStep does)")
+            out = self._forward_periodic_train(R, plan, cell, t2) if graph else self._forward_periodic(R, plan, cell)
             if late is not None:
                 plan.join_late()
             return out
@@ -561,6 +581,21 @@ class GemNet(torch.nn.Module):
             plan.join_late()
         return E_mol, F_j
 
+    def _train2_widths_ok(self):
+        """The adjoint and tangent sweeps of the fused training form are GEMMs whose N is an embedding width: the split-operand
+        chain kernel takes multiples of 16 (kernels.chain_split_supported) and its f32 sibling carries no second-order source
+        terms, so a model with another embedding width (test-sized models: 8-wide radial / triplet embeddings) trains on the
+        composite closure as a whole."""
+        b = self.int_blocks[0]
+        t = b.trip_interaction
+        widths = [self.atom_emb.embeddings.weight.shape[1], self.mlp_rbf3.weight.shape[0], self.mlp_cbf3.weight.shape[2],
+                  *t.down_projection.weight.shape, t.up_projection_ca.weight.shape[1]]
+        if not self.triplets_only:
+            q = b.quad_interaction
+            widths += [self.mlp_rbf4.weight.shape[0], self.mlp_cbf4.weight.shape[0], self.mlp_sbf4.weight.shape[2],
+                       q.down_projection.weight.shape[0], q.up_projection_ca.weight.shape[1]]
+        return all(int(w) % 16 == 0 for w in widths)
+
     def _check_periodic(self, inputs):
         """What a cell is not supported with raises (no silent molecular result)."""
         if not self.triplets_only:
@@ -590,6 +625,22 @@ class GemNet(torch.nn.Module):
         F = pbc.forces(G, plan)
         S = pbc.stress(V.detach(), G, plan, cell)
         return E_mol.detach(), F, S
+
+    def _forward_periodic_train(self, R, plan, cell, t2):
+        """E, F, S of a periodic batch with an autograd graph to the parameters (`periodic_training`): E under the context of
+        the molecular training branch, G = -dE/dV with create_graph=True, and F, S linear in G through ONE differentiable
+        Function (pbc.force_stress: its backward is the adjoint kernel of csrc/pbc_train.hip).  V is a private leaf — positions
+        and cell never join an autograd graph — so `loss.backward()` reaches the parameters through G alone."""
+        from .. import pbc
+        V = pbc.edge_vectors(R, plan, cell).requires_grad_(True)
+        with ops.weight_cache(self._wcache), ops.fused_first_order(False), ops.param_grads(True), \
+                ops.train2(t2, self._packs if (t2 and R.is_cuda) else None), ops.chain_mode(self.matmul_precision), \
+                ops.position_graph(False), torch.enable_grad():
+            E_mol, _, _ = self._energy(R.detach(), plan, V=V)
+            with ops.param_grads(False):  # only dE/dV is needed here
+                G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0), create_graph=True)[0]
+            F, S = pbc.force_stress(G, V.detach(), plan, cell)
+        return E_mol, F, S
 
     def _cotangent(self, E_mol, target):
         """Constant -1 in column `target` (zeros elsewhere) shaped like E_mol, cached per (shape, device)."""

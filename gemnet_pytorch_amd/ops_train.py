@@ -1181,3 +1181,94 @@ class _QuadAngles2B(torch.autograd.Function):
 
 def quad_angles(R, ri_c, ri_a, ri_b, ri_d, plan=None):
     return _QuadAngles2.apply(R, ri_c, ri_a, ri_b, ri_d, plan)
+
+
+# ============================================================ distances and triplet angles from the edge vectors of a periodic batch
+class _DistVec2(torch.autograd.Function):
+    """D[e] = |V[e]| on the edge vectors of a periodic batch (pbc.edge_vectors), twice differentiable: _Dist2 on V (csrc/
+    pbc_train.hip).  V is the private leaf the force and the stress are taken from and never joins a caller's graph, so the
+    tangent pass returns the cotangent of gD only (no second-order term w.r.t. V)."""
+
+    @staticmethod
+    def forward(ctx, V):
+        ctx.save_for_backward(V)
+        return K.dist_vec_fwd(V)
+
+    @staticmethod
+    def backward(ctx, gD):
+        (V,) = ctx.saved_tensors
+        if gD is None or not ctx.needs_input_grad[0]:
+            return None
+        if torch.is_grad_enabled():
+            return _DistVec2B.apply(gD, V)
+        return K.dist_vec_bwd(gD.contiguous(), V)
+
+
+class _DistVec2B(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gD, V):
+        gD = gD.contiguous()
+        ctx.save_for_backward(V)
+        return K.dist_vec_bwd(gD, V)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tV):
+        (V,) = ctx.saved_tensors
+        if tV is None or not ctx.needs_input_grad[0]:
+            return None, None
+        return K.dist_vec_jvp(V, tV.contiguous()), None
+
+
+def distances_vec(V):
+    return _DistVec2.apply(V)
+
+
+def _edges2(Gu, Gv, trip, n_edges):
+    """Per-triplet terms (u = -V[reduce edge], v = -V[expand edge]) -> edges, one multi-term segmented sum."""
+    return K.segsum_multi([(Gu, *trip.reduce.csr, -1.0), (Gv, *trip.expand.csr, -1.0)], n_edges)
+
+
+class _AngleVec2(torch.autograd.Function):
+    """theta[t] = atan2(max(|u x v|, 1e-9), u . v), u = -V[reduce edge], v = -V[expand edge] (the image-aware c <- a -> b of
+    pbc.trip_basis), twice differentiable: _Angle2 on V."""
+
+    @staticmethod
+    def forward(ctx, V, trip):
+        ctx.save_for_backward(V)
+        ctx.trip = trip
+        return K.angle_vec_fwd(V, trip.reduce.idx32, trip.expand.idx32)
+
+    @staticmethod
+    def backward(ctx, g):
+        (V,) = ctx.saved_tensors
+        trip = ctx.trip
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None
+        if torch.is_grad_enabled():
+            return _AngleVec2B.apply(g, V, trip), None
+        Gu, Gv = K.angle_vec_bwd(g.contiguous(), V, trip.reduce.idx32, trip.expand.idx32)
+        return _edges2(Gu, Gv, trip, V.shape[0]), None
+
+
+class _AngleVec2B(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, V, trip):
+        g = g.contiguous()
+        ctx.save_for_backward(V)
+        ctx.trip = trip
+        Gu, Gv = K.angle_vec_bwd(g, V, trip.reduce.idx32, trip.expand.idx32)
+        return _edges2(Gu, Gv, trip, V.shape[0])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tV):
+        (V,) = ctx.saved_tensors
+        trip = ctx.trip
+        if tV is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        return K.angle_vec_jvp(V, tV.contiguous(), trip.reduce.idx32, trip.expand.idx32), None, None
+
+
+def triplet_angles_vec(V, trip):
+    return _AngleVec2.apply(V, trip)

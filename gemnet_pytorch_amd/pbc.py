@@ -1,5 +1,7 @@
-"""Periodic cells for GemNet-T (triplets_only=True, forces by autograd, first-order path): the image neighbour list, the
-shifted edge geometry and the stress (csrc/pbc.hip; conventions in include/gemnet_hip.h).
+"""Periodic cells for GemNet-T (triplets_only=True, forces by autograd): the image neighbour list, the shifted edge geometry
+and the stress (csrc/pbc.hip; conventions in include/gemnet_hip.h).  The Functions of the first-order (eval) path are
+once-differentiable; training (GemNet.periodic_training) differentiates the energy through ops_train._DistVec2 / _AngleVec2
+instead and takes forces and stress from `force_stress` below (csrc/pbc_train.hip).
 
     builder = PeriodicGraphBuilder(N, cutoff, pbc=[[True, True, True]])          # N: atoms per structure (host)
     idx = builder(R, cell)                                                       # R (A,3), cell (B,3,3) on the device
@@ -213,3 +215,34 @@ def stress(V, G, plan, cell):
     check(_lib.load().gn_pbc_stress_f32(ptr(V), ptr(G.contiguous()), ptr(perm), ptr(seg), ptr(cell), plan.n_mol, -1.0, ptr(S),
                                         stream()), "gn_pbc_stress_f32")
     return S
+
+
+class _ForceStress(torch.autograd.Function):
+    """G = -dE/dV (E,3) -> F (A,3), S (B,3,3): `forces` + `stress`, differentiable in G for the training step (V and the cell are
+    constants: positions and cell never join an autograd graph).  Backward: one launch of the exact adjoint,
+    gG_e = gF[a(e)] - gF[c(e)] - 1/|det cell_b| V_e . gS_b (gn_pbc_force_stress_adj_f32)."""
+
+    @staticmethod
+    def forward(ctx, G, V, plan, cell):
+        ctx.set_materialize_grads(False)
+        G = G.contiguous()
+        ctx.save_for_backward(V, cell)
+        ctx.plan = plan
+        return forces(G, plan), stress(V, G, plan, cell)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gS):
+        V, cell = ctx.saved_tensors
+        plan = ctx.plan
+        if gF is None and gS is None:
+            return None, None, None, None
+        if gF is None:
+            gF = torch.zeros((plan.n_atoms, 3), device=V.device, dtype=V.dtype)
+        gG = K.pbc_force_stress_adj(gF, gS, V, plan.id_c.idx32, plan.id_a.idx32, plan.batch_seg.idx32, cell.detach(), -1.0)
+        return gG, None, None, None
+
+
+def force_stress(G, V, plan, cell):
+    """(F, S) from G = -dE/dV with an autograd graph through G (force training on periodic batches)."""
+    return _ForceStress.apply(G, V, plan, cell)

@@ -160,7 +160,10 @@ class TrainStep:
         return float(n_mol), float(n_atoms)
 
     def loss(self, E, F, targets):
-        B, A = self._counts(E.shape[0], F.shape[0], E.device)
+        return self._energy_force_loss(E, F, targets, *self._counts(E.shape[0], F.shape[0], E.device))
+
+    def _energy_force_loss(self, E, F, targets, B, A):
+        """The loss for the global counts (B molecules, A atoms) — one exchange of the counts serves every term of a subclass."""
         if USE_FUSED_LOSS and E.is_cuda and E.dtype == torch.float32:
             # one launch for the loss and its cotangents (csrc/optim.hip: force_loss_kernel) instead of 16 + 16 ATen nodes
             return _ForceLoss.apply(E, F, targets["E"], targets["F"], (1 - self.rho) / (B * E.shape[1]), self.rho / A, None, None)

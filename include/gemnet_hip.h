@@ -697,6 +697,33 @@ int gn_trip_basis_vec_bwd_f32(const float* gY, const float* V, const int32_t* re
 int gn_pbc_stress_f32(const float* V, const float* G, const int32_t* perm, const int32_t* seg_off, const float* cell, int B,
                       float scale, float* S, void* stream);
 
+/* ---- force training on periodic batches (csrc/pbc_train.hip; additive, ABI 15) ---------------------------------------------
+ * The twice-differentiable geometry of gn_dist_* / gn_angle_* on the edge vectors V (E,3) of a periodic batch, for
+ * `loss.backward()` through G = -dE/dV (create_graph=True), and the adjoint of the map G -> (F, S):
+ *   D[e]      = |V[e]|  (sqrtf(sum V^2), as gn_dist_fwd_f32)                               gn_dist_vec_fwd_f32
+ *   W[e,:]    = gD[e] V[e] / |V[e]|                                                         gn_dist_vec_bwd_f32
+ *   Ddot[e]   = V[e] / |V[e]| . tV[e]                                                       gn_dist_vec_jvp_f32
+ *   theta[t]  = atan2(max(|u x v|, 1e-9), u . v), u = -V[red[t]], v = -V[exp[t]]            gn_angle_vec_fwd_f32
+ *               (the convention of gn_trip_basis_vec_fwd_f32)
+ *   Gu, Gv    = g dtheta/du, g dtheta/dv (T,3); dE/dV = -segsum(Gu by reduce edge) - segsum(Gv by expand edge)
+ *               (gn_segsum_multi_f32)                                                       gn_angle_vec_bwd_f32
+ *   thdot[t]  = dtheta . (du, dv), du = -tV[red[t]], dv = -tV[exp[t]]                       gn_angle_vec_jvp_f32
+ *               (g: the slot of gn_angle_jvp_f32's adjoint, not read — V carries no second-order terms; may be NULL)
+ *   gG[e,j]   = gF[id_a[e],j] - gF[id_c[e],j] + scale / |det cell_b| sum_i V[e,i] gS[b,i,j],  b = batch_seg[id_a[e]]
+ *               — the exact adjoint of F = segsum(G, id_a) - segsum(G, id_c) and gn_pbc_stress_f32(scale) in one launch;
+ *               gS (B,3,3) may be NULL                                                      gn_pbc_force_stress_adj_f32
+ * One thread per edge / triplet, no atomics; E = 0 / T = 0 return 0 without a launch. */
+int gn_dist_vec_fwd_f32(const float* V, float* D, int64_t E, void* stream);
+int gn_dist_vec_bwd_f32(const float* gD, const float* V, float* W, int64_t E, void* stream);
+int gn_dist_vec_jvp_f32(const float* V, const float* tV, float* Ddot, int64_t E, void* stream);
+int gn_angle_vec_fwd_f32(const float* V, const int32_t* red, const int32_t* exp, float* theta, int64_t T, void* stream);
+int gn_angle_vec_bwd_f32(const float* g, const float* V, const int32_t* red, const int32_t* exp, float* Gu, float* Gv, int64_t T,
+                         void* stream);
+int gn_angle_vec_jvp_f32(const float* V, const float* tV, const float* g, const int32_t* red, const int32_t* exp, float* thdot,
+                         int64_t T, void* stream);
+int gn_pbc_force_stress_adj_f32(const float* gF, const float* gS, const float* V, const int32_t* id_c, const int32_t* id_a,
+                                const int32_t* batch_seg, const float* cell, float scale, float* gG, int64_t E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,9 @@ size read-backs, ONE eager forward); `md_graph_exact_ms`: `runtime.DynamicForceF
 in the default mode (`exact=True`: the host waits for every step and reads the report of its index build — what `predict()`
 runs); `md_graph_ms`: the same with `exact=False` (nothing waits; comparable with `graph_periodic_ms`); `recaptures`: graphs
 captured after the first.
+`--train` times the TRAINING step instead (training/periodic.PeriodicTrainStep: energy + force + stress loss, rho_stress > 0, fused
+optimizer) on the same box, eager (`train_eager_ms`) and replayed from its captured graph (`train_graph_ms`), next to the
+molecular `TrainStep` on the same atoms without a cell (`train_molecular_*_ms`: fewer edges, no stress).
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -76,12 +79,32 @@ def random_walk(R, n, sigma=0.02, seed=5):
     return out
 
 
+def train_times(per, mol, args):
+    """Eager and captured step time of PeriodicTrainStep on `per` and of the molecular TrainStep on `mol` (optimizer included)."""
+    from gemnet_pytorch_amd.training.ddp import TrainStep
+    from gemnet_pytorch_amd.training.periodic import PeriodicTrainStep
+    g = torch.Generator().manual_seed(2)
+    A = per["R"].shape[0]
+    targets = {"E": torch.randn(1, 1, generator=g).cuda(), "F": torch.randn(A, 3, generator=g).cuda(),
+               "S": 0.01 * torch.randn(1, 3, 3, generator=g).cuda()}
+    out = {}
+    for key, inputs, make in (("train", per, lambda m: PeriodicTrainStep(m, rho_stress=0.01, fused_optimizer=True)),
+                              ("train_molecular", mol, lambda m: TrainStep(m, fused_optimizer=True))):
+        ts = make(make_model(args.cutoff).to("cuda"))
+        out[f"{key}_eager_ms"] = timed(lambda: ts(inputs, targets), args.steps, args.warmup)
+        ts.capture(inputs, targets)
+        out[f"{key}_graph_ms"] = timed(lambda: ts(inputs, targets), args.steps, args.warmup)
+        out[f"{key}_loss"] = float(ts.last_loss)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=4)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cutoff", type=float, default=5.0)
+    ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -104,6 +127,10 @@ def main():
     out = {"atoms": A, "cutoff": args.cutoff, "edges_periodic": int(idx["id_a"].shape[0]),
            "triplets_periodic": int(idx["id3_reduce_ca"].shape[0]), "edges_molecular": int(mol["id_a"].shape[0]),
            "triplets_molecular": int(mol["id3_reduce_ca"].shape[0])}
+    if args.train:
+        out.update(train_times(per, mol, args))
+        print(json.dumps(out))
+        return
     out["eager_periodic_ms"] = timed(lambda: model(per, stress=True), args.steps, args.warmup)
     out["eager_molecular_ms"] = timed(lambda: model(mol), args.steps, args.warmup)
     fp = ForceGraphs(model, [per])
