@@ -617,6 +617,67 @@ def edge_basis_bwd(gD, g_rbf, g_rad, R, idx_c, idx_a, freq, z, nrm, cutoff, p):
     return W
 
 
+RADIAL_HEAD_SHAPE = (6, 7, 16)      # (NR, S, columns) the kernels are built for
+
+
+def radial_head_weights(W_rbf3, W_rbf_h, W_rbf_out, W_cbf3):
+    """wcat (3 + S, NR, NI) of gn_radial_head_*: the three (NI, NR) Dense weights transposed, then the (S, NR, NI) weight of the
+    circular-basis down projection."""
+    S, NR, NI = W_cbf3.shape
+    for W in (W_rbf3, W_rbf_h, W_rbf_out):
+        if tuple(W.shape) != (NI, NR):
+            raise ValueError(f"radial head: Dense weight of shape {tuple(W.shape)}, expected {(NI, NR)}")
+    return torch.cat([W_rbf3.t()[None], W_rbf_h.t()[None], W_rbf_out.t()[None], W_cbf3], 0).to(torch.float32).contiguous()
+
+
+def _radial_head_args(R, idx_c, idx_a, freq, z, nrm, wcat):
+    require_device(R, idx_c, idx_a, freq, z, nrm, wcat)
+    S, NR = z.shape
+    if wcat.dim() != 3 or (NR, S, wcat.shape[2]) != RADIAL_HEAD_SHAPE or tuple(wcat.shape[:2]) != (3 + S, NR):
+        raise ValueError(f"radial head: tables {tuple(z.shape)} / weights {tuple(wcat.shape)}; the kernel takes "
+                         f"(S, NR) = (7, 6) and wcat (10, 6, 16)")
+    if freq.shape != (NR,) or nrm.shape != z.shape or nrm.dtype != torch.float64:
+        raise ValueError("radial head: freq (NR,) f32, z (S, NR) f32 and nrm (S, NR) f64 expected")
+    if idx_c.shape != idx_a.shape or idx_c.dim() != 1 or idx_c.dtype != torch.int32 or idx_a.dtype != torch.int32:
+        raise ValueError("radial head: id_c / id_a are (E,) int32")
+    return _f32c(R), idx_c.contiguous(), idx_a.contiguous(), _f32c(freq), _f32c(z), nrm.contiguous(), _f32c(wcat)
+
+
+def radial_head_fwd(R, idx_c, idx_a, freq, z, nrm, wcat, cutoff, p):
+    """-> rbf (E,NR), rbf3, rbf_h, rbf_out (E,16), rbf_W1 (E,S,16): distances, both radial bases and their four frozen
+    projections in one launch (gn_radial_head_fwd_f32; wcat from `radial_head_weights`)."""
+    R, idx_c, idx_a, freq, z, nrm, wcat = _radial_head_args(R, idx_c, idx_a, freq, z, nrm, wcat)
+    E = idx_c.shape[0]
+    NR, S, NI = RADIAL_HEAD_SHAPE
+    new = lambda *shape: torch.empty(shape, device=R.device, dtype=torch.float32)   # noqa: E731
+    rbf, rbf3, rbf_h, rbf_out, rbf_W1 = new(E, NR), new(E, NI), new(E, NI), new(E, NI), new(E, S, NI)
+    check(_lib.load().gn_radial_head_fwd_f32(ptr(R), ptr(idx_c), ptr(idx_a), ptr(freq), ptr(z), ptr(nrm), ptr(wcat), ptr(rbf),
+                                             ptr(rbf3), ptr(rbf_h), ptr(rbf_out), ptr(rbf_W1), E, NR, S, NI, cutoff, p,
+                                             stream()), "gn_radial_head_fwd_f32")
+    return rbf, rbf3, rbf_h, rbf_out, rbf_W1
+
+
+def radial_head_bwd(g_rbf, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1, R, idx_c, idx_a, freq, z, nrm, wcat, cutoff, p):
+    """-> W (E,3), the per-edge position gradient of `radial_head_fwd` (dE/dR = segsum(W, id_a) - segsum(W, id_c)); any
+    cotangent may be None."""
+    R, idx_c, idx_a, freq, z, nrm, wcat = _radial_head_args(R, idx_c, idx_a, freq, z, nrm, wcat)
+    E = idx_c.shape[0]
+    NR, S, NI = RADIAL_HEAD_SHAPE
+    gs = []
+    for g, shape in ((g_rbf, (E, NR)), (g_rbf3, (E, NI)), (g_rbf_h, (E, NI)), (g_rbf_out, (E, NI)), (g_rbf_W1, (E, S, NI))):
+        if g is not None:
+            require_device(g)
+            if tuple(g.shape) != shape:
+                raise ValueError(f"radial head: cotangent of shape {tuple(g.shape)}, expected {shape}")
+            g = _f32c(g)
+        gs.append(g)
+    W = torch.empty((E, 3), device=R.device, dtype=torch.float32)
+    check(_lib.load().gn_radial_head_bwd_f32(*[ptr(g) for g in gs], ptr(R), ptr(idx_c), ptr(idx_a), ptr(freq), ptr(z), ptr(nrm),
+                                             ptr(wcat), ptr(W), E, NR, S, NI, cutoff, p, stream()),
+          "gn_radial_head_bwd_f32")
+    return W
+
+
 def trip_basis_fwd(R, tc, ta, tb, S, want_theta=False):
     """-> Y (T,S) = Y_l0(angle c<-a->b), theta (T,)|None   (gemnet.py:288-311,420-451 + basis_layers.py:130-131)."""
     require_device(R, tc, ta, tb)

@@ -222,6 +222,14 @@ class GemNet(torch.nn.Module):
         fork = side is not None and ops.is_fused() and T
         main = torch.cuda.current_stream(R.device) if fork else None
         h = terms = rbf_W1_3 = rbf_h = rbf_out = None
+        # Fused radial head (ops.radial_head): the four radial projections leave the basis kernel, rad3 never exists, and
+        # their adjoints, the sum of the rbf gradients and the basis adjoint are one launch.  GemNet-Q (needs rad3),
+        # periodic batches, direct forces, trainable weights and other widths keep the launches below.
+        proj = (self.mlp_rbf3, self.mlp_rbf_h, self.mlp_rbf_out)
+        head = (ops.is_fused() and T and V is None and not self.direct_forces and R.is_cuda
+                and all(d.bias is None and not d.act for d in proj)
+                and ops.radial_head_supported(tuple(d.weight for d in proj) + (self.mlp_cbf3.weight,), b3.z_ln,
+                                              self.rbf_basis.frequencies))
         if ops.is_fused():
             if fork:
                 side.wait_stream(main)
@@ -236,11 +244,22 @@ class GemNet(torch.nn.Module):
                 from .. import pbc
                 D_ca, rbf, rad3 = pbc.edge_basis(V, self.rbf_basis.frequencies, b3.z_ln, b3.n_ln, b3.cutoff, b3.p)
                 V_ca = None
+            elif head:
+                rbf, rbf3, rbf_h, rbf_out, rbf_W1_3 = self._radial_head(R, plan, proj)
+                V_ca = None
             else:
                 D_ca, V_ca, rbf, rad3 = ops.edge_basis(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a,
                                                        b3.z_ln, b3.n_ln, b3.cutoff, b3.p,
                                                        want_V=self.direct_forces)
-            if fork:
+            if fork and head:
+                # everything the side stream consumes of the head is rbf_out, and every output block orders itself behind
+                # the main stream before it reads it (out_block below)
+                if _RBF_OUT_ACC:
+                    rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
+                main.wait_event(ev_a)
+                for t in (sph3, h) + tuple(terms):
+                    t.record_stream(main)
+            elif fork:
                 ev_1 = torch.cuda.Event()
                 ev_1.record(main)
                 side.wait_event(ev_1)
@@ -345,8 +364,13 @@ class GemNet(torch.nn.Module):
         else:
             rbf4 = cbf4 = sbf4 = None
         # radial projections shared by all blocks: their gradients are summed inside the consumers' backward kernels
-        rbf3 = ops.accumulate_gradient(self.mlp_rbf3(rbf))
-        if fork:
+        rbf3 = ops.accumulate_gradient(rbf3 if head else self.mlp_rbf3(rbf))
+        if head:
+            cbf3 = (ops.accumulate_gradient(rbf_W1_3), sph3)
+            rbf_h = ops.accumulate_gradient(rbf_h)
+            if not fork and _RBF_OUT_ACC:
+                rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
+        elif fork:
             main.wait_event(ev_b)
             for t in (rbf_W1_3, rbf_h):    # produced on the side stream, consumed (and summed: `stream=`) on the main one
                 t.record_stream(main)
@@ -413,6 +437,11 @@ class GemNet(torch.nn.Module):
         if not self.extensive:
             E_mol = E_mol / plan.atoms_per_mol.clamp(min=1)[:, None]
         return E_mol, F_ca, V_ca
+
+    def _radial_head(self, R, plan, proj):
+        b3 = self.cbf_basis3
+        return ops.radial_head(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a, b3.z_ln, b3.n_ln,
+                               tuple(d.weight for d in proj) + (self.mlp_cbf3.weight,), b3.cutoff, b3.p)
 
     def _trip_basis3(self, R, plan, V):
         if V is not None:

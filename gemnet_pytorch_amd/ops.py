@@ -1014,6 +1014,57 @@ def edge_basis(R, freq, ri_c, ri_a, z, nrm, cutoff, p, want_V=False, want_rbf=Tr
     return D, (V if want_V else None), (rbf if want_rbf else None), rad
 
 
+# Fused radial head (csrc/radial_head.hip): distances, both radial bases and the four frozen projections of their values in
+# one launch, and one adjoint launch.  GEMNET_RADIAL_HEAD=0 restores edge_basis + four GEMMs (A/B runs, tests).
+USE_RADIAL_HEAD = os.environ.get("GEMNET_RADIAL_HEAD", "1") == "1"
+
+
+def radial_head_supported(weights, z, freq):
+    """May `radial_head` replace edge_basis and the projections `weights` = (W_rbf3, W_rbf_h, W_rbf_out, W_cbf3)?  On the
+    device, with frozen weights (the concatenated form is cached; no parameter gradients exist) and the widths the kernel is
+    built for."""
+    NR, S, NI = K.RADIAL_HEAD_SHAPE
+    return (USE_RADIAL_HEAD and _FUSED and constant_weights() and z.is_cuda and tuple(z.shape) == (S, NR)
+            and freq is not None and tuple(freq.shape) == (NR,)
+            and all(tuple(W.shape) == (NI, NR) for W in weights[:3]) and tuple(weights[3].shape) == (S, NR, NI)
+            and all(W.is_cuda and W.dtype == torch.float32 for W in weights))
+
+
+def _radial_head_wcat(weights):
+    key = ("rhead",) + tuple((W.data_ptr(), tuple(W.stride())) for W in weights)
+    return _cached(key, tuple(W._version for W in weights), lambda: K.radial_head_weights(*[W.detach() for W in weights]))
+
+
+class _RadialHead(torch.autograd.Function):
+    """(R) -> rbf, rbf3, rbf_h, rbf_out, rbf_W1 in one launch; the adjoint recomputes the geometry and folds the transposed
+    projections and the sum of the rbf gradients into the derivative kernel (first-order only, frozen weights)."""
+
+    @staticmethod
+    def forward(ctx, R, freq, ri_c, ri_a, z, nrm, wcat, cutoff, p):
+        outs = K.radial_head_fwd(R, ri_c.idx32, ri_a.idx32, freq, z, nrm, wcat, cutoff, p)
+        ctx.save_for_backward(R, freq, z, nrm, wcat)
+        ctx.cfg = (ri_c, ri_a, cutoff, p)
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rbf, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1):
+        R, freq, z, nrm, wcat = ctx.saved_tensors
+        ri_c, ri_a, cutoff, p = ctx.cfg
+        gR = None
+        if ctx.needs_input_grad[0]:
+            W = K.radial_head_bwd(g_rbf, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1, R, ri_c.idx32, ri_a.idx32, freq, z, nrm, wcat,
+                                  cutoff, p)
+            gR = K.segsum_multi([(W, *ri_a.csr, 1.0), (W, *ri_c.csr, -1.0)], ri_a.n_rows)
+        return gR, None, None, None, None, None, None, None, None
+
+
+def radial_head(R, freq, ri_c, ri_a, z, nrm, weights, cutoff, p):
+    """-> rbf (E,NR), rbf3, rbf_h, rbf_out (E,16), rbf_W1 (E,S,16); `weights` as in `radial_head_supported`."""
+    return _RadialHead.apply(R, freq.detach(), ri_c, ri_a, z, nrm, _radial_head_wcat(weights), float(cutoff), int(p))
+
+
 class _TripBasis(torch.autograd.Function):
     """(R) -> Y_l0 of every triplet angle in one launch (first-order adjoint)."""
 

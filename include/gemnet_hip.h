@@ -527,6 +527,25 @@ int gn_edge_basis_bwd_f32(const float* g_D, const float* g_rbf, const float* g_r
                           const int32_t* id_c, const int32_t* id_a, const float* freq, const float* z,
                           const double* nrm, float* W, int64_t E, int NR, int S, float cutoff, int p,
                           void* stream);
+/* ---- radial head of the first-order forward (csrc/radial_head.hip) ---------------------------------------------------
+ * gn_edge_basis_fwd_f32 followed by the four frozen projections of its values (gemnet.py:158-204), in one launch: the
+ * NR + S NR basis values of an edge stay on chip; rad, D and V are not written.  NR = 6, S = 7, NI = 16 only (else
+ * hipErrorInvalidValue).  wcat (3 + S, NR, NI): rows 0..2 = W_rbf3^T, W_rbf_h^T, W_rbf_out^T ((NI, NR) Dense weights
+ * transposed), row 3 + s = W_cbf3[s] (the (S, NR, NI) weight of the circular-basis down projection, efficient.py:41-57).
+ *   rbf (E,NR): bit-identical to gn_edge_basis_fwd_f32;   rbf3 / rbf_h / rbf_out (E,NI) = rbf W^T;
+ *   rbf_W1[e,s,i] = sum_r rad[e,s,r] W_cbf3[s,r,i]  (E,S,NI); every product is one fp32 FMA chain over r = 0..NR-1.
+ * A row depends on its own edge only. */
+int gn_radial_head_fwd_f32(const float* R, const int32_t* id_c, const int32_t* id_a, const float* freq, const float* z,
+                           const double* nrm, const float* wcat, float* rbf, float* rbf3, float* rbf_h, float* rbf_out,
+                           float* rbf_W1, int64_t E, int NR, int S, int NI, float cutoff, int p, void* stream);
+/* adjoint: W[e,:] = (sum_r c_r d rbf_r/dd + sum_{s,r} c_sr d rad_sr/dd) V[e,:] with
+ *   c_r = g_rbf[r] + sum_i (W_rbf3[i,r] g_rbf3[i] + W_rbf_h[i,r] g_rbf_h[i] + W_rbf_out[i,r] g_rbf_out[i]),
+ *   c_sr = sum_i W_cbf3[s,r,i] g_rbf_W1[s,i]      (any cotangent may be NULL; the (E,NI) ones 16-byte aligned);
+ * dE/dR = segsum(W, id_a) - segsum(W, id_c), as for gn_edge_basis_bwd_f32.  Deterministic (fixed-order lane sum). */
+int gn_radial_head_bwd_f32(const float* g_rbf, const float* g_rbf3, const float* g_rbf_h, const float* g_rbf_out,
+                           const float* g_rbf_W1, const float* R, const int32_t* id_c, const int32_t* id_a,
+                           const float* freq, const float* z, const double* nrm, const float* wcat, float* W, int64_t E,
+                           int NR, int S, int NI, float cutoff, int p, void* stream);
 /* gemnet.py:288-311,420-451 -> basis_layers.py:130-131: Y[t,l] = Y_l0(atan2(max(|u x v|,1e-9), u.v)),
  * u = R[tc]-R[ta], v = R[tb]-R[ta]; theta (T,) optional output */
 int gn_trip_basis_fwd_f32(const float* R, const int32_t* tc, const int32_t* ta, const int32_t* tb, float* Y,
