@@ -72,6 +72,7 @@ SIGNATURES = {
     "gn_gemm_f32_cfg": [ctypes.POINTER(GemmArgs), _i, _vp],
     "gn_chain_f32": [_vp, _vp],               # const gn_chain_args* (kernels.chain packs the block with `struct`)
     "gn_chain_split_f32": [_vp, _i, _vp],
+    "gn_chain_split_grouped_f32": [_vp, _i, _i, _i, _i, _vp],
     "gn_pack_weight_split": [_vp, _i, _i, _i, _i, _vp, _vp],
     "gn_pack_weight_split_fmt": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "gn_pack_weight_split_grouped": [_vp, _i, _i, _vp],
@@ -99,6 +100,10 @@ SIGNATURES = {
     "gn_bmm_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "gn_rbf_aggregate_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp],
     "gn_rbf_aggregate_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp],
+    "gn_rbf_aggregate_grouped_fwd_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
+    "gn_rbf_aggregate_grouped_bwd_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp],
+    "gn_energy_head_fwd_f32": [_vp, _vp, _vp, _i, _i64, _i, _vp],
+    "gn_energy_head_bwd_f32": [_vp, _vp, _vp, _i, _i64, _i, _vp],
     "gn_quad_angles_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "gn_quad_angles_bwd_ld_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i64, _vp],
     "gn_bil_reduce_project_ang_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],

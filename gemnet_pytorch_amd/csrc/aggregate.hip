@@ -152,10 +152,11 @@ __global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_fwd_kernel(cons
 // Forward, second form (round 5; same arithmetic in the same order: bit-identical): the wave index is made provably uniform,
 // so the edge ids (perm) and the 64-byte rbf rows of a wave's edges are SCALAR loads, and W goes through LDS once per workgroup
 // instead of 8 KB per wave from L2.
-__global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_fwd_kernel_v2(const float* __restrict__ m, const float* __restrict__ rbf,
-                                                                   const float* __restrict__ W, const int32_t* __restrict__ perm,
-                                                                   const int32_t* __restrict__ seg_off, float* __restrict__ out,
-                                                                   float scale) {
+// (the body is shared with the grouped launch below, whose workgroup (atom, group) runs it on the group's m, W and scale)
+__device__ __forceinline__ GN_AGG_ATTR void rbf_aggregate_fwd_v2_body(const float* __restrict__ m, const float* __restrict__ rbf,
+                                                                      const float* __restrict__ W, const int32_t* __restrict__ perm,
+                                                                      const int32_t* __restrict__ seg_off, float* __restrict__ out,
+                                                                      float scale) {
   constexpr int WP = R + 1;
   __shared__ float Wl[C * WP];
   __shared__ float2 part[4][64];
@@ -209,6 +210,37 @@ __global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_fwd_kernel_v2(c
   }
 }
 
+__global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_fwd_kernel_v2(const float* __restrict__ m, const float* __restrict__ rbf,
+                                                                   const float* __restrict__ W, const int32_t* __restrict__ perm,
+                                                                   const int32_t* __restrict__ seg_off, float* __restrict__ out,
+                                                                   float scale) {
+  rbf_aggregate_fwd_v2_body(m, rbf, W, perm, seg_off, out, scale);
+}
+
+// Grouped forms (gn_rbf_aggregate_grouped_*): the G OutputBlocks of a model share rbf and the CSR; per group its own m, W, scale.
+// The pointer tables travel by value in the argument block (no device table to keep alive for a captured graph).
+#ifndef GN_AGG_GROUP_GRID
+#define GN_AGG_GROUP_GRID 768     // workgroups of the grouped adjoint
+#endif
+#ifndef GN_AGG_GROUP_NE
+#define GN_AGG_GROUP_NE 6         // edges per wave and trip
+#endif
+struct agg_group_tab {
+  const float* m[GN_AGG_MAX_GROUPS];
+  const float* W[GN_AGG_MAX_GROUPS];
+  float* g_m[GN_AGG_MAX_GROUPS];
+};
+
+// forward: workgroup (atom, group) = the single launch of that group, writing the group's slab of the stacked output
+__global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_grouped_fwd_kernel(const agg_group_tab T, const float* __restrict__ scales,
+                                                                        const float* __restrict__ rbf,
+                                                                        const int32_t* __restrict__ perm,
+                                                                        const int32_t* __restrict__ seg_off, float* __restrict__ out,
+                                                                        int64_t n_atoms) {
+  const int g = blockIdx.y;
+  rbf_aggregate_fwd_v2_body(T.m[g], rbf, T.W[g], perm, seg_off, out + (size_t)g * n_atoms * C, scales[g]);
+}
+
 // Adjoint: a wave walks edges e = wave id, + #waves, ...  Per edge
 //   g_m[e][c]   = scale * g_out[a(e)][c] * (W rbf[e])[c]            lane l owns columns 2l, 2l+1 (as in the forward)
 //   g_rbf[e][k] = scale * sum_c g_out[a(e)][c] m[e][c] W[c][k]      a 128 x 16 mat-vec: the products t_c pass through
@@ -260,12 +292,16 @@ __global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_bwd_kernel(cons
         r0 += w0[4 * q] * b.x + w0[4 * q + 1] * b.y + w0[4 * q + 2] * b.z + w0[4 * q + 3] * b.w;
         r1 += w1[4 * q] * b.x + w1[4 * q + 1] * b.y + w1[4 * q + 2] * b.z + w1[4 * q + 3] * b.w;
       }
-      float2 o = make_float2(gx * r0, gy * r1);
-      if (accum & 1) {   // running gradient of m (ops.accumulate_gradient): the same lane reads and rewrites its element
-        const float2 p = *reinterpret_cast<const float2*>(g_m + (size_t)e * C + 2 * lane);
-        o.x += p.x; o.y += p.y;
+      {
+        // product and running-gradient add are two roundings, never one FMA: the grouped adjoint below repeats exactly this
+#pragma clang fp contract(off)
+        float2 o = make_float2(gx * r0, gy * r1);
+        if (accum & 1) {   // running gradient of m (ops.accumulate_gradient): the same lane reads and rewrites its element
+          const float2 p = *reinterpret_cast<const float2*>(g_m + (size_t)e * C + 2 * lane);
+          o.x += p.x; o.y += p.y;
+        }
+        *reinterpret_cast<float2*>(g_m + (size_t)e * C + 2 * lane) = o;
       }
-      *reinterpret_cast<float2*>(g_m + (size_t)e * C + 2 * lane) = o;
     }
     if (g_rbf) {
       const float2 me = *reinterpret_cast<const float2*>(m + (size_t)e * C + 2 * lane);
@@ -343,12 +379,16 @@ __global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_bwd_kernel_v2(c
         r0 += w0[4 * q] * bx + w0[4 * q + 1] * by + w0[4 * q + 2] * bz + w0[4 * q + 3] * bw;
         r1 += w1[4 * q] * bx + w1[4 * q + 1] * by + w1[4 * q + 2] * bz + w1[4 * q + 3] * bw;
       }
-      float2 o = make_float2(gx * r0, gy * r1);
-      if (accum & 1) {
-        const float2 p = *reinterpret_cast<const float2*>(g_m + (size_t)e * C + 2 * lane);
-        o.x += p.x; o.y += p.y;
+      {
+        // product and running-gradient add are two roundings, never one FMA: the grouped adjoint below repeats exactly this
+#pragma clang fp contract(off)
+        float2 o = make_float2(gx * r0, gy * r1);
+        if (accum & 1) {
+          const float2 p = *reinterpret_cast<const float2*>(g_m + (size_t)e * C + 2 * lane);
+          o.x += p.x; o.y += p.y;
+        }
+        *reinterpret_cast<float2*>(g_m + (size_t)e * C + 2 * lane) = o;
       }
-      *reinterpret_cast<float2*>(g_m + (size_t)e * C + 2 * lane) = o;
     }
     if (g_rbf) {
       *reinterpret_cast<float2*>(&tsm[wave][2 * lane]) = make_float2(gx * me.x, gy * me.y);
@@ -367,6 +407,125 @@ __global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_bwd_kernel_v2(c
       __builtin_amdgcn_wave_barrier();
     }
     a = an; g = gn; me = mn;
+  }
+}
+
+// Grouped adjoint.  A wave takes NE edges (e, e + #waves, ...) through ALL groups: the edge ids, id_a[e] and the rbf rows are
+// fetched once (scalar loads), the G contributions to g_rbf[e] are summed in a register per edge in the order g = 0 .. G-1
+// and stored once (the single launches pass that sum through memory G times, or leave G - 1 adds to the caller).  The G
+// weight matrices are staged in LDS once per workgroup (G x 8.5 KB); a wave fetches group g's W rows into registers once per
+// group and NE edges — per (edge, group) from LDS instead, the launch was LDS-bound and, at four workgroups per CU, did not fit
+// one resident round (79 us at E = 18 122, G = 5 against 5 x 8.5 us for the single launches).  All global operands of a
+// group's NE edges are requested before the first is used.  Per (edge, group) the arithmetic is the single launch's,
+// expression for expression: g_m[g] is bit-identical.
+template <int NE>
+__global__ __launch_bounds__(256) GN_AGG_ATTR void rbf_aggregate_grouped_bwd_kernel(const agg_group_tab T, const float* __restrict__ scales,
+                                                                        const int G, const float* __restrict__ g_out,
+                                                                        const float* __restrict__ rbf,
+                                                                        const int32_t* __restrict__ id_a, float* g_rbf,
+                                                                        const int64_t E, const int64_t n_atoms, const int accum_m,
+                                                                        const int accum_rbf) {
+  constexpr int WP = R + 1;
+  extern __shared__ __attribute__((aligned(16))) float agg_smem[];
+  float* const tsm_all = agg_smem;                          // [4][C], 16-byte aligned
+  float* const Wl_all = agg_smem + 4 * C;                   // [G][C * WP]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kq = lane & 15, part = lane >> 4;
+  for (int g = 0; g < G; ++g) {
+    const float* __restrict__ W = T.W[g];
+    for (int i = threadIdx.x; i < C * R / 4; i += 256) {
+      const float4 v = *reinterpret_cast<const float4*>(W + 4 * i);
+      float* d = Wl_all + g * (C * WP) + (i >> 2) * WP + 4 * (i & 3);
+      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+  }
+  __syncthreads();
+  float* const tsm = tsm_all + wave * C;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t e0 = (int64_t)blockIdx.x * 4 + wave; e0 < E; e0 += stride * NE) {
+    int64_t ej[NE];
+    bool ok[NE];
+    int aj[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+      ok[j] = e0 + j * stride < E;
+      ej[j] = ok[j] ? e0 + j * stride : e0;                   // (clamped: loads are unconditional, stores are not)
+      aj[j] = id_a[ej[j]];
+    }
+    float s_sum[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) s_sum[j] = 0.f;
+    for (int g = 0; g < G; ++g) {
+      const float* __restrict__ mg = T.m[g];
+      float* const g_m = T.g_m[g];
+      const bool acc = ((accum_m >> g) & 1) != 0;
+      const float scale = scales[g];
+      const float* const Wl = Wl_all + g * (C * WP);
+      float2 gc[NE], me[NE], pv[NE];
+#pragma unroll
+      for (int j = 0; j < NE; ++j) {
+        gc[j] = *reinterpret_cast<const float2*>(g_out + ((size_t)g * n_atoms + aj[j]) * C + 2 * lane);
+        me[j] = g_rbf ? *reinterpret_cast<const float2*>(mg + (size_t)ej[j] * C + 2 * lane) : make_float2(0.f, 0.f);
+        pv[j] = (g_m && acc) ? *reinterpret_cast<const float2*>(g_m + (size_t)ej[j] * C + 2 * lane) : make_float2(0.f, 0.f);
+      }
+      if (g_m) {
+        float w0[R], w1[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          w0[k] = Wl[(2 * lane) * WP + k];
+          w1[k] = Wl[(2 * lane + 1) * WP + k];
+        }
+#pragma unroll
+        for (int j = 0; j < NE; ++j) {
+          const float* __restrict__ b = rbf + (size_t)ej[j] * R;      // uniform address: scalar loads
+          const float gx = gc[j].x * scale, gy = gc[j].y * scale;
+          float r0 = 0.f, r1 = 0.f;
+#pragma unroll
+          for (int q = 0; q < R / 4; ++q) {
+            const float bx = b[4 * q], by = b[4 * q + 1], bz = b[4 * q + 2], bw = b[4 * q + 3];
+            r0 += w0[4 * q] * bx + w0[4 * q + 1] * by + w0[4 * q + 2] * bz + w0[4 * q + 3] * bw;
+            r1 += w1[4 * q] * bx + w1[4 * q + 1] * by + w1[4 * q + 2] * bz + w1[4 * q + 3] * bw;
+          }
+          {
+            // product and running-gradient add are two roundings, as in the single launches (contraction is off for these
+            // statements there too): with it on, the compiler fuses them into one FMA here
+#pragma clang fp contract(off)
+            float2 o = make_float2(gx * r0, gy * r1);
+            if (acc) { o.x += pv[j].x; o.y += pv[j].y; }
+            if (ok[j]) *reinterpret_cast<float2*>(g_m + (size_t)ej[j] * C + 2 * lane) = o;
+          }
+        }
+      }
+      if (g_rbf) {
+        float wt[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) wt[j] = Wl[(32 * part + j) * WP + kq];
+#pragma unroll
+        for (int j = 0; j < NE; ++j) {
+          const float gx = gc[j].x * scale, gy = gc[j].y * scale;
+          *reinterpret_cast<float2*>(&tsm[2 * lane]) = make_float2(gx * me[j].x, gy * me[j].y);
+          __builtin_amdgcn_s_waitcnt(0xc07f);
+          __builtin_amdgcn_wave_barrier();
+          float s = 0.f;
+#pragma unroll
+          for (int j4 = 0; j4 < 8; ++j4) {
+            const float4 t = *reinterpret_cast<const float4*>(&tsm[32 * part + 4 * j4]);
+            s += t.x * wt[4 * j4] + t.y * wt[4 * j4 + 1] + t.z * wt[4 * j4 + 2] + t.w * wt[4 * j4 + 3];
+          }
+          s += __shfl_xor(s, 16, 64);
+          s += __shfl_xor(s, 32, 64);
+          s_sum[j] = g == 0 ? s : s_sum[j] + s;
+          __builtin_amdgcn_s_waitcnt(0xc07f);
+          __builtin_amdgcn_wave_barrier();   // all lanes have read tsm before the next edge overwrites it
+        }
+      }
+    }
+    if (g_rbf && lane < R) {
+#pragma unroll
+      for (int j = 0; j < NE; ++j)
+        if (ok[j]) g_rbf[(size_t)ej[j] * R + lane] = accum_rbf ? g_rbf[(size_t)ej[j] * R + lane] + s_sum[j] : s_sum[j];
+    }
   }
 }
 
@@ -406,6 +565,55 @@ extern "C" int gn_rbf_aggregate_bwd_f32(const float* g_out, const float* m, cons
   hipLaunchKernelGGL(rbf_aggregate_bwd_kernel_v2, dim3((unsigned)(blocks < GN_AGG_GRID ? blocks : GN_AGG_GRID)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), g_out, m, rbf, W, id_a, g_m, g_rbf, E, scale, accum);
 #endif
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_rbf_aggregate_grouped_fwd_f32(const float* const* m_list, const float* const* W_list, const float* scales, int G,
+                                                const float* rbf, const int32_t* perm, const int32_t* seg_off, float* out,
+                                                int64_t n_atoms, int C_, int R_, void* stream) {
+  if (C_ != C || R_ != R || G < 0 || G > GN_AGG_MAX_GROUPS) return (int)hipErrorInvalidValue;
+  if (n_atoms <= 0 || G == 0) return 0;
+  agg_group_tab T = {};
+  for (int g = 0; g < G; ++g) {
+    if (!m_list[g] || !W_list[g]) return (int)hipErrorInvalidValue;
+    T.m[g] = m_list[g];
+    T.W[g] = W_list[g];
+  }
+  hipLaunchKernelGGL(rbf_aggregate_grouped_fwd_kernel, dim3((unsigned)n_atoms, (unsigned)G), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), T, scales, rbf, perm, seg_off, out, n_atoms);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_rbf_aggregate_grouped_bwd_f32(const float* g_out, const float* const* m_list, const float* const* W_list,
+                                                const float* scales, int G, const float* rbf, const int32_t* id_a,
+                                                float* const* g_m_list, float* g_rbf, int64_t E, int64_t n_atoms, int C_, int R_,
+                                                int accum_m, int accum_rbf, void* stream) {
+  if (C_ != C || R_ != R || G < 0 || G > GN_AGG_MAX_GROUPS) return (int)hipErrorInvalidValue;
+  if (E <= 0 || G == 0) return 0;
+  agg_group_tab T = {};
+  for (int g = 0; g < G; ++g) {
+    if (!m_list[g] || !W_list[g]) return (int)hipErrorInvalidValue;
+    T.m[g] = m_list[g];
+    T.W[g] = W_list[g];
+    T.g_m[g] = g_m_list ? g_m_list[g] : nullptr;
+  }
+  constexpr size_t smem_max = (size_t)(4 * C + GN_AGG_MAX_GROUPS * C * (R + 1)) * sizeof(float);   // 70 KB at 8 groups
+  static std::atomic<bool> configured{false};   // set-once flag of an idempotent attribute
+  if (!configured.load(std::memory_order_acquire)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbf_aggregate_grouped_bwd_kernel<GN_AGG_GROUP_NE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max);
+    if (e != hipSuccess) return (int)e;
+    configured.store(true, std::memory_order_release);
+  }
+  const size_t smem = (size_t)(4 * C + G * C * (R + 1)) * sizeof(float);
+  // one resident round: the staged weights (45.5 KB at five groups) leave room for three workgroups per CU on 256 CUs, and six
+  // edges per wave and trip cover E = 18 122 in one trip
+  const int64_t blocks = gn_cdiv(E, 4);
+  hipLaunchKernelGGL(rbf_aggregate_grouped_bwd_kernel<GN_AGG_GROUP_NE>,
+                     dim3((unsigned)(blocks < GN_AGG_GROUP_GRID ? blocks : GN_AGG_GROUP_GRID)), dim3(256), smem,
+                     static_cast<hipStream_t>(stream), T, scales, G, g_out, rbf, id_a, g_rbf, E, n_atoms, accum_m, accum_rbf);
   GN_LAUNCH_CHECK();
   return 0;
 }

@@ -60,8 +60,12 @@ using namespace gn_split;
 #else
 #define GN2_BOUNDS __launch_bounds__(NT)
 #endif
-template <int RT, int NPL, bool ADJ, bool HF>
-__global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int meta) {
+// GRP (gn_chain_split_grouped_f32): one launch runs the program for several groups — workgroup -> (group, row tile of the
+// group; `tpg` tiles per group); group g reads and writes rows g * pitch + [0, M) of every global operand and uses the g-th
+// packed weight of every GEMM op (the groups' packed weights are stacked contiguously).  A tile never spans two groups and
+// rows past M are masked as in the single launch, so a partial tile cannot reach the next group's rows.
+template <int RT, int NPL, bool ADJ, bool HF, bool GRP = false>
+__global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int meta, const int tpg, const int pitch) {
   static_assert(!HF || NPL == 2, "format H has two planes");
   constexpr int BM = 16 * RT;
   constexpr int PLANE = BM * ROWB;          // bytes of one plane
@@ -73,7 +77,9 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
   const int lane = tid & 63;
   const int l15 = lane & 15;
   const int lg = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * BM;
+  const int grp = GRP ? (int)(blockIdx.x / (unsigned)tpg) : 0;
+  const int64_t row0 = (int64_t)(GRP ? (int)blockIdx.x - grp * tpg : (int)blockIdx.x) * BM;   // first row of the tile in its group
+  const int64_t rbase = GRP ? (int64_t)grp * pitch : 0;                                       // first row of the group
   const int M = P.M;
   // weight pointer / shape of the GEMM ops in program order, staged in LDS: the next op's fragments are requested at the
   // top of every GEMM op and must not wait for a scalar load of its descriptor from the kernarg segment
@@ -128,6 +134,7 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
     // packed layout: [col tile][k-chunk][plane (3)][lane][8 bf16]
     const int N = nk >> 16, kc = ((nk & 0xffff) + 31) >> 5;
     const uint4* __restrict__ base = reinterpret_cast<const uint4*>(Wp) + ((size_t)wave * kc * SP) * 64 + lane;
+    if (GRP) base += (size_t)grp * ((size_t)((N + 15) >> 4) * kc * SP * 64);   // this group's packed weight
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -228,9 +235,9 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         zz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (in[i]) {
-          const int64_t sr = rows ? (int64_t)rows[gr] : gr;
+          const int64_t sr = rows ? (int64_t)rows[gr] : gr + rbase;
           v[i] = *reinterpret_cast<const float4*>(src + sr * ld + c);
-          if (ADJ && y2_slot >= 0 && Z2) zz[i] = *reinterpret_cast<const float4*>(Z2 + gr * width + c);
+          if (ADJ && y2_slot >= 0 && Z2) zz[i] = *reinterpret_cast<const float4*>(Z2 + (gr + rbase) * width + c);
         }
       }
       float sig[RT];
@@ -263,7 +270,7 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
               else { u.x *= gn_ssilu(z.x); u.y *= gn_ssilu(z.y); u.z *= gn_ssilu(z.z); u.w *= gn_ssilu(z.w); }
             }
             if (lsrc && in[i]) {
-              const int64_t gr = row0 + r;
+              const int64_t gr = row0 + r + rbase;
               const float4 p = *reinterpret_cast<const float4*>(srcP + gr * width + c);
               const float4 q = srcQ ? *reinterpret_cast<const float4*>(srcQ + gr * width + c) : make_float4(1.f, 1.f, 1.f, 1.f);
               const float4 sv = src_term(zz[i], p, q, src_mode, src_alpha);
@@ -309,21 +316,22 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
           const float a_true = HF ? alpha * inv_pow2(sc) : alpha;
           v.x *= a_true; v.y *= a_true; v.z *= a_true; v.w *= a_true;
           float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+          const int64_t gg = gr + rbase;      // row in the (stacked) global operands
           if (src && gr < M) {
-            z = *reinterpret_cast<const float4*>(src + gr * ld + c);
+            z = *reinterpret_cast<const float4*>(src + gg * ld + c);
             if (mode == 0) { v.x *= gn_dssilu(z.x); v.y *= gn_dssilu(z.y); v.z *= gn_dssilu(z.z); v.w *= gn_dssilu(z.w); }
             else if (mode == 1) { v.x *= z.x; v.y *= z.y; v.z *= z.z; v.w *= z.w; }
             else { v.x *= gn_ssilu(z.x); v.y *= gn_ssilu(z.y); v.z *= gn_ssilu(z.z); v.w *= gn_ssilu(z.w); }
           }
           if (ADJ && op.src_stage == 1 && op.srcP && gr < M) {
-            const float4 p = *reinterpret_cast<const float4*>(op.srcP + gr * ld + c);
-            const float4 q = op.srcQ ? *reinterpret_cast<const float4*>(op.srcQ + gr * ld + c) : make_float4(1.f, 1.f, 1.f, 1.f);
+            const float4 p = *reinterpret_cast<const float4*>(op.srcP + gg * ld + c);
+            const float4 q = op.srcQ ? *reinterpret_cast<const float4*>(op.srcQ + gg * ld + c) : make_float4(1.f, 1.f, 1.f, 1.f);
             const float4 sv = src_term(z, p, q, op.src_mode, op.src_alpha);
             v.x += sv.x; v.y += sv.y; v.z += sv.z; v.w += sv.w;
           }
           slot_write(slot, r, c, HF ? mul4(v, sc) : v);
           if (HF && c == 0 && slot != a_slot) rs[slot][r] = sc;
-          if (out && gr < M) *reinterpret_cast<float4*>(out + gr * ld + c) = v;
+          if (out && gr < M) *reinterpret_cast<float4*>(out + gg * ld + c) = v;
         }
         lds_barrier();
         if (HF) {
@@ -339,7 +347,7 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
         const int64_t gr = row0 + r;
         if (gr < M) {
           const float4 v = slot_read(slot, r, c);
-          *reinterpret_cast<float4*>(out + gr * ld + c) = HF ? mul4(v, inv_pow2(rs[slot][r])) : v;
+          *reinterpret_cast<float4*>(out + (gr + rbase) * ld + c) = HF ? mul4(v, inv_pow2(rs[slot][r])) : v;
         }
       }
       lds_barrier();
@@ -383,7 +391,7 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
           const int64_t grow = row0 + 16 * t + l15;
-          if (grow < M) g2lds16(mul_g + (uint32_t)grow * (uint32_t)N + (uint32_t)n0, stage_lds + t * 1024);
+          if (grow < M) g2lds16(mul_g + (uint32_t)(grow + rbase) * (uint32_t)N + (uint32_t)n0, stage_lds + t * 1024);
         }
       }
       // hh | the cross terms hm + mh + hl + lh + mm (summed among themselves first).  Format H: hl and lh in registers of their
@@ -512,7 +520,7 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
         for (int t = 0; t < RT; ++t) {
           const int64_t grow = row0 + 16 * t + l15;
           ok[t] = grow < M;
-          off[t] = (uint32_t)grow * (uint32_t)N + (uint32_t)n0;
+          off[t] = (uint32_t)(grow + rbase) * (uint32_t)N + (uint32_t)n0;
         }
 #define GN2_EACH(body) _Pragma("unroll") for (int t = 0; t < RT; ++t) { body }
 #define GN2_ADD(q) v[t].x += q.x; v[t].y += q.y; v[t].z += q.z; v[t].w += q.w;
@@ -641,8 +649,8 @@ __global__ GN2_BOUNDS void chain_split_kernel(const gn_chain_args P, const int m
   }
 }
 
-template <int RT, int NPL, bool ADJ, bool HF>
-int launch_chain_split(const gn_chain_args* args, hipStream_t st) {
+template <int RT, int NPL, bool ADJ, bool HF, bool GRP = false>
+int launch_chain_split(const gn_chain_args* args, hipStream_t st, int groups = 1, int pitch = 0) {
   int first = 0xff, linear = 1;
   for (int i = 0; i < args->n_ops; ++i)
     if (args->ops[i].kind == GN_OP_GEMM) {
@@ -655,13 +663,15 @@ int launch_chain_split(const gn_chain_args* args, hipStream_t st) {
   static std::atomic<bool> configured{false};   // set-once flag of an idempotent attribute (two racing threads both set it)
   if (!configured.load(std::memory_order_acquire)) {
     if (smem > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_split_kernel<RT, NPL, ADJ, HF>),
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_split_kernel<RT, NPL, ADJ, HF, GRP>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
       if (e != hipSuccess) return (int)e;
     }
     configured.store(true, std::memory_order_release);
   }
-  hipLaunchKernelGGL((chain_split_kernel<RT, NPL, ADJ, HF>), dim3(gn_cdiv(args->M, BM)), dim3(NT), smem, st, *args, meta);
+  const int tpg = gn_cdiv(args->M, BM);      // row tiles per group (a plain launch is one group)
+  hipLaunchKernelGGL((chain_split_kernel<RT, NPL, ADJ, HF, GRP>), dim3((unsigned)(GRP ? groups * tpg : tpg)), dim3(NT), smem, st,
+                     *args, meta, tpg, pitch);
   GN_LAUNCH_CHECK();
   return 0;
 }
@@ -791,19 +801,10 @@ extern "C" int gn_pack_weight_split(const float* W, int N, int K, int ldw, int t
   return gn_pack_weight_split_fmt(W, N, K, ldw, trans, GN_SPLIT_BF16X3, out, stream);
 }
 
-extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream) {
-  if (args->M <= 0 || args->n_ops <= 0) return 0;
+// what every launch form checks of a program: 0, or hipErrorInvalidValue
+static int chain_split_check(const gn_chain_args* args) {
   if (args->n_ops > GN_CHAIN_MAX_OPS) return (int)hipErrorInvalidValue;
   if (args->M > (1 << 24)) return (int)hipErrorInvalidValue;
-  // wide layout: tile height (GN_CHAIN_WIDE_ROWS) and start-up stagger (GN_CHAIN_WIDE_STAGGER) ride in the upper bits of `nprod`
-  // — per call, no library state (ABI 13)
-  const bool row = nprod == (GN_CHAIN_F16X2 | GN_CHAIN_ROW);
-  if (row) nprod = GN_CHAIN_F16X2;
-  const bool wide = (nprod & 0xfff) == (GN_CHAIN_F16X2 | GN_CHAIN_WIDE);
-  const int wide_rows = ((nprod >> 12) & 0xf) * 8, wide_stagger = (nprod >> 16) & 0xffff;
-  if (!wide && (nprod & ~0xfff)) return (int)hipErrorInvalidValue;
-  if (wide && wide_rows > 48) return (int)hipErrorInvalidValue;
-  if (nprod != 1 && nprod != 3 && nprod != 6 && nprod != GN_CHAIN_F16X2 && !wide) return (int)hipErrorInvalidValue;
   // the prologue requests the first GEMM's weights and publishes the op table without a barrier of its own: it relies on the
   // barrier every LOAD ends with, so a program must start with one (every generated program does)
   if (args->ops[0].kind != GN_OP_LOAD) return (int)hipErrorInvalidValue;
@@ -830,7 +831,12 @@ extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* st
       if (o.src_stage && o.src_mode == 1 && !(o.kind == GN_OP_SCALE ? o.src : o.Z2)) return (int)hipErrorInvalidValue;
     }
   }
-  bool adj = false;   // does the program touch the parking slot or a second output?
+  return 0;
+}
+
+// does the program touch the parking slot or a second output?
+static bool chain_split_is_adj(const gn_chain_args* args) {
+  bool adj = false;
   for (int i = 0; i < args->n_ops; ++i) {
     const gn_chain_op& o = args->ops[i];
     if (o.kind == GN_OP_GEMM)
@@ -839,6 +845,24 @@ extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* st
     else
       adj = adj || o.slot == 2 || (o.kind == GN_OP_LOAD && o.y2_slot >= 0) || o.src_stage != 0;
   }
+  return adj;
+}
+
+extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream) {
+  if (args->M <= 0 || args->n_ops <= 0) return 0;
+  if (args->n_ops > GN_CHAIN_MAX_OPS) return (int)hipErrorInvalidValue;
+  if (args->M > (1 << 24)) return (int)hipErrorInvalidValue;
+  // wide layout: tile height (GN_CHAIN_WIDE_ROWS) and start-up stagger (GN_CHAIN_WIDE_STAGGER) ride in the upper bits of `nprod`
+  // — per call, no library state (ABI 13)
+  const bool row = nprod == (GN_CHAIN_F16X2 | GN_CHAIN_ROW);
+  if (row) nprod = GN_CHAIN_F16X2;
+  const bool wide = (nprod & 0xfff) == (GN_CHAIN_F16X2 | GN_CHAIN_WIDE);
+  const int wide_rows = ((nprod >> 12) & 0xf) * 8, wide_stagger = (nprod >> 16) & 0xffff;
+  if (!wide && (nprod & ~0xfff)) return (int)hipErrorInvalidValue;
+  if (wide && wide_rows > 48) return (int)hipErrorInvalidValue;
+  if (nprod != 1 && nprod != 3 && nprod != 6 && nprod != GN_CHAIN_F16X2 && !wide) return (int)hipErrorInvalidValue;
+  if (const int e = chain_split_check(args)) return e;
+  const bool adj = chain_split_is_adj(args);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (row) return gn_chain_row_dispatch(args, adj, st);     // chain4.hip (its weights: GN_SPLIT_F16X2_ROW)
   if (wide) {      // chain3.hip: 4 waves x 32 columns, two workgroups per CU — it has no parking slot
@@ -854,4 +878,33 @@ extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* st
   if (nprod == 6) return dispatch_adj<3>(args, adj, st);
   if (nprod == 3) return dispatch_adj<2>(args, adj, st);
   return dispatch_adj<1>(args, adj, st);
+}
+
+template <int NPL, bool HF>
+static int dispatch_grouped(const gn_chain_args* args, bool adj, int tile_rows, int groups, int pitch, hipStream_t st) {
+  if (tile_rows == 16)
+    return adj ? launch_chain_split<1, NPL, true, HF, true>(args, st, groups, pitch)
+               : launch_chain_split<1, NPL, false, HF, true>(args, st, groups, pitch);
+  return adj ? launch_chain_split<2, NPL, true, HF, true>(args, st, groups, pitch)
+             : launch_chain_split<2, NPL, false, HF, true>(args, st, groups, pitch);
+}
+
+extern "C" int gn_chain_split_grouped_f32(const gn_chain_args* args, int nprod, int groups, int group_pitch, int tile_rows,
+                                          void* stream) {
+  if (args->M <= 0 || args->n_ops <= 0 || groups <= 0) return 0;
+  if (groups > GN_CHAIN_MAX_GROUPS) return (int)hipErrorInvalidValue;
+  if (nprod != GN_CHAIN_F16X2 && nprod != 6) return (int)hipErrorInvalidValue;
+  if (tile_rows == 0) tile_rows = GN_CHAIN_GROUP_TILE_ROWS;
+  if (tile_rows != 16 && tile_rows != 32) return (int)hipErrorInvalidValue;
+  // element offsets of the stacked operands are 32-bit in the epilogues, like M * 128 of the single launch
+  if (group_pitch < args->M || (int64_t)groups * group_pitch > (1 << 24)) return (int)hipErrorInvalidValue;
+  if (const int e = chain_split_check(args)) return e;
+  for (int i = 0; i < args->n_ops; ++i) {     // a row gather would address rows outside the group: not a grouped program
+    const gn_chain_op& o = args->ops[i];
+    if (o.rows || o.gidx1 || o.gidx2 || o.gadd1 || o.gadd2 || o.res_rows) return (int)hipErrorInvalidValue;
+  }
+  const bool adj = chain_split_is_adj(args);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (nprod == GN_CHAIN_F16X2) return dispatch_grouped<2, true>(args, adj, tile_rows, groups, group_pitch, st);
+  return dispatch_grouped<3, false>(args, adj, tile_rows, groups, group_pitch, st);
 }

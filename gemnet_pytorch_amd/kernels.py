@@ -13,7 +13,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, addr, check, ptr, require_device, stream
+from ._lib import GN_CHAIN_MAX_OPS, GemmArgs, addr, check, ptr, require_device, stream
 
 
 def _f32c(t):
@@ -391,6 +391,70 @@ def rbf_aggregate_bwd(g_out, m, rbf, W, id_a32, scale, want_m=True, want_rbf=Tru
                                                m.shape[0], m.shape[1], rbf.shape[1], float(scale), accum, stream()),
           "gn_rbf_aggregate_bwd_f32")
     return g_m, g_rbf
+
+
+def rbf_aggregate_grouped_fwd(m_list, rbf, W_list, scales, perm, seg_off, n_atoms):
+    """out (G, n_atoms, C): out[g] = scales[g] * sum_{e -> a} m_list[g][e] * (W_list[g] rbf[e]) for the G groups that share
+    rbf and the CSR, one launch (gn_rbf_aggregate_grouped_fwd_f32).  `scales`: device tensor (G)."""
+    require_device(rbf, scales, *m_list, *W_list)
+    m_list, W_list = [_f32c(t) for t in m_list], [_f32c(t) for t in W_list]
+    rbf, scales = _f32c(rbf), _f32c(scales)
+    G = len(m_list)
+    assert len(W_list) == G and scales.numel() == G
+    out = torch.empty((G, n_atoms, m_list[0].shape[1]), device=rbf.device, dtype=torch.float32)
+    arr = ctypes.c_void_p * G
+    check(_lib.load().gn_rbf_aggregate_grouped_fwd_f32(arr(*[addr(t) for t in m_list]), arr(*[addr(t) for t in W_list]),
+                                                       ptr(scales), G, ptr(rbf), ptr(perm), ptr(seg_off), ptr(out), n_atoms,
+                                                       m_list[0].shape[1], rbf.shape[1], stream()),
+          "gn_rbf_aggregate_grouped_fwd_f32")
+    return out
+
+
+def rbf_aggregate_grouped_bwd(g_out, m_list, rbf, W_list, scales, id_a32, acc_m=None, want_rbf=True, acc_rbf=None):
+    """Adjoint of `rbf_aggregate_grouped_fwd` (gn_rbf_aggregate_grouped_bwd_f32) -> ([g_m[g] (E,C)], g_rbf (E,R) or None).
+    g_out: the stacked (G, n_atoms, C) gradient.  acc_m[g] / acc_rbf: running gradients the contribution is ADDED to in the
+    same pass (and which are returned); g_rbf is the sum over the groups, in group order."""
+    require_device(g_out, rbf, scales, *m_list, *W_list)
+    m_list, W_list = [_f32c(t) for t in m_list], [_f32c(t) for t in W_list]
+    g_out, rbf, scales = _f32c(g_out), _f32c(rbf), _f32c(scales)
+    G = len(m_list)
+    acc_m = list(acc_m) if acc_m is not None else [None] * G
+    g_m, accum = [], 0
+    for g, (t, like) in enumerate(zip(acc_m, m_list)):
+        assert t is None or (t.shape == like.shape and t.dtype == torch.float32 and t.is_contiguous())
+        accum |= (1 << g) if t is not None else 0
+        g_m.append(t if t is not None else torch.empty_like(like))
+    assert acc_rbf is None or (acc_rbf.shape == rbf.shape and acc_rbf.dtype == torch.float32 and acc_rbf.is_contiguous())
+    g_rbf = acc_rbf if acc_rbf is not None else (torch.empty_like(rbf) if want_rbf else None)
+    arr = ctypes.c_void_p * G
+    check(_lib.load().gn_rbf_aggregate_grouped_bwd_f32(ptr(g_out), arr(*[addr(t) for t in m_list]),
+                                                       arr(*[addr(t) for t in W_list]), ptr(scales), G, ptr(rbf), ptr(id_a32),
+                                                       arr(*[addr(t) for t in g_m]), ptr(g_rbf), m_list[0].shape[0],
+                                                       g_out.shape[1], m_list[0].shape[1], rbf.shape[1], accum,
+                                                       int(acc_rbf is not None), stream()),
+          "gn_rbf_aggregate_grouped_bwd_f32")
+    return g_m, g_rbf
+
+
+def energy_head_fwd(x, w):
+    """E (A,1) = sum_g x[g] @ w[g], g in order: x (G,A,C) stacked, w (G,C) (gn_energy_head_fwd_f32)."""
+    require_device(x, w)
+    x, w = _f32c(x), _f32c(w)
+    G, A, C = x.shape
+    E = torch.empty((A, 1), device=x.device, dtype=torch.float32)
+    check(_lib.load().gn_energy_head_fwd_f32(ptr(x), ptr(w), ptr(E), G, A, C, stream()), "gn_energy_head_fwd_f32")
+    return E
+
+
+def energy_head_bwd(g_E, w):
+    """g_x (G,A,C) = g_E[a] * w[g] (gn_energy_head_bwd_f32)."""
+    require_device(g_E, w)
+    g_E, w = _f32c(g_E), _f32c(w)
+    G, C = w.shape
+    A = g_E.shape[0]
+    g_x = torch.empty((G, A, C), device=w.device, dtype=torch.float32)
+    check(_lib.load().gn_energy_head_bwd_f32(ptr(g_E), ptr(w), ptr(g_x), G, A, C, stream()), "gn_energy_head_bwd_f32")
+    return g_x
 
 
 def bmm(A, B, ta, tb):
@@ -1232,9 +1296,38 @@ def _source(v, src, stage, cols):
     v[F_srcQ] = _mat(src["Q"], cols) if src["Q"] is not None else 0
 
 
-def chain(prog, mode=None):
-    """Run a ChainProgram (one launch)."""
-    from ._lib import GN_CHAIN_MAX_OPS, GN_OP_GEMM, GN_OP_LOAD, GN_OP_SCALE, GN_OP_STORE
+# tile height of the grouped launch (16 or 32 rows; 0 = the library's default, GN_CHAIN_GROUP_TILE_ROWS)
+GROUP_TILE_ROWS = int(os.environ.get("GN_CHAIN_GROUP_TILE_ROWS", "0"))
+
+
+def pack_weight_split_stacked(Ws, trans=False, fmt=None):
+    """The packed planes of G equally shaped weights back to back (the operand layout of the grouped chain launch)."""
+    if fmt is None:
+        fmt = split_format() or 0
+    W0 = Ws[0]
+    N, Kd = (W0.shape[1], W0.shape[0]) if trans else (W0.shape[0], W0.shape[1])
+    nbytes = -(-N // 16) * -(-Kd // 32) * (2 if fmt else 3) * 64 * 16
+    out = torch.empty((len(Ws), nbytes), device=W0.device, dtype=torch.uint8)
+    for g, W in enumerate(Ws):
+        require_device(W)
+        W = _rowmajor(W)
+        assert tuple(W.shape) == tuple(W0.shape)
+        check(_lib.load().gn_pack_weight_split_fmt(ptr(W), N, Kd, W.stride(0), int(bool(trans)), int(fmt), ptr(out[g]), stream()),
+              "gn_pack_weight_split_fmt")
+    out._gn_fmt = fmt
+    return out
+
+
+def chain_grouped_supported(mode=None):
+    """Does the grouped launch exist for this arithmetic and kernel layout?"""
+    return (mode or current_mode()) in ("h3", "split6") and CHAIN_LAYOUT == "tall"
+
+
+def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
+    """Run a ChainProgram (one launch).
+    groups > 0 (gn_chain_split_grouped_f32): `prog` describes group 0 — M rows, operands = the first slab of stacked tensors
+    whose slabs lie `group_pitch` rows apart, every `packed` = the G packed weights back to back (pack_weight_split_stacked)."""
+    from ._lib import GN_OP_GEMM, GN_OP_LOAD, GN_OP_SCALE, GN_OP_STORE
     ops = prog.ops
     if len(ops) > GN_CHAIN_MAX_OPS:
         raise ValueError("chain program too long")
@@ -1242,6 +1335,8 @@ def chain(prog, mode=None):
     nprod = CHAIN_MODES[mode]
     if nprod and not chain_split_supported(prog):
         nprod = 0
+    if groups and not (nprod and chain_grouped_supported(mode)):
+        raise RuntimeError(f"chain: no grouped launch in mode {mode!r} / layout {CHAIN_LAYOUT!r} for this program")
     fmt = SPLIT_FORMAT.get(mode, 0)
     row = nprod == CHAIN_MODES["h3"] and CHAIN_LAYOUT == "row"
     if row and not chain_row_supported(prog):
@@ -1378,7 +1473,23 @@ def chain(prog, mode=None):
         if WIDE_TILE_ROWS and (WIDE_TILE_ROWS % 8 or not 8 <= WIDE_TILE_ROWS <= 48):
             raise ValueError("GN_CHAIN_TILE_ROWS: a multiple of 8 in 8..48")
         nprod |= GN_CHAIN_WIDE | ((WIDE_TILE_ROWS // 8) << 12) | ((max(WIDE_STAGGER, 0) & 0xffff) << 16)
-    if nprod:
+    if groups:
+        if _lib.TRACE is not None:
+            # the argument block names group 0's slab of every operand; the launch touches all `groups` slabs, `group_pitch`
+            # rows apart, and the stacked packed weights: declared as regions (hbcheck.py)
+            reads, writes = [], []
+            for o in ops:
+                for key, t in o.items():
+                    if key == "packed" and t is not None:
+                        reads.append((t.data_ptr(), t.numel() * t.element_size()))
+                    elif torch.is_tensor(t) and key not in ("W", "packed") and t.dim() == 2:
+                        span = ((int(groups) - 1) * int(group_pitch) + t.shape[0]) * t.stride(0) * t.element_size()
+                        (writes if key in ("pre_out", "out", "out2") else reads).append((t.data_ptr(), span))
+            _lib.note(reads=reads, writes=writes)
+        check(_lib.load().gn_chain_split_grouped_f32(ctypes.addressof(cbuf), nprod, int(groups), int(group_pitch),
+                                                     GROUP_TILE_ROWS if tile_rows is None else int(tile_rows), stream()),
+              "gn_chain_split_grouped_f32")
+    elif nprod:
         check(_lib.load().gn_chain_split_f32(ctypes.addressof(cbuf), nprod, stream()), "gn_chain_split_f32")
     else:
         check(_lib.load().gn_chain_f32(ctypes.addressof(cbuf), stream()), "gn_chain_f32")

@@ -23,7 +23,7 @@ import torch
 
 from .. import ops
 from ..graph import GraphPlan
-from .layers import (AtomEmbedding, BesselBasisLayer, Dense, EdgeEmbedding,
+from .layers import (INV_SQRT_2, AtomEmbedding, BesselBasisLayer, Dense, EdgeEmbedding,
                      EfficientInteractionDownProjection, InteractionBlock,
                      InteractionBlockTripletsOnly, OutputBlock, SphericalBasisLayer, TensorBasisLayer)
 from .scaling import AutomaticFit
@@ -383,11 +383,22 @@ class GemNet(torch.nn.Module):
             if _RBF_OUT_ACC:
                 rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
 
-        # OutputBlock i only feeds the final energy sum: it runs on a side stream, concurrently with
-        # InteractionBlock i+1 (and, since autograd replays a node on its forward stream, so does its
-        # backward).  Its kernels are atom-side (A = 1024 rows: 32 workgroups) and latency-bound, so
-        # overlapping them is free.  Captured hipGraphs keep the fork/join as graph edges.
+        # OutputBlock i only feeds the final energy sum.  Two forms:
+        #  * grouped (`_out_group_blocks`: GemNet-T force pass with constant weights, the published widths, one target):
+        #    all blocks run ONCE, in line, after the last interaction block, as three launches over (block, atom) tiles
+        #    (ops.output_group: grouped aggregation, grouped chain launch, energy head) and three in the backward.  Per
+        #    block the launches are latency-bound and fill a quarter of the CUs; on a side stream they were not free
+        #    either (they slowed the main chain's kernels they ran beside, and the backward's five adjoint groups ran back
+        #    to back in front of the main chain's first adjoint).  Deferring them UNGROUPED measured 4.5 % slower than
+        #    the side stream: the grouping is the point.  Only the output blocks leave the side stream — the forked head
+        #    above stays on it.
+        #  * per block on a side stream (everything else), concurrently with InteractionBlock i+1 (and, since autograd
+        #    replays a node on its forward stream, so does its backward).  Captured hipGraphs keep the fork/join as
+        #    graph edges.
         outs = []
+        # decided HERE, before the first interaction block: a pass that does not group keeps the interleaved issue below
+        group = self._out_group_blocks(R, m, rbf_out)
+        group_ms = []
 
         def ready():
             """Event on the main stream: (h, m) of this point exist.  None without a side stream."""
@@ -418,25 +429,56 @@ class GemNet(torch.nn.Module):
         # (Issuing the output block of the LAST interaction block early — so that its backward is not enqueued between
         # the backward of output block nb, which the main chain waits for, and the main chain itself — measured 4 %
         # slower on the same box.)
-        # Same-box A/B of the issue lag (output block i after interaction block i + lag - 1): lag 0 (before) 11.20 k,
-        # 1 (here) 11.36-11.45 k, 2 11.16 k, 3 11.00 k, all at the end 10.84 k molecules/s.
         for i in range(self.num_blocks):
-            ev = ready()
+            ev = ready() if group is None else None
             h_i, m_i = h, m
             h, m = self.int_blocks[i](h=h, m=m, rbf4=rbf4, cbf4=cbf4, sbf4=sbf4, rbf3=rbf3, cbf3=cbf3,
                                       rbf_h=rbf_h, plan=plan)
-            out_block(i, h_i, m_i, ev)
-        out_block(self.num_blocks, h, m, ready())
+            if group is None:
+                out_block(i, h_i, m_i, ev)
+            else:
+                group_ms.append(m_i)
+        if group is None:
+            out_block(self.num_blocks, h, m, ready())
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-        E_a, F_ca = outs[-1][0], outs[0][1]
-        for _, F in outs[1:]:
-            F_ca = F_ca + F
+        if group is not None:
+            # every block's aggregation joins the running gradient of its m (ops.accumulate_gradient in the interaction
+            # block that consumed it): the grouped adjoint runs first in the backward and seeds those sums
+            if side is not None:
+                rbf_out.record_stream(torch.cuda.current_stream())     # (produced on the side stream without the fused head)
+            E_a, F_ca = ops.output_group(group, group_ms + [m], rbf_out, plan.id_a, s=INV_SQRT_2), 0
+        else:
+            E_a, F_ca = outs[-1][0], outs[0][1]
+            for _, F in outs[1:]:
+                F_ca = F_ca + F
 
         E_mol = ops.segsum_rows(E_a, plan.batch_seg)                      # (nMolecules, num_targets)
         if not self.extensive:
             E_mol = E_mol / plan.atoms_per_mol.clamp(min=1)[:, None]
         return E_mol, F_ca, V_ca
+
+    def _out_group_blocks(self, R, m, rbf_out):
+        """The OutputBlocks in the form `ops.output_group` takes, or None when this pass keeps one set of launches per block:
+        GemNet-Q, training (trainable weights / the twice-differentiable path), direct forces, scale fitting, several
+        targets, host tensors, blocks that are not Dense + ResidualLayer stacks on the fused aggregation, and whatever
+        `ops.output_group_supported` turns away (other widths, a chain arithmetic or kernel layout without the grouped launch,
+        the aggregation switched off).  `m`: the edge embedding — every block's m has its shape."""
+        if not (self.triplets_only and R.is_cuda and ops.is_fused() and ops.constant_weights() and not ops.train2_enabled()
+                and not self.direct_forces and not AutomaticFit.fitting_mode and ops.USE_OUT_GROUP):
+            return None
+        blocks = []
+        for ob in self.out_blocks:
+            if not (ob.fuse_aggregate and not ob.direct_forces and ob.dense_rbf.bias is None and not ob.dense_rbf.act
+                    and ob._stackable(ob.seq_energy) and ob.out_energy.bias is None and not ob.out_energy.act
+                    and ob.out_energy.weight.shape[0] == 1):
+                return None
+            gemms = [ob.seq_energy[0].weight]
+            for layer in ob.seq_energy[1:]:
+                gemms += [layer.dense_mlp[0].weight, layer.dense_mlp[1].weight]
+            blocks.append(dict(W_rbf=ob.dense_rbf.weight, scale=ob.scale_sum.scale_factor, gemms=gemms,
+                               act0=bool(ob.seq_energy[0].act), w_out=ob.out_energy.weight))
+        return blocks if ops.output_group_supported(blocks, [m] * len(blocks), rbf_out) else None
 
     def _radial_head(self, R, plan, proj):
         b3 = self.cbf_basis3

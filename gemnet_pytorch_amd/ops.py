@@ -1491,6 +1491,153 @@ def stack(x, first=None, layers=(), s=0.7071067811865475, tails=()):
     return _Stack.apply(spec, x, res, res2, g1, g2, *skips)
 
 
+# ---------------------------------------------------------------------------------------------- grouped output blocks
+# All OutputBlocks of a model as ONE op.  Nothing consumes an output block except the final energy
+# sum and, in the force pass, its weights are constants: the G blocks run as one pass over (block, atom) tiles after the
+# last interaction block — grouped aggregation -> grouped chain launch -> energy head, three launches instead of 3 G — and
+# their adjoint as three launches at the start of the backward.  GEMNET_OUT_GROUP=0 keeps one set of launches per block.
+USE_OUT_GROUP = os.environ.get("GEMNET_OUT_GROUP", "1") == "1"
+OUT_GROUP_CALLS = 0       # forwards that took the grouped path (tests assert eligibility through it)
+
+
+def _stacked_form(tag, Ws, make):
+    """A form derived from SEVERAL frozen weights (the G blocks' copies of one layer), cached on their addresses and
+    versions like `cached_form`."""
+    key = (tag,) + tuple((W.data_ptr(), tuple(W.shape), tuple(W.stride())) for W in Ws)
+    return _cached(key, tuple(W._version for W in Ws), make)
+
+
+def _stacked_packed(Ws, trans):
+    return _stacked_form(("pkgt" if trans else "pkg", K.split_format()), Ws,
+                         lambda: K.pack_weight_split_stacked([W.detach() for W in Ws], trans=trans))
+
+
+class _OutputGroup(torch.autograd.Function):
+    """E_a (A,1) = sum_g out_energy_g(MLP_g(scale_g * sum_{e -> a} m_g[e] (.) (W_rbf,g rbf[e]))): the energy part of all
+    OutputBlocks (atom_update_block.py:157-172 and the sum gemnet.py:596-600).  Forward: grouped aggregation, grouped chain
+    (Dense + ResidualLayers, ssilu' stored), energy head.  Backward: the seed, the grouped adjoint chain, the grouped
+    aggregation adjoint — g_m[g] seeds (or adds to) the running gradient of m_g, g_rbf is summed over the groups in-kernel."""
+
+    @staticmethod
+    def forward(ctx, spec, rbf, *ms):
+        ri, s, blocks = spec["ri"], spec["s"], spec["blocks"]
+        G = len(ms)
+        perm, seg = ri.csr
+        A = ri.n_rows
+        ctx.acc_m = [_acc_join(m, cross=True) for m in ms]
+        ctx.acc_rbf = _acc_join(rbf)
+        W_rbf = [contiguous_weight(b["W_rbf"]) for b in blocks]
+        scales = _stacked_form("ogs", [b["scale"] for b in blocks],
+                               lambda: torch.stack([b["scale"].detach().reshape(()) for b in blocks]).float().contiguous())
+        w_out = _stacked_form("ogw", [b["w_out"] for b in blocks],
+                              lambda: torch.cat([b["w_out"].detach().reshape(1, -1) for b in blocks]).contiguous())
+        x = K.rbf_aggregate_grouped_fwd(ms, rbf, W_rbf, scales, perm, seg, A)
+        # the program of _Stack.forward, written once for group 0 of the stacked operands
+        gemms = spec["gemms"]                  # per GEMM of the stack: the G blocks' weights
+        n_layers = (len(gemms) - 1) // 2
+        act0 = blocks[0]["act0"]
+        zs = [torch.empty((G, A, Ws[0].shape[0]), device=x.device, dtype=x.dtype) for Ws in gemms]
+        if not act0:
+            zs[0] = None
+        y = torch.empty((G, A, gemms[-1][0].shape[0]), device=x.device, dtype=x.dtype)
+        prog = K.ChainProgram(A)
+        prog.load(0, x[0])
+        prog.gemm(gemms[0][0], packed=_stacked_packed(gemms[0], False), a_slot=0, y_slot=1, act=act0, pre_deriv=act0,
+                  pre_out=zs[0][0] if act0 else None, out=None if n_layers else y[0])
+        cur, oth = 1, 0
+        for k in range(n_layers):
+            last = k + 1 == n_layers
+            prog.gemm(gemms[1 + 2 * k][0], packed=_stacked_packed(gemms[1 + 2 * k], False), a_slot=cur, y_slot=oth, act=True,
+                      pre_out=zs[1 + 2 * k][0], pre_deriv=True)
+            prog.gemm(gemms[2 + 2 * k][0], packed=_stacked_packed(gemms[2 + 2 * k], False), a_slot=oth, y_slot=cur, act=True,
+                      pre_out=zs[2 + 2 * k][0], pre_deriv=True, res=cur, beta=s, out=y[0] if last else None)
+        ctx.mode = K.current_mode()
+        K.chain(prog, groups=G, group_pitch=A)
+        E_a = K.energy_head_fwd(y, w_out)
+        ctx.spec = spec
+        ctx.n_z = len(zs)
+        ctx.has_z0 = act0
+        ctx.save_for_backward(rbf, scales, w_out, *W_rbf, *ms, *[z for z in zs if z is not None])
+        return E_a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @_in_mode
+    def backward(ctx, g_E):
+        spec = ctx.spec
+        ri, s, gemms = spec["ri"], spec["s"], spec["gemms"]
+        G = len(spec["blocks"])
+        saved = list(ctx.saved_tensors)
+        rbf, scales, w_out = saved[:3]
+        W_rbf, ms, zs = saved[3:3 + G], saved[3 + G:3 + 2 * G], saved[3 + 2 * G:]
+        if not ctx.has_z0:
+            zs = [None] + zs
+        A = ri.n_rows
+        n_layers = (len(gemms) - 1) // 2
+        g_y = K.energy_head_bwd(g_E.contiguous(), w_out)                 # (G, A, C): the seed of every block's adjoint
+        width = g_y.shape[2]
+        # the program of _Stack.backward (no skips, no residuals of the first Dense) for group 0 of the stacked operands
+        prog = K.ChainProgram(A)
+        prog.load(0, g_y[0])
+        cur, oth = 0, 1
+        for k in range(n_layers - 1, -1, -1):
+            z1, z2 = zs[1 + 2 * k], zs[2 + 2 * k]
+            prog.scale(cur, cur, s, width=width)                      # G = dL/d(x + f(x))
+            prog.scale(oth, cur, 1.0, Z=z2[0], mode=1)                # dz2 (the saved tensors hold ssilu'(z))
+            prog.gemm(gemms[2 + 2 * k][0].t(), packed=_stacked_packed(gemms[2 + 2 * k], True), a_slot=oth, y_slot=oth)
+            prog.scale(oth, oth, 1.0, Z=z1[0], mode=1)                # dz1
+            prog.gemm(gemms[1 + 2 * k][0].t(), packed=_stacked_packed(gemms[1 + 2 * k], True), a_slot=oth, y_slot=cur,
+                      res=cur, beta=1.0)
+        src = cur
+        if zs[0] is not None:
+            prog.scale(oth, cur, 1.0, Z=zs[0][0], width=width, mode=1)
+            src = oth
+        g_x = torch.empty((G, A, gemms[0][0].shape[1]), device=g_y.device, dtype=g_y.dtype)
+        prog.gemm(gemms[0][0].t(), packed=_stacked_packed(gemms[0], True), a_slot=src, y_slot=-1, out=g_x[0])
+        K.chain(K.fuse_program(prog), groups=G, group_pitch=A)
+        # aggregation adjoint: per block the running gradient of its m (the interaction block's own consumers add onto it
+        # later, in their kernels), one g_rbf summed over the blocks in-kernel
+        entered = [acc.enter() if acc is not None else (None, True) for acc in ctx.acc_m]
+        acc_r = ctx.acc_rbf
+        prev_r, last_r = acc_r.enter() if acc_r is not None else (None, True)
+        g_m, g_rbf = K.rbf_aggregate_grouped_bwd(g_x, ms, rbf, W_rbf, scales, ri.idx32, acc_m=[p for p, _ in entered],
+                                                 want_rbf=ctx.needs_input_grad[1] or acc_r is not None, acc_rbf=prev_r)
+        for acc, (_, last), gm in zip(ctx.acc_m, entered, g_m):
+            if acc is not None:
+                acc.leave(gm, last)
+        if acc_r is not None:
+            acc_r.leave(g_rbf, last_r)
+        return (None, g_rbf if last_r else None) + tuple(gm if last else None for gm, (_, last) in zip(g_m, entered))
+
+
+def output_group_supported(blocks, ms, rbf):
+    """Can `output_group` run these OutputBlocks?  Constant weights, the fused aggregation and stack shapes (128 columns,
+    16 radial features), one target, a chain arithmetic / layout that has the grouped launch."""
+    if not (USE_OUT_GROUP and USE_AGGREGATE and constant_weights() and stacks_enabled() and not _TRAIN2):
+        return False
+    if not (1 <= len(blocks) <= 8 and K.chain_grouped_supported()):
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in (rbf, *ms)):
+        return False
+    for b, m in zip(blocks, ms):
+        Ws = b["gemms"]
+        if not (K.rbf_aggregate_supported(m, rbf, b["W_rbf"]) and tuple(b["w_out"].shape) == (1, 128) and len(Ws) % 2 == 1
+                and tuple(Ws[0].shape) == (128, 128) and all(tuple(W.shape) == (128, 128) for W in Ws)
+                and b["act0"] == blocks[0]["act0"] and len(Ws) == len(blocks[0]["gemms"])):
+            return False
+    return 2 * len(blocks[0]["gemms"]) + 4 <= K.GN_CHAIN_MAX_OPS
+
+
+def output_group(blocks, ms, rbf, ri, s=0.7071067811865475):
+    """Sum over the OutputBlocks of their per-atom energies, (A,1).  blocks[g]: dict(W_rbf, scale (the 0-dim scale_sum
+    parameter), gemms = [W0, W1, W2, ...] (Dense + ResidualLayer pairs), act0, w_out (1,128)); ms[g]: the block's m."""
+    global OUT_GROUP_CALLS
+    OUT_GROUP_CALLS += 1
+    n = len(blocks[0]["gemms"])
+    spec = dict(ri=ri, s=float(s), blocks=blocks, gemms=[[b["gemms"][j] for b in blocks] for j in range(n)])
+    return _OutputGroup.apply(spec, rbf, *ms)
+
+
 class _DenseHadamardDown(torch.autograd.Function):
     """x -> Dense_a(x) (.) (rbf W_r^T) * alpha -> Dense_d(.) as ONE launch forward and ONE backward (gn_chain_f32):
     the head of TripletInteraction / QuadrupletInteraction (interaction_block.py:667-675, :531-541: dense_ba/db,

@@ -173,6 +173,21 @@ int gn_chain_f32(const gn_chain_args* args, void* stream);
 #define GN_CHAIN_WIDE_STAGGER(u) (((u) & 0xffff) << 16)
 /* A program must start with a GN_OP_LOAD (the kernel's prologue relies on that op's barrier); else hipErrorInvalidValue. */
 int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream);
+/* Grouped launch: the SAME program for `groups` <= GN_CHAIN_MAX_GROUPS independent row ranges with their own weights, in one
+ * launch — the five OutputBlocks of a model (atom_update_block.py:100-172) are five such stacks of 1 024 rows, 64 workgroups
+ * each as single launches.  `args` describes group 0 (M = rows of ONE group); group g reads and writes rows
+ * g * group_pitch + [0, M) of every global operand (stacked row-major tensors, group_pitch >= M rows apart) and multiplies by
+ * the g-th packed weight of every GEMM op: the groups' packed weights lie back to back behind `W`, each
+ * ceil(N/16) * ceil(K/32) * planes * 1024 bytes (planes = 2 for GN_CHAIN_F16X2, 3 for nprod = 6).  The strided form rather than
+ * a table of programs: the groups differ in nothing but those offsets, the argument block stays the by-value gn_chain_args of
+ * the single launch (no device table to keep alive for a captured graph), and a workgroup finds its operands with one
+ * multiply-add per pointer.  A workgroup owns one tile of `tile_rows` (16 or 32; 0 = GN_CHAIN_GROUP_TILE_ROWS) rows of one
+ * group: a tile never spans two groups, rows past M are masked as in the single launch.
+ * nprod: GN_CHAIN_F16X2 or 6 (the "tall" layout only).  Programs with row gathers (rows, gadd1/2, res_rows): hipErrorInvalidValue.
+ * groups * group_pitch <= 2^24.  Results: bit for bit those of `groups` gn_chain_split_f32 launches. */
+#define GN_CHAIN_MAX_GROUPS 8
+#define GN_CHAIN_GROUP_TILE_ROWS 32
+int gn_chain_split_grouped_f32(const gn_chain_args* args, int nprod, int groups, int group_pitch, int tile_rows, void* stream);
 /* the automatic tile height of the wide layout for M rows (a pure function) */
 int gn_chain_wide_tile_rows(int M);
 /* W (N,K) fp32 with row pitch ldw — or, trans != 0, the (K,N) matrix whose transpose is the weight — -> three bf16
@@ -242,6 +257,29 @@ int gn_rbf_aggregate_fwd_f32(const float* m, const float* rbf, const float* W, c
                              float* out, int64_t n_atoms, int C, int R, float scale, void* stream);
 int gn_rbf_aggregate_bwd_f32(const float* g_out, const float* m, const float* rbf, const float* W, const int32_t* id_a,
                              float* g_m, float* g_rbf, int64_t E, int C, int R, float scale, int accum, void* stream);
+
+/* Grouped forms for the G <= GN_AGG_MAX_GROUPS OutputBlocks of a model, which share rbf and the CSR but have their own m, W and
+ * scale (pointer tables are HOST arrays, copied into the kernel's argument block; `scales` (G) lives on the device):
+ *   forward: out (G, n_atoms, C) stacked; out[g] is bit for bit gn_rbf_aggregate_fwd_f32(m_list[g], rbf, W_list[g], scales[g]).
+ *   adjoint: g_out (G, n_atoms, C) stacked; g_m_list[g] (E,C) bit for bit the single launch's g_m (bit g of `accum_m`: +=);
+ *            ONE g_rbf (E,R) = sum over g = 0 .. G-1, in that order, of the single launches' g_rbf (accum_rbf != 0: g_rbf +=).
+ *            A wave handles one edge for all groups: the indices, the rbf row and g_rbf are touched once per edge. */
+#define GN_AGG_MAX_GROUPS 8
+int gn_rbf_aggregate_grouped_fwd_f32(const float* const* m_list, const float* const* W_list, const float* scales, int G,
+                                     const float* rbf, const int32_t* perm, const int32_t* seg_off, float* out, int64_t n_atoms,
+                                     int C, int R, void* stream);
+int gn_rbf_aggregate_grouped_bwd_f32(const float* g_out, const float* const* m_list, const float* const* W_list,
+                                     const float* scales, int G, const float* rbf, const int32_t* id_a, float* const* g_m_list,
+                                     float* g_rbf, int64_t E, int64_t n_atoms, int C, int R, int accum_m, int accum_rbf,
+                                     void* stream);
+
+/* ---- energy head of the grouped OutputBlocks (csrc/energy_head.hip) ---------------------------------------------------
+ * E_a = sum over the OutputBlocks of out_energy(x_g) (atom_update_block.py:168-172 and the sum gemnet.py:596-600), one target:
+ *   forward: E[a] = sum_{g = 0 .. G-1, in this order} w[g] . x[g, a, :]      x (G, n_atoms, C) stacked, w (G, C), E (n_atoms)
+ *   adjoint: g_x[g, a, :] = g_E[a] * w[g]                                     (the seed of the grouped adjoint chain)
+ * C == 128; G <= 8. */
+int gn_energy_head_fwd_f32(const float* x, const float* w, float* E, int G, int64_t n_atoms, int C, void* stream);
+int gn_energy_head_bwd_f32(const float* g_E, const float* w, float* g_x, int G, int64_t n_atoms, int C, void* stream);
 
 /* ---- tensor basis in ANGLE form (csrc/geometry.hip, csrc/bilinear_ang.hip) ------------------------------------------
  * Instead of the (Q, S^2 = 49) harmonics of TensorBasisLayer (basis_layers.py:239-295) — 196 B per quadruplet, re-read
