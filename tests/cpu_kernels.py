@@ -612,6 +612,63 @@ def cbf_project_bwd(g, rad, seg_off, y, W):
     return g_rad, g_y
 
 
+# ---- fp64 restatements of the first-order periodic kernels of csrc/pbc.hip (on edge vectors).  They are yardsticks of
+# tests/test_gpu_pbc_cases.py, not launchers: `emulate()` does not install them.
+def pbc_edge_vec(R, id_c, id_a, batch_seg, cell, offs):
+    """V_e = R[a] - (R[c] + n_e cell_b), b the structure of atom a (gn_pbc_edge_vec_f32)."""
+    a, c = id_a.long(), id_c.long()
+    shift = torch.einsum("ek,ekj->ej", offs.to(R.dtype), cell[batch_seg.long()[a]])
+    return R[a] - (R[c] + shift)
+
+
+def edge_basis_vec_fwd(V, freq, z, nrm, cutoff, p):
+    """-> D (E,), rbf (E,NR), rad (E,S,NR) (gn_edge_basis_vec_fwd_f32)."""
+    D = torch.sqrt((V * V).sum(1))
+    return D, bessel_rbf(D, freq, cutoff, p, 0, 0), sph_radial(D, z, nrm, cutoff, p, 0)
+
+
+def edge_basis_vec_bwd(gD, g_rbf, g_rad, V, freq, z, nrm, cutoff, p):
+    """-> W (E,3) = dE/dV_e = (gD + <g_rbf, d rbf/dD> + <g_rad, d rad/dD>) V / D (gn_edge_basis_vec_bwd_f32)."""
+    D = torch.sqrt((V * V).sum(1))
+    g = torch.zeros_like(D)
+    if gD is not None:
+        g = g + gD
+    if g_rbf is not None:
+        g = g + (g_rbf * bessel_rbf(D, freq, cutoff, p, 1, 0)).sum(1)
+    if g_rad is not None:
+        g = g + (g_rad * sph_radial(D, z, nrm, cutoff, p, 1)).sum((1, 2))
+    return g[:, None] * V / D[:, None]
+
+
+def trip_basis_vec_fwd(V, red, exp, S):
+    """-> Y (T,S), theta (T,): the angle between u = -V[reduce edge] and v = -V[expand edge] (gn_trip_basis_vec_fwd_f32)."""
+    th = _angle_uv(-V[red.long()], -V[exp.long()])
+    return ylm0(th, S, 0), th
+
+
+def trip_basis_vec_bwd(gY, V, red, exp):
+    """-> Gu, Gv (T,3) = dE/du, dE/dv with the reference's max(|u x v|, 1e-9) clamp: a clamped row keeps only the d/dx term
+    (gn_trip_basis_vec_bwd_f32)."""
+    with torch.enable_grad():
+        u = (-V[red.long()]).detach().clone().requires_grad_(True)
+        v = (-V[exp.long()]).detach().clone().requires_grad_(True)
+        th = _angle_uv(u, v)
+        gth = (gY * ylm0(th.detach(), gY.shape[1], 1)).sum(1)
+        Gu, Gv = torch.autograd.grad(th, (u, v), gth)
+    return Gu, Gv
+
+
+def pbc_stress(V, G, perm, seg_off, cell, scale=-1.0):
+    """S[b] = scale / |det cell_b| sum over the edges perm[seg_off[b] : seg_off[b + 1]] of V_e (x) G_e (gn_pbc_stress_f32)."""
+    B_ = cell.shape[0]
+    out = torch.zeros((B_, 3, 3), dtype=V.dtype)
+    for b in range(B_):
+        e = torch.arange(int(seg_off[b]), int(seg_off[b + 1]))
+        e = e if perm is None else perm.long()[e]
+        out[b] = scale * torch.einsum("ei,ej->ij", V[e], G[e]) / torch.linalg.det(cell[b]).abs()
+    return out
+
+
 _NAMES = ["cbf_project_supported", "cbf_project_fwd", "cbf_project_bwd", "quad_angles_jvp", "bil_reduce_project_tan", "bil_reduce_t_tan", "bil_ang_train_supported", "dist_fwd", "dist_bwd", "dist_jvp", "angle_fwd", "angle_bwd", "angle_jvp", "bil_train_supported", "gather_mul", "bil_fused_bwd", "bil_fused_bwd_supported", "segsum_multi", "is_angle_form", "quad_angles_fwd", "quad_angles_bwd", "rbf_aggregate_fwd", "rbf_aggregate_bwd", "bil_fused_fwd", "quad_basis_fwd", "quad_basis_bwd", "quad_basis_bwd_packed", "bil_reduce_project", "bil_project_bwd", "bil_dy_multi", "chain", "edge_basis_fwd", "edge_basis_bwd", "trip_basis_fwd", "trip_basis_bwd", "gemm", "dact_mul", "gather", "segsum", "bmm", "ssilu", "pm", "bil_reduce", "bil_reduce_t", "bil_dot",
           "bessel_rbf", "sph_radial", "ylm0", "ylm"]
 

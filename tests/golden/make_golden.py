@@ -724,8 +724,40 @@ def golden_fullsize():
     print("fullsize.npz", len(out), "arrays; fullsize_index.json", len(digests), "digests")
 
 
+# ----------------------------------------------------- G8: periodic cluster-oracle results (no reference code involved)
+PBC_CASES = ("cubic1", "bcc", "bcc_pert", "thin", "skewed", "skewed_lh")
+
+
+def _pbc_case(kind):
+    torch.set_num_threads(1)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pbc_common as P
+    params = P.make_params()
+    R, Z, cell, pbc = P.structure(kind)
+    E = P.cluster_energy(params, R, Z, cell, pbc)
+    F, S = P.fd_forces_stress(params, R, Z, cell, pbc)
+    return kind, dict(R=R, Z=Z, cell=cell, pbc=pbc, E=np.array(E), F=F, S=S)
+
+
+def golden_pbc_cases():
+    """-> pbc_cases.npz: `cluster_energy` and `fd_forces_stress` of tests/pbc_common.py (the project's own fp64 cluster oracle,
+    under P.CFG and P.make_params()) for the cells whose clusters are too large to evaluate inside a test (a bcc cluster has 392
+    atoms, and the central differences take about thirty energies per case).  tests/test_pbc_cpu.py recomputes every stored
+    energy and one force and one stress component per case."""
+    from concurrent.futures import ProcessPoolExecutor
+    import multiprocessing as mp
+    out = {}
+    with ProcessPoolExecutor(max_workers=len(PBC_CASES), mp_context=mp.get_context("fork")) as pool:
+        for kind, res in pool.map(_pbc_case, PBC_CASES):
+            for k, v in res.items():
+                out[f"{kind}.{k}"] = v
+            print(kind, "E", float(res["E"]), "|F|max", float(np.abs(res["F"]).max()), "S diag", np.diag(res["S"]), flush=True)
+    np.savez_compressed(os.path.join(HERE, "pbc_cases.npz"), **out)
+    print("pbc_cases.npz", len(out), "arrays")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["basis", "indices", "models", "models2", "keys", "trainer", "scaling", "tfnames", "fullsize"]
+    which = sys.argv[1:] or ["basis", "indices", "models", "models2", "keys", "trainer", "scaling", "tfnames", "fullsize", "pbc"]
     if "tfnames" in which:
         golden_tfnames()
     if "scaling" in which:
@@ -744,3 +776,5 @@ if __name__ == "__main__":
         golden_keys()
     if "fullsize" in which:
         golden_fullsize()
+    if "pbc" in which:
+        golden_pbc_cases()
