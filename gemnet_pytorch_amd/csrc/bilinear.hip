@@ -565,13 +565,42 @@ constexpr int FTE = 16, FLDP = 1024 + 4;
 typedef _Float16 h8_b __attribute__((ext_vector_type(8)));
 constexpr int FPH = 1024 + 8;      // fp16 elements per P-plane row (2 064 B: the 16 rows of a b128 read fall in distinct banks)
 
-template <bool HP>
+// UP (gn_bil_up_fwd_f32): the two 64 -> 128 up projections of the interaction tail run as one more phase on the 16 x 64 output
+// tile instead of as a launch of their own.  The kq = 0 waves park the alpha-scaled tile in LDS as fp32 (in the P planes, dead
+// after K3); every wave then forms the B fragments of the 16 edge rows exactly as phase 1 of the fused adjoint does (row
+// maximum -> exact power-of-two scale, hi / 2^11 lo fp16 planes: no range limit beyond K3's own) and multiplies them with its
+// 16 rows of the packed cat(W_ac, W_ca) (256 x 64, gn_pack_weight_split_fmt(.., GN_SPLIT_F16X2)): waves 0-7 own z_ac, waves
+// 8-15 z_ca.  A lane ends with four consecutive columns of one edge: z and y = alpha_up ssilu(z) leave as float4; `out` is
+// never written.  A row's result depends on that row alone (its own scale, its own MFMA column).
+struct bil_up_fwd_args {
+  const uint4* Wp;            // cat(W_ac, W_ca) as two fp16 planes, [16 tiles][2 chunks][2 planes][64 lanes]
+  float *z_ac, *z_ca;         // (E,128) pre-activations (act != 0 only)
+  float *y_ac, *y_ca;         // (E,128)
+  float alpha;
+  int act;
+};
+constexpr int UPLD = 64 + 4;       // fp32 pitch of the 16 x 64 tile between K3 and the up projections
+
+// one exact power-of-two scale per cotangent / activation row: maximum m -> [0.25, 0.5); a zero row takes scale 1
+__device__ __forceinline__ void bil_row_scale(float m, float& sigma, float& inv_sigma) {
+  sigma = 1.f, inv_sigma = 1.f;
+  const uint32_t ex = __float_as_uint(m) >> 23;
+  const uint32_t ec = ex < 2u ? 2u : (ex > 250u ? 250u : ex);
+  if (m > 0.f) {
+    sigma = __uint_as_float((252u - ec) << 23);
+    inv_sigma = __uint_as_float((2u + ec) << 23);
+  }
+}
+
+template <bool HP, bool UP = false>
 __global__ __launch_bounds__(1024) void bil_fused_fwd_mfma7_kernel(const float* __restrict__ Y, const float* __restrict__ x,
                                                      const int32_t* __restrict__ expand_idx,
                                                      const int32_t* __restrict__ seg_off, const float* __restrict__ B,
                                                      const float* __restrict__ W2T, const uint4* __restrict__ W2Tp,
                                                      float* __restrict__ Sm,
-                                                     float* __restrict__ out, int64_t E, float alpha) {
+                                                     float* __restrict__ out, int64_t E, float alpha,
+                                                     const bil_up_fwd_args up) {
+  static_assert(HP || !UP, "the up projections ride on the fp16-plane K3");
   constexpr int S = 7, C = 64, I = 16;
   extern __shared__ __attribute__((aligned(16))) float Pl[];   // [FFTE][FFLDP] (HP: two fp16 planes [FTE][FPH]) + partial tiles
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -678,6 +707,71 @@ __global__ __launch_bounds__(1024) void bil_fused_fwd_mfma7_kernel(const float* 
     v4f_b c0 = ch + cx * (1.f / 2048.f);
     if (kq > 0) *reinterpret_cast<v4f_b*>(red + (((kq - 1) * 4 + nt) * 64 + lane) * 4) = c0;
     __syncthreads();
+    if constexpr (UP) {
+      // the weight fragments of this wave's 16 output columns: requested before the tile is complete
+      const uint4* __restrict__ up_w = up.Wp + (size_t)(wave * 4) * 64 + lane;      // [tile][chunk][plane][lane]
+      h8_b uh[2], ul[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        uh[c] = __builtin_bit_cast(h8_b, up_w[(2 * c) * 64]);
+        ul[c] = __builtin_bit_cast(h8_b, up_w[(2 * c + 1) * 64]);
+      }
+      float* xt = Pl;     // [FTE][UPLD]: every wave read its last P fragment in front of the barrier above
+      if (kq == 0) {
+#pragma unroll
+        for (int z = 0; z < 3; ++z) c0 += *reinterpret_cast<const v4f_b*>(red + ((z * 4 + nt) * 64 + lane) * 4);
+        *reinterpret_cast<float4*>(xt + l15 * UPLD + 16 * nt + 4 * lg) =
+            make_float4(alpha * c0[0], alpha * c0[1], alpha * c0[2], alpha * c0[3]);
+      }
+      __syncthreads();
+      // B operand: x[e = l15][o = 32 c + 8 lg + i]  (rows past E are zero: scale 1, never stored)
+      float xv[2][8];
+      float m = 0.f;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float* xr = xt + l15 * UPLD + 32 * c + 8 * lg;
+        const float4 u0 = *reinterpret_cast<const float4*>(xr), u1 = *reinterpret_cast<const float4*>(xr + 4);
+        xv[c][0] = u0.x; xv[c][1] = u0.y; xv[c][2] = u0.z; xv[c][3] = u0.w;
+        xv[c][4] = u1.x; xv[c][5] = u1.y; xv[c][6] = u1.z; xv[c][7] = u1.w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(xv[c][i]));
+      }
+      m = fmaxf(m, __shfl_xor(m, 16, 64));       // the four lanes (lg) that hold the row of edge l15
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      float sigma, inv_sigma;
+      bil_row_scale(m, sigma, inv_sigma);
+      v4f_b uch = (v4f_b){0.f, 0.f, 0.f, 0.f}, ucx = uch;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        h8_b xh, xl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float v = xv[c][i] * sigma;
+          const _Float16 h = (_Float16)v;
+          xh[i] = h;
+          xl[i] = (_Float16)((v - (float)h) * 2048.f);
+        }
+        uch = __builtin_amdgcn_mfma_f32_16x16x32_f16(uh[c], xh, uch, 0, 0, 0);
+        ucx = __builtin_amdgcn_mfma_f32_16x16x32_f16(uh[c], xl, ucx, 0, 0, 0);
+        ucx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ul[c], xh, ucx, 0, 0, 0);
+      }
+      // D^T: row = up column 16 (wave & 7) + 4 lg + r of z_ac (waves 0-7) / z_ca (waves 8-15), col = edge l15
+      const v4f_b zc = (uch + ucx * (1.f / 2048.f)) * inv_sigma;
+      const int64_t e = e0 + l15;
+      if (e < E) {
+        const int64_t off = e * 128 + 16 * (wave & 7) + 4 * lg;
+        float* __restrict__ yo = (wave < 8 ? up.y_ac : up.y_ca) + off;
+        if (up.act) {
+          float* __restrict__ zo = (wave < 8 ? up.z_ac : up.z_ca) + off;
+          *reinterpret_cast<float4*>(zo) = make_float4(zc[0], zc[1], zc[2], zc[3]);
+          *reinterpret_cast<float4*>(yo) = make_float4(gn_ssilu(zc[0]) * up.alpha, gn_ssilu(zc[1]) * up.alpha,
+                                                       gn_ssilu(zc[2]) * up.alpha, gn_ssilu(zc[3]) * up.alpha);
+        } else {
+          *reinterpret_cast<float4*>(yo) = make_float4(zc[0] * up.alpha, zc[1] * up.alpha, zc[2] * up.alpha, zc[3] * up.alpha);
+        }
+      }
+      return;
+    }
     if (kq == 0) {
 #pragma unroll
       for (int z = 0; z < 3; ++z) c0 += *reinterpret_cast<const v4f_b*>(red + ((z * 4 + nt) * 64 + lane) * 4);
@@ -1423,10 +1517,37 @@ extern "C" int gn_bil_fused_fwd_f32(const float* Y, const float* x, const int32_
   }
   if (W2T_planes)
     hipLaunchKernelGGL(bil_fused_fwd_mfma7_kernel<true>, dim3(gn_cdiv(E, FTE)), dim3(1024), lds, static_cast<hipStream_t>(stream),
-                       Y, x, expand_idx, seg_off, B, W2T, static_cast<const uint4*>(W2T_planes), Sm, out, E, alpha);
+                       Y, x, expand_idx, seg_off, B, W2T, static_cast<const uint4*>(W2T_planes), Sm, out, E, alpha,
+                       bil_up_fwd_args{});
   else
     hipLaunchKernelGGL(bil_fused_fwd_mfma7_kernel<false>, dim3(gn_cdiv(E, FTE)), dim3(1024), lds, static_cast<hipStream_t>(stream),
-                       Y, x, expand_idx, seg_off, B, W2T, nullptr, Sm, out, E, alpha);
+                       Y, x, expand_idx, seg_off, B, W2T, nullptr, Sm, out, E, alpha, bil_up_fwd_args{});
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_bil_up_fwd_f32(const float* Y, const float* x, const int32_t* expand_idx, const int32_t* seg_off,
+                                 const float* B, const void* W2T_planes, const void* Wup_planes, float* Sm, float* z_ac,
+                                 float* z_ca, float* y_ac, float* y_ca, int64_t E, int S, int C, int I, int O, int N_up,
+                                 float alpha, float alpha_up, int act, void* stream) {
+  if (E <= 0) return 0;
+  if (S != 7 || C != 64 || I != 16 || O != 64 || N_up != 128 || !W2T_planes || !Wup_planes) return (int)hipErrorInvalidValue;
+  if (!aligned16(W2T_planes) || !aligned16(Wup_planes) || !y_ac || !y_ca || !aligned16(y_ac) || !aligned16(y_ca))
+    return (int)hipErrorInvalidValue;
+  if (act && (!z_ac || !z_ca || !aligned16(z_ac) || !aligned16(z_ca))) return (int)hipErrorInvalidValue;
+  constexpr size_t lds = (size_t)2 * FTE * FPH * 2 + (size_t)3 * 4 * 64 * 4 * sizeof(float);   // the tile reuses the P planes
+  static_assert((size_t)FTE * UPLD * sizeof(float) <= (size_t)2 * FTE * FPH * 2, "the x tile lives in the P planes");
+  static std::atomic<bool> configured{false};   // set-once flag of an idempotent attribute (two racing threads both set it)
+  if (!configured.load(std::memory_order_acquire)) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bil_fused_fwd_mfma7_kernel<true, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    configured.store(true, std::memory_order_release);
+  }
+  const bil_up_fwd_args up{static_cast<const uint4*>(Wup_planes), z_ac, z_ca, y_ac, y_ca, alpha_up, act};
+  hipLaunchKernelGGL((bil_fused_fwd_mfma7_kernel<true, true>), dim3(gn_cdiv(E, FTE)), dim3(1024), lds,
+                     static_cast<hipStream_t>(stream), Y, x, expand_idx, seg_off, B, nullptr,
+                     static_cast<const uint4*>(W2T_planes), Sm, nullptr, E, alpha, up);
   GN_LAUNCH_CHECK();
   return 0;
 }
@@ -1443,12 +1564,28 @@ namespace {
 // gn_pack_weight_split_fmt(W2, 1024, 64, GN_SPLIT_F16X2); B = the g rows of the 16 edges): 24 v_mfma_f32_16x16x32_f16 per wave
 // instead of 64 f32 MFMAs of twice the length.  g is a COTANGENT: every edge's row gets one exact power-of-two scale (row
 // maximum -> [0.25, 0.5)) before the split, and the lane that ends up with four consecutive k of that edge multiplies it back.
-template <bool HP>
+// UP (gn_bil_up_bwd_f32): the adjoint of the up-projection pair as a phase 0 in front, so that g never exists in HBM:
+//   g[e] = (G[inv[e]] (.) a act'(z_ac[e])) W_ac + (G[e] (.) a act'(z_ca[e])) W_ca
+// as ONE K = 256 product against the packed cat(W_ac^T, W_ca^T) (64 x 256).  Wave (kq, nt) owns the column tile nt over the
+// K-quarter kq (quarters 0, 1: the swapped term, 2, 3: the direct one) under its own exact power-of-two scale per
+// (edge, quarter), multiplied back before the quarters meet in LDS; every wave then sums the four quarters of the g
+// fragments it needs in the fixed order ((q0 + q1) + q2) + q3 — a row's result depends on that row alone.
+struct bil_up_bwd_args {
+  const float* G;             // (E,128): the one tied gradient of the pair
+  const int32_t* inv;         // inverse of the swap permutation
+  const float *z_ac, *z_ca;   // (E,128) pre-activations (act != 0 only)
+  const uint4* Wp;            // cat(W_ac^T, W_ca^T) as two fp16 planes, [4 tiles][8 chunks][2 planes][64 lanes]
+  float alpha;
+  int act;
+};
+
+template <bool HP, bool UP = false>
 __global__ __launch_bounds__(1024) void bil_fused_bwd_mfma7_kernel(const float* __restrict__ g, const float* __restrict__ W2,
                                                       const uint4* __restrict__ W2p,
                                                       const float* __restrict__ Sm, const float* __restrict__ B,
                                                       float* __restrict__ gB, float* __restrict__ dSm, int64_t E,
-                                                      float alpha, int gb_acc) {
+                                                      float alpha, int gb_acc, const bil_up_bwd_args up) {
+  static_assert(HP || !UP, "the pair adjoint rides on the fp16-plane phase 1");
   constexpr int S = 7, C = 64, I = 16, TE = 16, LDP = 1024 + 4;
   extern __shared__ __attribute__((aligned(16))) float dPl[];   // [TE][LDP]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1462,14 +1599,89 @@ __global__ __launch_bounds__(1024) void bil_fused_bwd_mfma7_kernel(const float* 
     // B operand: g[e = l15][o = 32 c + 8 lg + i]
     float gv[2][8];
     float m = 0.f;
+    if constexpr (UP) {
+      // ---- phase 0: quarter kq of the K = 256 product for the column tile nt
+      float* red = dPl;   // [4 kq][4 nt][64 lanes][4]
+      {
+        const int kq = wave >> 2, nt = wave & 3;
+        const bool ac = kq < 2;                                   // (wave-uniform)
+        const int64_t grow = ac ? (int64_t)up.inv[er] : er;
+        const int koff = 64 * (kq & 1) + 8 * lg;                  // B operand: k = 64 kq + 32 c + 8 lg + i
+        const float* __restrict__ Gr = up.G + grow * 128 + koff;
+        float av[2][8];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const float* __restrict__ gr = g + er * 64 + 32 * c + 8 * lg;
-      const float4 u0 = *reinterpret_cast<const float4*>(gr), u1 = *reinterpret_cast<const float4*>(gr + 4);
-      gv[c][0] = u0.x; gv[c][1] = u0.y; gv[c][2] = u0.z; gv[c][3] = u0.w;
-      gv[c][4] = u1.x; gv[c][5] = u1.y; gv[c][6] = u1.z; gv[c][7] = u1.w;
+        for (int c = 0; c < 2; ++c) {
+          const float4 u0 = *reinterpret_cast<const float4*>(Gr + 32 * c), u1 = *reinterpret_cast<const float4*>(Gr + 32 * c + 4);
+          av[c][0] = u0.x * up.alpha; av[c][1] = u0.y * up.alpha; av[c][2] = u0.z * up.alpha; av[c][3] = u0.w * up.alpha;
+          av[c][4] = u1.x * up.alpha; av[c][5] = u1.y * up.alpha; av[c][6] = u1.z * up.alpha; av[c][7] = u1.w * up.alpha;
+        }
+        if (up.act) {
+          const float* __restrict__ zr = (ac ? up.z_ac : up.z_ca) + er * 128 + koff;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(gv[c][i]));
+          for (int c = 0; c < 2; ++c) {
+            const float4 z0 = *reinterpret_cast<const float4*>(zr + 32 * c), z1 = *reinterpret_cast<const float4*>(zr + 32 * c + 4);
+            av[c][0] *= gn_dssilu(z0.x); av[c][1] *= gn_dssilu(z0.y); av[c][2] *= gn_dssilu(z0.z); av[c][3] *= gn_dssilu(z0.w);
+            av[c][4] *= gn_dssilu(z1.x); av[c][5] *= gn_dssilu(z1.y); av[c][6] *= gn_dssilu(z1.z); av[c][7] *= gn_dssilu(z1.w);
+          }
+        }
+        float mq = 0.f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) mq = fmaxf(mq, fabsf(av[c][i]));
+        mq = fmaxf(mq, __shfl_xor(mq, 16, 64));
+        mq = fmaxf(mq, __shfl_xor(mq, 32, 64));
+        float sq, inv_sq;
+        bil_row_scale(mq, sq, inv_sq);
+        const uint4* __restrict__ wq = up.Wp + ((size_t)(nt * 8 + 2 * kq) * 2) * 64 + lane;     // [tile][chunk][plane][lane]
+        v4f_b qh = (v4f_b){0.f, 0.f, 0.f, 0.f}, qx = qh;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const h8_b ah = __builtin_bit_cast(h8_b, wq[(2 * c) * 64]);
+          const h8_b al = __builtin_bit_cast(h8_b, wq[(2 * c + 1) * 64]);
+          h8_b bh, bl;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const float v = av[c][i] * sq;
+            const _Float16 h = (_Float16)v;
+            bh[i] = h;
+            bl[i] = (_Float16)((v - (float)h) * 2048.f);
+          }
+          qh = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, qh, 0, 0, 0);
+          qx = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, qx, 0, 0, 0);
+          qx = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, qx, 0, 0, 0);
+        }
+        // D^T: row = g column 16 nt + 4 lg + r, col = edge l15
+        *reinterpret_cast<v4f_b*>(red + (wave * 64 + lane) * 4) = (qh + qx * (1.f / 2048.f)) * inv_sq;
+      }
+      __syncthreads();
+      // g[e = l15][o = 32 c + 8 lg + 4 h + r]: column tile 2 c + lg / 2, lane group 2 (lg & 1) + h of the tile's owner
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float* rp = red + (((2 * c + (lg >> 1)) * 64) + (2 * (lg & 1) + h) * 16 + l15) * 4;
+          v4f_b a = *reinterpret_cast<const v4f_b*>(rp);
+#pragma unroll
+          for (int q = 1; q < 4; ++q) a += *reinterpret_cast<const v4f_b*>(rp + q * 4 * 64 * 4);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gv[c][4 * h + r] = a[r];
+        }
+      __syncthreads();   // the quarters are read: phase 1 overwrites them with dP
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(gv[c][i]));
+    } else {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float* __restrict__ gr = g + er * 64 + 32 * c + 8 * lg;
+        const float4 u0 = *reinterpret_cast<const float4*>(gr), u1 = *reinterpret_cast<const float4*>(gr + 4);
+        gv[c][0] = u0.x; gv[c][1] = u0.y; gv[c][2] = u0.z; gv[c][3] = u0.w;
+        gv[c][4] = u1.x; gv[c][5] = u1.y; gv[c][6] = u1.z; gv[c][7] = u1.w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(gv[c][i]));
+      }
     }
     m = fmaxf(m, __shfl_xor(m, 16, 64));       // the four lanes (lg) that hold the row of edge l15
     m = fmaxf(m, __shfl_xor(m, 32, 64));
@@ -1601,10 +1813,37 @@ extern "C" int gn_bil_fused_bwd_f32(const float* g, const float* W2, const void*
   if (W2_planes)
     hipLaunchKernelGGL(bil_fused_bwd_mfma7_kernel<true>, dim3((unsigned)gn_cdiv(E, 16)), dim3(1024), lds,
                        static_cast<hipStream_t>(stream), g, W2, static_cast<const uint4*>(W2_planes), Sm, B, gB, dSm, E, alpha,
-                       (accumulate >> 1) & 1);
+                       (accumulate >> 1) & 1, bil_up_bwd_args{});
   else
     hipLaunchKernelGGL(bil_fused_bwd_mfma7_kernel<false>, dim3((unsigned)gn_cdiv(E, 16)), dim3(1024), lds,
-                       static_cast<hipStream_t>(stream), g, W2, nullptr, Sm, B, gB, dSm, E, alpha, (accumulate >> 1) & 1);
+                       static_cast<hipStream_t>(stream), g, W2, nullptr, Sm, B, gB, dSm, E, alpha, (accumulate >> 1) & 1,
+                       bil_up_bwd_args{});
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_bil_up_bwd_f32(const float* G, const int32_t* inv_swap, const float* z_ac, const float* z_ca,
+                                 const void* Wupt_planes, const void* W2_planes, const float* Sm, const float* B, float* gB,
+                                 float* dSm, int64_t E, int S, int C, int I, int O, int N_up, float alpha, float alpha_up, int act,
+                                 int accumulate, void* stream) {
+  if (E <= 0) return 0;
+  if (S != 7 || C != 64 || I != 16 || O != 64 || N_up != 128 || !W2_planes || !Wupt_planes || !G || !inv_swap)
+    return (int)hipErrorInvalidValue;
+  if (!aligned16(G) || !aligned16(Wupt_planes) || !aligned16(W2_planes) || !aligned16(Sm) || !aligned16(B))
+    return (int)hipErrorInvalidValue;
+  if (act && (!z_ac || !z_ca || !aligned16(z_ac) || !aligned16(z_ca))) return (int)hipErrorInvalidValue;
+  constexpr size_t lds = (size_t)16 * (1024 + 4) * sizeof(float);   // the four quarter tiles (16 KiB) sit where dP goes afterwards
+  static std::atomic<bool> configured{false};   // set-once flag of an idempotent attribute (two racing threads both set it)
+  if (!configured.load(std::memory_order_acquire)) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bil_fused_bwd_mfma7_kernel<true, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    configured.store(true, std::memory_order_release);
+  }
+  const bil_up_bwd_args up{G, inv_swap, z_ac, z_ca, static_cast<const uint4*>(Wupt_planes), alpha_up, act};
+  hipLaunchKernelGGL((bil_fused_bwd_mfma7_kernel<true, true>), dim3((unsigned)gn_cdiv(E, 16)), dim3(1024), lds,
+                     static_cast<hipStream_t>(stream), nullptr, nullptr, static_cast<const uint4*>(W2_planes), Sm, B, gB, dSm, E,
+                     alpha, (accumulate >> 1) & 1, up);
   GN_LAUNCH_CHECK();
   return 0;
 }

@@ -1538,14 +1538,30 @@ def bil_reduce_project(Y, x, B, sp, Sm_init=None, B2=None, Sm2=None, want_P=True
 USE_K3_F16 = os.environ.get("GEMNET_K3_F16", "1") == "1"
 
 
-def bil_fused_fwd(Y, x, B, W2T, sp, alpha=1.0, W2T_planes=None):
+def bil_fused_fwd(Y, x, B, W2T, sp, alpha=1.0, W2T_planes=None, up=None):
     """K1+K2+K3 in one launch -> (Sm (E,S,C), out (E,O)); W2T (O, I*C) = the bilinear weight, k-contiguous.
     W2T_planes: pack_weight_split(W2T, fmt=1) — K3 then runs on the fp16 matrix pipe with split operands.
-    Spherical basis only (S, C, I, O) = (7, 64, 16, 64); see `bil_fused_fwd_supported`."""
+    Spherical basis only (S, C, I, O) = (7, 64, 16, 64); see `bil_fused_fwd_supported`.
+    `up` = dict(planes=pack_weight_split(cat(W_ac, W_ca), fmt=1), act, alpha): the up-projection pair of the interaction
+    tail runs as one more phase of the launch (gn_bil_up_fwd_f32) -> (Sm, z_ac, z_ca, y_ac, y_ca), z_* None without
+    activation; `out` is not formed.  Needs W2T_planes."""
     require_device(Y, x, B, W2T)
     Y, x, B, W2T = _f32c(Y), _f32c(x), _f32c(B), _f32c(W2T)
     S, C, I, O = Y.shape[1], x.shape[1], B.shape[2], W2T.shape[0]
     Sm = torch.empty((sp.n_reduce, S, C), device=x.device, dtype=torch.float32)
+    if up is not None:
+        planes, act, N = up["planes"], bool(up["act"]), UP_PAIR_WIDTH
+        if not (USE_K3_F16 and W2T_planes is not None and getattr(W2T_planes, "_gn_fmt", None) == 1
+                and W2T_planes.numel() == 4 * 32 * 2 * 64 * 16):
+            raise RuntimeError("bil_fused_fwd(up=...): the up-projection phase needs the fp16 planes of the bilinear weight")
+        assert getattr(planes, "_gn_fmt", None) == 1 and planes.numel() == 16 * 2 * 2 * 64 * 16
+        E = sp.n_reduce
+        z_ac, z_ca = (torch.empty((E, N), device=x.device, dtype=torch.float32) for _ in range(2)) if act else (None, None)
+        y_ac, y_ca = (torch.empty((E, N), device=x.device, dtype=torch.float32) for _ in range(2))
+        check(_lib.load().gn_bil_up_fwd_f32(ptr(Y), ptr(x), ptr(sp.expand.idx32), ptr(sp.seg_off), ptr(B), ptr(W2T_planes),
+                                            ptr(planes), ptr(Sm), ptr(z_ac), ptr(z_ca), ptr(y_ac), ptr(y_ca), E, S, C, I, O, N,
+                                            float(alpha), float(up["alpha"]), int(act), stream()), "gn_bil_up_fwd_f32")
+        return Sm, z_ac, z_ca, y_ac, y_ca
     out = torch.empty((sp.n_reduce, O), device=x.device, dtype=torch.float32)
     if W2T_planes is not None:
         assert getattr(W2T_planes, "_gn_fmt", None) == 1 and W2T_planes.numel() == 4 * 32 * 2 * 64 * 16
@@ -1558,6 +1574,14 @@ def bil_fused_fwd(Y, x, B, W2T, sp, alpha=1.0, W2T_planes=None):
 
 def bil_fused_fwd_supported(S, C, I, O):
     return (S, C, I, O) == (7, 64, 16, 64)
+
+
+UP_PAIR_WIDTH = 128     # width of the two up projections the bilinear kernels can carry
+
+
+def bil_up_supported(S, C, I, O, N_up, K_up):
+    """Shapes for which the up-projection pair rides in the fused bilinear launches (`up=` of bil_fused_fwd / bil_fused_bwd)."""
+    return (S, C, I, O) == (7, 64, 16, 64) and (N_up, K_up) == (UP_PAIR_WIDTH, O)
 
 
 def is_angle_form(Y, S):
@@ -1712,19 +1736,37 @@ def bil_fused_bwd_supported(S, C, I, O):
     return (S, C, I, O) == (7, 64, 16, 64)
 
 
-def bil_fused_bwd(g, W2, Sm, B, alpha=1.0, gB_accum=None, W2_planes=None):
+def bil_fused_bwd(g, W2, Sm, B, alpha=1.0, gB_accum=None, W2_planes=None, up=None):
     """Adjoint of the bilinear tail in one launch -> (gB (E,S,I), dSm (E,S,C)); W2 (I*C, O) = the bilinear weight
     (gn_bil_fused_bwd_f32: dP = alpha g W2^T stays in LDS).  `gB_accum`: running gradient gB is added to (and returned).
-    W2_planes: pack_weight_split(W2, fmt=1) — the first product then runs on the fp16 matrix pipe with split operands."""
+    W2_planes: pack_weight_split(W2, fmt=1) — the first product then runs on the fp16 matrix pipe with split operands.
+    `up` = dict(planes=pack_weight_split(cat(W_ac^T, W_ca^T), fmt=1), inv=inverse swap (int32), z_ac, z_ca, act, alpha): `g`
+    is then the tied gradient G (E,128) of the up-projection pair and the pair's adjoint runs as phase 0 of the launch
+    (gn_bil_up_bwd_f32).  Needs W2_planes."""
     require_device(g, W2, Sm, B)
     g, W2, Sm, B = _f32c(g), _f32c(W2), _f32c(Sm), _f32c(B)
     E, S, C = Sm.shape
-    I, O = B.shape[2], g.shape[1]
+    I, O = B.shape[2], (g.shape[1] if up is None else W2.shape[1])
     assert tuple(W2.shape) == (I * C, O) and B.shape[:2] == (E, S) and g.shape[0] == E
     if gB_accum is not None:
         assert gB_accum.shape == (E, S, I) and gB_accum.is_contiguous() and gB_accum.dtype == torch.float32
     gB = gB_accum if gB_accum is not None else torch.empty((E, S, I), device=g.device, dtype=torch.float32)
     dSm = torch.empty((E, S, C), device=g.device, dtype=torch.float32)
+    if up is not None:
+        planes, act, N = up["planes"], bool(up["act"]), UP_PAIR_WIDTH
+        if not (USE_K3_F16 and W2_planes is not None and getattr(W2_planes, "_gn_fmt", None) == 1
+                and W2_planes.numel() == 64 * 2 * 2 * 64 * 16):
+            raise RuntimeError("bil_fused_bwd(up=...): the pair adjoint phase needs the fp16 planes of the bilinear weight")
+        assert getattr(planes, "_gn_fmt", None) == 1 and planes.numel() == 4 * 8 * 2 * 64 * 16
+        inv, z_ac, z_ca = up["inv"], up["z_ac"], up["z_ca"]
+        assert g.shape == (E, N) and inv.dtype == torch.int32 and inv.numel() == E and inv.is_contiguous()
+        if act:
+            assert all(z.shape == (E, N) and z.is_contiguous() and z.dtype == torch.float32 for z in (z_ac, z_ca))
+        check(_lib.load().gn_bil_up_bwd_f32(ptr(g), ptr(inv), ptr(z_ac) if act else None, ptr(z_ca) if act else None,
+                                            ptr(planes), ptr(W2_planes), ptr(Sm), ptr(B), ptr(gB), ptr(dSm), E, S, C, I, O, N,
+                                            float(alpha), float(up["alpha"]), int(act),
+                                            2 if gB_accum is not None else 0, stream()), "gn_bil_up_bwd_f32")
+        return gB, dSm
     if W2_planes is not None:
         assert getattr(W2_planes, "_gn_fmt", None) == 1 and W2_planes.numel() == 64 * 2 * 2 * 64 * 16
     check(_lib.load().gn_bil_fused_bwd_f32(ptr(g), ptr(W2), ptr(W2_planes) if USE_K3_F16 else None, ptr(Sm), ptr(B), ptr(gB),

@@ -438,6 +438,15 @@ class TripletInteraction(torch.nn.Module):
             x_ba = ops.dense_hadamard_down(m, rbf3, self.dense_ba.weight, self.mlp_rbf.weight,
                                            self.down_projection.weight, self.dense_ba.act,
                                            self.down_projection.act, self.scale_rbf.value())
+            if (pair and ops.constant_weights() and self._pair_ok() and plan.id_swap.inverse is not None
+                    and ops.bilinear_up_pair_supported(rbf_W1, sph, x_ba, self.mlp_cbf.weight, self.up_projection_ac.weight,
+                                                       self.up_projection_ca.weight)):
+                # the bilinear layer and both up projections in one launch (and one adjoint launch): its output never
+                # leaves the chip
+                y_ac, y_ca = ops.bilinear_up_pair(rbf_W1, sph, x_ba, self.mlp_cbf.weight, self.up_projection_ac.weight,
+                                                  self.up_projection_ca.weight, plan.trip, plan.id_swap,
+                                                  self.scale_cbf_sum.value(), self.up_projection_ca.act, INV_SQRT_2)
+                return ops.SwappedPair(y_ca, y_ac, plan.id_swap)
             x = self.mlp_cbf(rbf_W1, sph, x_ba, plan.trip, alpha=self.scale_cbf_sum.value())
             if pair and ops.constant_weights() and self._pair_ok() and plan.id_swap.inverse is not None:
                 # both up projections in one launch (and one adjoint launch); the swap gather and the sum move into

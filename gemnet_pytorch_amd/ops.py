@@ -875,64 +875,74 @@ class _FusedBilinear(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        rbf_W1, sph, x, W, Sm, P = ctx.saved_tensors
-        C, I, O = W.shape
-        sp, alpha = ctx.sp, ctx.alpha
-        need = ctx.needs_input_grad
-        g = g.contiguous()
-        sink = ctx.sink
-        # K3^T + the gB / dSm part in ONE launch when the Y gradient is deferred anyway (dP stays in LDS)
-        fused_tail = (need[1] and not ctx.ang and sink is not None and sink.consumers <= 4
-                      and tuple(Sm.shape[1:]) == (7, 64) and K.bil_fused_bwd_supported(Sm.shape[1], C, I, O)
-                      and not (need[3] and _PARAM_GRADS and P is not None))
-        dP = None if fused_tail else \
-            K.gemm(g, bilinear_weight(W, False), alpha=alpha).reshape(-1, I, C)   # g @ W2^T: W2 is (N=I*C, K=O)
-        accB = ctx.acc_B   # running gradient of the radial part of the basis (shared by the blocks)
-        prevB, lastB = accB.enter() if accB is not None else (None, True)
-        if need[1] and ctx.ang and (sink is None or sink.consumers > 4):
-            # angle form without a shared sink: this block's angle gradient alone
-            gB, dSm, _ = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, want_dY=False, gB_accum=prevB)
-            gsph = K.bil_dy_multi([dSm], [x], sp, ang=sph)
-            if sink is not None:
-                sink.arrive()
-        elif sink is not None and need[1] and tuple(Sm.shape[1:]) in ((49, 32), (7, 64)) and sink.consumers <= 4:
-            # gB and dSm now, the Y gradient of all consumers of this basis in ONE pass when the last one arrives
-            if fused_tail:
-                gB, dSm = K.bil_fused_bwd(g, bilinear_weight(W, False), Sm, rbf_W1, alpha, gB_accum=prevB,
-                                          W2_planes=bilinear_weight_planes(W, False))
-            else:
-                gB, dSm, _ = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, want_dY=False, gB_accum=prevB)
-            last = sink.arrive()
-            sink.pending.append((dSm, x))
-            gsph = None
-            if last:
-                ds, xs = [d for d, _ in sink.pending], [xx for _, xx in sink.pending]
-                gsph = _on_home_stream(sink, ds + xs + [sph], lambda: K.bil_dy_multi(ds, xs, sp, ang=sph if ctx.ang else None))
-                sink.pending = []
-        elif sink is not None and need[1]:
-            # the Y gradient is summed across the consumers of `sph` inside the kernel (see GradSink)
-            last = sink.arrive()
-            gB, dSm, sink.buf = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, dY_accum=sink.buf, gB_accum=prevB)
-            gsph = sink.buf if last else None
-            if last:
-                sink.buf = None
+        return (*_bilinear_backward(ctx, ctx.saved_tensors, g.contiguous(), ctx.needs_input_grad), None, None)
+
+
+def _bilinear_backward(ctx, saved, g, need, up=None):
+    """Backward of the fused bilinear layer -> (gB, gsph, gx, gW).  `up` (ops.bilinear_up_pair): the layer's output fed the
+    up-projection pair inside the same launch, so its cotangent g does not exist yet — up["G"] is the pair's tied gradient,
+    up["kw"] the `up=` operands of K.bil_fused_bwd (the pair's adjoint as phase 0 of the fused tail) and up["make_g"]()
+    forms g by the pair's own adjoint launch for the graphs the fused tail does not serve."""
+    rbf_W1, sph, x, W, Sm, P = saved
+    C, I, O = W.shape
+    sp, alpha = ctx.sp, ctx.alpha
+    sink = ctx.sink
+    # K3^T + the gB / dSm part in ONE launch when the Y gradient is deferred anyway (dP stays in LDS)
+    fused_tail = (need[1] and not ctx.ang and sink is not None and sink.consumers <= 4
+                  and tuple(Sm.shape[1:]) == (7, 64) and K.bil_fused_bwd_supported(Sm.shape[1], C, I, O)
+                  and not (need[3] and _PARAM_GRADS and P is not None))
+    if up is not None and not fused_tail:
+        g, up = up["make_g"](), None
+    dP = None if fused_tail else \
+        K.gemm(g, bilinear_weight(W, False), alpha=alpha).reshape(-1, I, C)   # g @ W2^T: W2 is (N=I*C, K=O)
+    accB = ctx.acc_B   # running gradient of the radial part of the basis (shared by the blocks)
+    prevB, lastB = accB.enter() if accB is not None else (None, True)
+    if need[1] and ctx.ang and (sink is None or sink.consumers > 4):
+        # angle form without a shared sink: this block's angle gradient alone
+        gB, dSm, _ = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, want_dY=False, gB_accum=prevB)
+        gsph = K.bil_dy_multi([dSm], [x], sp, ang=sph)
+        if sink is not None:
+            sink.arrive()
+    elif sink is not None and need[1] and tuple(Sm.shape[1:]) in ((49, 32), (7, 64)) and sink.consumers <= 4:
+        # gB and dSm now, the Y gradient of all consumers of this basis in ONE pass when the last one arrives
+        if fused_tail:
+            # (`up` is only named when it is used: the host emulations of the launcher know the plain form alone)
+            kw = {} if up is None else dict(up=up["kw"])
+            gB, dSm = K.bil_fused_bwd(g if up is None else up["G"], bilinear_weight(W, False), Sm, rbf_W1, alpha,
+                                      gB_accum=prevB, W2_planes=bilinear_weight_planes(W, False), **kw)
         else:
-            gB, dSm, gsph = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, gB_accum=prevB)      # 2 bmm + bil_dot in one launch
-        if accB is not None:
-            accB.leave(gB, lastB)
-            if not lastB:
-                gB = None
-        gx = gW = None
-        if not need[0]:
+            gB, dSm, _ = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, want_dY=False, gB_accum=prevB)
+        last = sink.arrive()
+        sink.pending.append((dSm, x))
+        gsph = None
+        if last:
+            ds, xs = [d for d, _ in sink.pending], [xx for _, xx in sink.pending]
+            gsph = _on_home_stream(sink, ds + xs + [sph], lambda: K.bil_dy_multi(ds, xs, sp, ang=sph if ctx.ang else None))
+            sink.pending = []
+    elif sink is not None and need[1]:
+        # the Y gradient is summed across the consumers of `sph` inside the kernel (see GradSink)
+        last = sink.arrive()
+        gB, dSm, sink.buf = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, dY_accum=sink.buf, gB_accum=prevB)
+        gsph = sink.buf if last else None
+        if last:
+            sink.buf = None
+    else:
+        gB, dSm, gsph = K.bil_project_bwd(dP, Sm, rbf_W1, x, sp, gB_accum=prevB)      # 2 bmm + bil_dot in one launch
+    if accB is not None:
+        accB.leave(gB, lastB)
+        if not lastB:
             gB = None
-        if not need[1]:
-            gsph = None
-        if need[2]:
-            gx = K.bil_reduce_t(sph, dSm, sp)
-        if need[3] and _PARAM_GRADS and P is not None:
-            gW2 = K.gemm(P.reshape(-1, I * C), g, True, True, alpha=alpha)   # P^T @ g  (I*C, O)
-            gW = gW2.reshape(I, C, O).permute(1, 0, 2)
-        return gB, gsph, gx, gW, None, None
+    gx = gW = None
+    if not need[0]:
+        gB = None
+    if not need[1]:
+        gsph = None
+    if need[2]:
+        gx = K.bil_reduce_t(sph, dSm, sp)
+    if need[3] and _PARAM_GRADS and P is not None:
+        gW2 = K.gemm(P.reshape(-1, I * C), g, True, True, alpha=alpha)   # P^T @ g  (I*C, O)
+        gW = gW2.reshape(I, C, O).permute(1, 0, 2)
+    return gB, gsph, gx, gW
 
 
 def bilinear_weight(W, transposed_form):
@@ -1762,17 +1772,23 @@ class _UpPair(torch.autograd.Function):
             gx, prev, last = acc.target((M, ctx.width), G)
         else:
             gx, prev, last = torch.empty((M, ctx.width), device=G.device, dtype=G.dtype), None, True
-        inv = ctx.swap.inverse if ctx.swap.inverse is not None else None
-        assert inv is not None, "id_swap is a permutation"
-        prog = K.ChainProgram(M)
-        mode = 0 if ctx.act else 1
-        # slot 1 <- raw rows, slot 0 <- rows * alpha * act'(z): the second tensor of the load
-        prog.load(1, G, rows=inv.idx32, y2=0, alpha2=ctx.alpha, Z2=z_ac, mode2=mode)
-        _gemm(prog, W_ac, trans=True, a_slot=0, y_slot=2)                        # parked in registers
-        prog.load(1, G, y2=0, alpha2=ctx.alpha, Z2=z_ca, mode2=mode)
-        _gemm(prog, W_ca, trans=True, a_slot=0, y_slot=-1, res=2, beta=1.0, res2=prev, beta2=1.0, out=gx)
-        K.chain(prog)
+        _up_pair_adjoint(G, z_ac, z_ca, W_ac, W_ca, ctx.swap, ctx.act, ctx.alpha, prev, gx)
         return (gx if last else None), None, None, None, None, None
+
+
+def _up_pair_adjoint(G, z_ac, z_ca, W_ac, W_ca, swap, act, alpha, prev, gx):
+    """gx = (G[swap^-1] (.) alpha act'(z_ac)) W_ac + (G (.) alpha act'(z_ca)) W_ca (+ prev): one chain launch."""
+    inv = swap.inverse
+    assert inv is not None, "id_swap is a permutation"
+    prog = K.ChainProgram(G.shape[0])
+    mode = 0 if act else 1
+    # slot 1 <- raw rows, slot 0 <- rows * alpha * act'(z): the second tensor of the load
+    prog.load(1, G, rows=inv.idx32, y2=0, alpha2=alpha, Z2=z_ac, mode2=mode)
+    _gemm(prog, W_ac, trans=True, a_slot=0, y_slot=2)                        # parked in registers
+    prog.load(1, G, y2=0, alpha2=alpha, Z2=z_ca, mode2=mode)
+    _gemm(prog, W_ca, trans=True, a_slot=0, y_slot=-1, res=2, beta=1.0, res2=prev, beta2=1.0, out=gx)
+    K.chain(prog)
+    return gx
 
 
 class SwappedPair:
@@ -1786,6 +1802,85 @@ class SwappedPair:
 def up_project_pair(x, W_ac, W_ca, swap, act, alpha):
     assert constant_weights(), "the fused up-projection pair is the constant-weight inference path"
     return _UpPair.apply(x, W_ac, W_ca, swap, bool(act), float(alpha))
+
+
+# The up-projection pair as one more phase of the fused bilinear launches: the bilinear output x and
+# its gradient never reach HBM and two chain launches per interaction block go.  GEMNET_BIL_UP=0: the two-launch form.
+USE_BIL_UP = os.environ.get("GEMNET_BIL_UP", "1") == "1"
+BIL_UP_CALLS = 0          # forwards that took the joined path (tests assert eligibility through it)
+
+
+def up_pair_planes(W_ac, W_ca, transposed_form):
+    """cat(W_ac, W_ca) (256 x 64) — or cat(W_ac^T, W_ca^T) (64 x 256) — of two FROZEN 64 -> 128 up projections as two fp16
+    planes in MFMA fragment order, cached on both parameters' versions like `bilinear_weight_planes`."""
+    def make():
+        Wc = torch.cat([W_ac.detach(), W_ca.detach()], 0)
+        return K.pack_weight_split(Wc.t().contiguous() if transposed_form else Wc.contiguous(), fmt=1)
+    if not (_frozen(W_ac) and _frozen(W_ca)):
+        return make()
+    return _cached(("upTp" if transposed_form else "upp", W_ac.data_ptr(), W_ca.data_ptr(), tuple(W_ac.shape)),
+                   (W_ac._version, W_ca._version), make)
+
+
+def bilinear_up_pair_supported(rbf_W1, sph, x, W, W_ac, W_ca):
+    """May `bilinear_up_pair` replace ops.bilinear + ops.up_project_pair?  Device tensors, frozen weights, the fp16-plane
+    arithmetic in the tall chain layout (the K3 planes and their overflow guard), the one shape the kernels are built for."""
+    C, I, O = W.shape
+    return (USE_BIL_UP and _FUSED and constant_weights() and all(t.is_cuda for t in (rbf_W1, sph, x, W, W_ac, W_ca))
+            and K.current_mode() == "h3" and K.CHAIN_LAYOUT == "tall" and K.USE_K3_F16
+            and _frozen(W) and _frozen(W_ac) and _frozen(W_ca)
+            and not K.is_angle_form(sph, rbf_W1.shape[1]) and x.shape[1] == C
+            and tuple(W_ac.shape) == tuple(W_ca.shape)
+            and K.bil_up_supported(sph.shape[1], C, I, O, W_ac.shape[0], W_ac.shape[1]))
+
+
+class _BilinearUpPair(torch.autograd.Function):
+    """_FusedBilinear and _UpPair joined: (y_ac, y_ca) = alpha_up act(x W_*^T) of x = alpha K3(K2(rbf_W1, K1(sph, x_in))) in
+    ONE launch, and in the backward the pair's adjoint as phase 0 of the fused bilinear tail; x and dL/dx stay on the chip.
+    The deferred Y gradient and the running gradient of rbf_W1 behave as in _FusedBilinear.backward (shared code)."""
+
+    @staticmethod
+    def forward(ctx, rbf_W1, sph, x, W, W_ac, W_ca, sp, swap, alpha, act, alpha_up):
+        global BIL_UP_CALLS
+        BIL_UP_CALLS += 1
+        ctx.sink = getattr(sph, "_gn_sink", None)
+        if ctx.sink is not None:
+            ctx.sink.consumers += 1
+        ctx.acc_B = _acc_join(rbf_W1)
+        ctx.ang = False
+        Sm, z_ac, z_ca, y_ac, y_ca = K.bil_fused_fwd(
+            sph, x, rbf_W1, bilinear_weight(W, True), sp, alpha, W2T_planes=bilinear_weight_planes(W),
+            up=dict(planes=up_pair_planes(W_ac, W_ca, False), act=act, alpha=alpha_up))
+        ctx.set_materialize_grads(False)
+        ctx.mode = K.current_mode()
+        ctx.save_for_backward(rbf_W1, sph, x, W, Sm, z_ac, z_ca, W_ac, W_ca)
+        ctx.sp, ctx.alpha, ctx.swap, ctx.act, ctx.alpha_up = sp, alpha, swap, act, alpha_up
+        return y_ac, y_ca
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @_in_mode
+    def backward(ctx, g_ac, g_ca):
+        if g_ac is not None:
+            raise RuntimeError("bilinear_up_pair: y_ac may only be consumed together with y_ca as a tied residual pair")
+        rbf_W1, sph, x, W, Sm, z_ac, z_ca, W_ac, W_ca = ctx.saved_tensors
+        E, N = Sm.shape[0], W_ac.shape[0]
+        G = g_ca.contiguous() if g_ca is not None else torch.zeros((E, N), device=Sm.device, dtype=Sm.dtype)
+        inv = ctx.swap.inverse
+        assert inv is not None, "id_swap is a permutation"
+        up = dict(G=G, kw=dict(planes=up_pair_planes(W_ac, W_ca, True), inv=inv.idx32, z_ac=z_ac, z_ca=z_ca, act=ctx.act,
+                               alpha=ctx.alpha_up),
+                  make_g=lambda: _up_pair_adjoint(G, z_ac, z_ca, W_ac, W_ca, ctx.swap, ctx.act, ctx.alpha_up, None,
+                                                  torch.empty((E, W_ac.shape[1]), device=G.device, dtype=G.dtype)))
+        gB, gsph, gx, _ = _bilinear_backward(ctx, (rbf_W1, sph, x, W, Sm, None), None, ctx.needs_input_grad, up=up)
+        return gB, gsph, gx, None, None, None, None, None, None, None, None
+
+
+def bilinear_up_pair(rbf_W1, sph, x, W, W_ac, W_ca, sp, swap, alpha, act, alpha_up):
+    """ops.bilinear followed by ops.up_project_pair in one launch each way -> (y_ac, y_ca) for ops.SwappedPair; see
+    `bilinear_up_pair_supported`."""
+    assert bilinear_up_pair_supported(rbf_W1, sph, x, W, W_ac, W_ca)
+    return _BilinearUpPair.apply(rbf_W1, sph, x, W, W_ac, W_ca, sp, swap, float(alpha), bool(act), float(alpha_up))
 
 
 def dense_hadamard_down(x, rbf, Wa, Wr, Wd, act_a, act_d, alpha):

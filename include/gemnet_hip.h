@@ -509,6 +509,17 @@ int gn_bil_reduce_project2_f32(const float* Y, const float* x, const int32_t* ex
 int gn_bil_fused_fwd_f32(const float* Y, const float* x, const int32_t* expand_idx, const int32_t* seg_off,
                          const float* B, const float* W2T, const void* W2T_planes, float* Sm, float* out, int64_t E, int S,
                          int C, int I, int O, float alpha, void* stream);
+/* gn_bil_fused_fwd_f32 with the up-projection pair of the interaction tail (interaction_block.py:696-705) as one more phase
+ * of the same launch: with x[e] = alpha * K3(K2(K1)) (never written),
+ *   z_ac = x W_ac^T, z_ca = x W_ca^T (E,128);   y_* = alpha_up * ScaledSiLU(z_*)   (act == 0: y_* = alpha_up * z_*, z_* unused)
+ * Wup_planes = cat(W_ac, W_ca) (256 x 64) as gn_pack_weight_split_fmt(W, 256, 64, 64, 0, GN_SPLIT_F16X2, ...); W2T_planes as
+ * above and required.  The rows of x are split under an exact power-of-two scale each: no range limit beyond K3's own.  Sm is
+ * bit-identical to gn_bil_fused_fwd_f32's; a row's result does not depend on its position.
+ * (S, C, I, O, N_up) = (7, 64, 16, 64, 128) only (else hipErrorInvalidValue). */
+int gn_bil_up_fwd_f32(const float* Y, const float* x, const int32_t* expand_idx, const int32_t* seg_off, const float* B,
+                      const void* W2T_planes, const void* Wup_planes, float* Sm, float* z_ac, float* z_ca, float* y_ac,
+                      float* y_ca, int64_t E, int S, int C, int I, int O, int N_up, float alpha, float alpha_up, int act,
+                      void* stream);
 /* Fused adjoint: gB[e,s,i] = sum_c Sm[e,s,c] dP[e,i,c]; dSm[e,s,c] = sum_i B[e,s,i] dP[e,i,c];
  * dY[t,s] = sum_c dSm[r(t),s,c] x[g(t),c].  x rows 16-byte aligned, C % 4 == 0. */
 int gn_bil_project_bwd_f32(const float* dP, const float* Sm, const float* B, const float* x,
@@ -531,6 +542,15 @@ int gn_bil_project_bwd_acc_f32(const float* dP, const float* Sm, const float* B,
  * to fp32 rounding. */
 int gn_bil_fused_bwd_f32(const float* g, const float* W2, const void* W2_planes, const float* Sm, const float* B, float* gB,
                          float* dSm, int64_t E, int S, int C, int I, int O, float alpha, int accumulate, void* stream);
+/* gn_bil_fused_bwd_f32 with the adjoint of the up-projection pair in front (g never leaves the chip): G (E,128) is the one
+ * gradient of y_ca + y_ac[swap], inv_swap the inverse permutation,
+ *   g[e] = (G[inv_swap[e]] (.) alpha_up act'(z_ac[e])) W_ac + (G[e] (.) alpha_up act'(z_ca[e])) W_ca        (act == 0: act' = 1)
+ * then gB / dSm as above.  Wupt_planes = cat(W_ac^T, W_ca^T) (64 x 256) as gn_pack_weight_split_fmt(W, 64, 256, 256, 0,
+ * GN_SPLIT_F16X2, ...); W2_planes as above and required.  Every (edge, K-quarter) of the cotangent is split under its own exact
+ * power-of-two scale: any magnitude.  Same shapes as gn_bil_up_fwd_f32. */
+int gn_bil_up_bwd_f32(const float* G, const int32_t* inv_swap, const float* z_ac, const float* z_ca, const void* Wupt_planes,
+                      const void* W2_planes, const float* Sm, const float* B, float* gB, float* dSm, int64_t E, int S, int C, int I,
+                      int O, int N_up, float alpha, float alpha_up, int act, int accumulate, void* stream);
 /* gn_bil_project_bwd*_f32 accept dY == NULL (gB and dSm only).  The deferred Y gradient of up to 4 blocks that
  * share one basis tensor (S = 49, C = 32 or S = 7, C = 64; else hipErrorInvalidValue) is then produced in one pass:
  *   dY[t,s] = sum_b sum_c x_b[g(t),c] dSm_b[r(t),s,c]        (dSm_list / x_list: host arrays of nb device pointers) */

@@ -1,0 +1,346 @@
+"""-m gpu: the up-projection pair inside the fused triplet bilinear launches (gn_bil_up_fwd_f32 /
+gn_bil_up_bwd_f32, ops.bilinear_up_pair).
+
+Kernel level, E in {1, 15, 16, 17, 50} with triplet segments of length 0, 1, 8, 9 and 33 (an empty segment, one K1 step, the
+second trip of the K1 loop, the longest look-ahead) and a swap permutation with one pair inside a 16-edge tile and one across
+two tiles:
+  * Sm is bit-identical to gn_bil_fused_fwd_f32's;
+  * z against a float64 product of the same fp32 row x (= the `out` of gn_bil_fused_fwd_f32, which the new launch forms with
+    the same code and keeps on the chip):  |z - z64| <= 2^-19 sum_k |x_k| |W_k|.  Each split operand carries 2^-22 relative
+    error, the dropped lo.lo term is 2^-22, fp32 accumulation runs over K = 64; 2^-19 is four times their sum;
+  * z no worse than twice the maximum error of the two-launch composition (gn_bil_fused_fwd_f32 -> chain pair program, "h3");
+  * y against float64 ScaledSiLU of the kernel's own z at the bar tests/test_gpu_kernels.py holds the chain kernel's
+    activation to (rtol = atol = 2e-5);
+  * the adjoint's gB and dSm against float64 by the same rule propagated through the linear tail: the K = 256 product g
+    carries 2^-19 sum_k |a_k| |W_k| plus what the fp32 ssilu' (v_exp / v_rcp sigmoid, two ulp of 1, times its sensitivity
+    (1 + |z|) / 0.6 and the rounding of the formula: 2^-20 (1 + |z|)) puts into a = G alpha act'(z); phase 1 (K = 64, split
+    operands) adds 2^-19 sum_o |g_o| |W2_o|, the fp32 MFMAs of phase 2 (n + 1) 2^-24 sum |terms| over their n = 64 resp. 16
+    terms; and no worse than twice the composition (chain pair adjoint -> gn_bil_fused_bwd_f32);
+  * with and without the running gB, with an edge whose cotangent is all zero, with rows of G scaled by 1e-20 and 1e+20;
+  * the first 17 edges of the 50-edge case, run as a problem of their own, give the same bits row by row.
+Model level (2 molecules x 8 atoms, one block at the published widths, weights from the oracle's seeded generator):
+GEMNET_BIL_UP on and off against the float64 oracle at the bar of tests/test_gpu_fullsize_golden.py, captured replay == eager
+bit for bit, the happens-before check of the captured step, and a "split6" model that keeps the two-launch form."""
+import numpy as np
+import pytest
+import torch
+
+import cpu_kernels as CK
+from conftest import SCALE_FILE
+from gemnet_pytorch_amd import hbcheck
+from gemnet_pytorch_amd import kernels as K
+from gemnet_pytorch_amd import ops
+from gemnet_pytorch_amd.graph import RowIndex, SegmentPlan
+from oracle import gemnet_oracle as GO
+from oracle import index_oracle as IO
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+S, C, I, O, N = 7, 64, 16, 64, 128
+ALPHA, ALPHA_UP = 0.6, 2 ** -0.5
+SEG = (0, 1, 8, 9, 33)
+CLOSED = 17          # the first 17 edges of a larger case form a problem of their own (triplets and swap stay inside)
+
+
+def f32(t):
+    return t.to(torch.float32).to(DEV)
+
+
+class Case:
+    """One problem of E edges; every launch it is compared with runs once, here."""
+
+    def __init__(self, E, parent=None):
+        self.E = E
+        if parent is None:
+            g = torch.Generator().manual_seed(100 + E)
+            lens = torch.tensor([SEG[(e + (E == 1)) % len(SEG)] for e in range(E)])       # (a lone edge gets one triplet)
+            red = torch.repeat_interleave(torch.arange(E), lens)
+            lo_hi = [(0, min(E, CLOSED)) if e < CLOSED else (0, E) for e in red.tolist()]
+            exp = torch.tensor([int(torch.randint(lo, hi, (1,), generator=g)) for lo, hi in lo_hi], dtype=torch.long)
+            swap = torch.arange(E)
+            if E >= CLOSED:
+                head = torch.randperm(CLOSED, generator=g)
+                # 2 <-> 5 inside the first tile, 15 <-> 16 across the tile boundary, the rest of the head a random cycle
+                rest = [int(v) for v in head if int(v) not in (2, 5, 15, 16)]
+                swap[2], swap[5], swap[15], swap[16] = 5, 2, 16, 15
+                for a, b in zip(rest, rest[1:] + rest[:1]):
+                    swap[a] = b
+                swap[CLOSED:] = CLOSED + torch.randperm(E - CLOSED, generator=g)
+            else:
+                swap = torch.randperm(E, generator=g)
+            rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)      # noqa: E731
+            self.Y, self.x, self.Bm = f32(rn(red.shape[0], S)), f32(rn(E, C)), f32(rn(E, S, I))
+            self.W2T = f32(rn(O, I * C) / 32)
+            self.W_ac, self.W_ca = f32(rn(N, O) / 8), f32(rn(N, O) / 8)
+            self.G = f32(rn(E, N))
+            self.base = f32(rn(E, S, I))
+        else:       # the closed head of `parent`
+            T = int(parent.seg_cpu[E])
+            red, exp, swap = parent.red[:T], parent.exp[:T], parent.swap[:E]
+            assert int(exp.max()) < E and int(swap.max()) < E
+            self.Y, self.x, self.Bm = parent.Y[:T].contiguous(), parent.x[:E].contiguous(), parent.Bm[:E].contiguous()
+            self.W2T, self.W_ac, self.W_ca = parent.W2T, parent.W_ac, parent.W_ca
+            self.G, self.base = parent.G[:E].contiguous(), parent.base[:E].contiguous()
+        self.red, self.exp, self.swap = red, exp, swap
+        self.seg_cpu = torch.cat([torch.zeros(1, dtype=torch.long), torch.bincount(red, minlength=E).cumsum(0)])
+        self.sp = SegmentPlan(red.to(DEV), exp.to(DEV), E, E)
+        inv = torch.empty_like(swap)
+        inv[swap] = torch.arange(E)
+        self.inv = inv
+        self.swap_ri = RowIndex(swap.to(DEV), E, inverse=RowIndex(inv.to(DEV), E))
+        self.W2 = self.W2T.t().contiguous()
+        self.planes_T, self.planes = K.pack_weight_split(self.W2T, fmt=1), K.pack_weight_split(self.W2, fmt=1)
+        self.up_f = K.pack_weight_split(torch.cat([self.W_ac, self.W_ca], 0).contiguous(), fmt=1)
+        self.up_b = K.pack_weight_split(torch.cat([self.W_ac, self.W_ca], 0).t().contiguous(), fmt=1)
+        # ---- forward: the two-launch composition and the new launch
+        self.Sm0, self.out0 = K.bil_fused_fwd(self.Y, self.x, self.Bm, self.W2T, self.sp, ALPHA, W2T_planes=self.planes_T)
+        self.z0 = [torch.empty(E, N, device=DEV) for _ in range(2)]
+        self.y0 = [torch.empty(E, N, device=DEV) for _ in range(2)]
+        prog = K.ChainProgram(E)
+        prog.load(0, self.out0)
+        for W, z, y in zip((self.W_ac, self.W_ca), self.z0, self.y0):
+            prog.gemm(W, a_slot=0, y_slot=-1, act=True, alpha=ALPHA_UP, pre_out=z, out=y)
+        K.chain(prog, mode="h3")
+        self.Sm, *zy = K.bil_fused_fwd(self.Y, self.x, self.Bm, self.W2T, self.sp, ALPHA, W2T_planes=self.planes_T,
+                                       up=dict(planes=self.up_f, act=True, alpha=ALPHA_UP))
+        self.z, self.y = zy[:2], zy[2:]
+
+    def up_kw(self):
+        return dict(planes=self.up_b, inv=self.swap_ri.inverse.idx32, z_ac=self.z[0], z_ca=self.z[1], act=True, alpha=ALPHA_UP)
+
+    def adjoint(self, G, gB_accum=None):
+        return K.bil_fused_bwd(G, self.W2, self.Sm, self.Bm, ALPHA, gB_accum=gB_accum, W2_planes=self.planes, up=self.up_kw())
+
+    def adjoint_two_launches(self, G):
+        g = torch.empty(self.E, O, device=DEV)
+        prog = K.ChainProgram(self.E)
+        prog.load(1, G, rows=self.swap_ri.inverse.idx32, y2=0, alpha2=ALPHA_UP, Z2=self.z[0], mode2=0)
+        prog.gemm(self.W_ac.t().contiguous(), a_slot=0, y_slot=2)
+        prog.load(1, G, y2=0, alpha2=ALPHA_UP, Z2=self.z[1], mode2=0)
+        prog.gemm(self.W_ca.t().contiguous(), a_slot=0, y_slot=-1, res=2, beta=1.0, out=g)
+        K.chain(prog, mode="h3")
+        return K.bil_fused_bwd(g, self.W2, self.Sm, self.Bm, ALPHA, W2_planes=self.planes)
+
+    def adjoint_float64(self, G):
+        """-> (gB, dSm, bound_gB, bound_dSm) in float64 from the fp32 operands (module docstring)."""
+        d = lambda t: t.double().cpu()      # noqa: E731
+        G, inv = d(G), self.inv
+        a = []
+        da = []
+        for z, rows in ((d(self.z[0]), G[inv]), (d(self.z[1]), G)):
+            sg = torch.sigmoid(z)
+            a.append(rows * ALPHA_UP * (sg * (1 + z * (1 - sg)) / 0.6))
+            da.append(rows.abs() * ALPHA_UP * 2.0 ** -20 * (1 + z.abs()))
+        a, da = torch.cat(a, 1), torch.cat(da, 1)                      # (E, 256)
+        Wt = torch.cat([d(self.W_ac), d(self.W_ca)], 0)                # (256, 64): g = a @ Wt
+        W2, Sm, Bm = d(self.W2), d(self.Sm), d(self.Bm)
+        g = a @ Wt
+        g_err = 2.0 ** -19 * (a.abs() @ Wt.abs()) + da @ Wt.abs()
+        gB, dSm = CK.bil_fused_bwd(g, W2, Sm, Bm, ALPHA)
+        dP = (ALPHA * g @ W2.t()).reshape(-1, I, C)
+        dP_err = (ALPHA * (g_err + 2.0 ** -19 * g.abs()) @ W2.abs().t()).reshape(-1, I, C)
+        b_gB = torch.einsum("esc,eic->esi", Sm.abs(), dP_err + 65 * 2.0 ** -24 * dP.abs())
+        b_dSm = torch.einsum("esi,eic->esc", Bm.abs(), dP_err + 17 * 2.0 ** -24 * dP.abs())
+        return gB, dSm, b_gB, b_dSm
+
+
+_CASES = {}
+
+
+def case(E):
+    if E not in _CASES:
+        _CASES[E] = Case(E)
+    return _CASES[E]
+
+
+def head_of_50():
+    if "head" not in _CASES:
+        _CASES["head"] = Case(CLOSED, parent=case(50))
+    return _CASES["head"]
+
+
+def test_the_cases_hold_what_they_are_for():
+    c = case(50)
+    lens = torch.bincount(c.red, minlength=50)
+    assert set(SEG) <= set(lens.tolist()) and int(lens[:CLOSED].max()) == 33
+    assert sorted(c.swap.tolist()) == list(range(50)) and sorted(c.swap[:CLOSED].tolist()) == list(range(CLOSED))
+    assert int(c.swap[2]) == 5 and int(c.swap[15]) == 16          # inside a tile / across two tiles
+    assert int(c.exp[: int(c.seg_cpu[CLOSED])].max()) < CLOSED
+
+
+@pytest.mark.parametrize("E", [1, 15, 16, 17, 50])
+def test_forward(E):
+    c = case(E)
+    assert torch.equal(c.Sm, c.Sm0)
+    x = c.out0.double().cpu()
+    worst = []
+    for name, W, z, z0, y in zip(("ac", "ca"), (c.W_ac, c.W_ca), c.z, c.z0, c.y):
+        W = W.double().cpu()
+        z64, mag = x @ W.t(), x.abs() @ W.abs().t()
+        err, err0 = (z.double().cpu() - z64).abs(), (z0.double().cpu() - z64).abs()
+        print(f"E={E} z_{name}: max err {float(err.max()):.3e} (two launches {float(err0.max()):.3e}), "
+              f"max err / (2^-19 sum|x||W|) {float((err / (2.0 ** -19 * mag).clamp_min(1e-300)).max()):.3f}")
+        assert (err <= 2.0 ** -19 * mag).all()
+        worst.append((float(err.max()), float(err0.max())))
+        zk = z.double().cpu()
+        ref = ALPHA_UP * zk * torch.sigmoid(zk) / 0.6
+        assert ((y.double().cpu() - ref).abs() <= 2e-5 + 2e-5 * ref.abs()).all()
+    assert all(e <= 2 * e0 for e, e0 in worst), worst
+
+
+def _check_adjoint(c, G, gB, dSm, tag):
+    rgB, rdSm, b_gB, b_dSm = c.adjoint_float64(G)
+    out = []
+    for name, got, ref, bound in (("gB", gB, rgB, b_gB), ("dSm", dSm, rdSm, b_dSm)):
+        assert torch.isfinite(got).all()
+        err = (got.double().cpu() - ref).abs()
+        print(f"E={c.E} {tag} {name}: max err {float(err.max()):.3e}, max err / bound "
+              f"{float((err / bound.clamp_min(1e-300)).max()):.3f}")
+        assert (err <= bound).all()
+        out.append(err)
+    return out, (rgB, rdSm)
+
+
+@pytest.mark.parametrize("E", [1, 15, 16, 17, 50])
+def test_adjoint(E):
+    c = case(E)
+    gB, dSm = c.adjoint(c.G)
+    (e_gB, e_dSm), (rgB, rdSm) = _check_adjoint(c, c.G, gB, dSm, "plain")
+    gB0, dSm0 = c.adjoint_two_launches(c.G)
+    for name, err, got0, ref in (("gB", e_gB, gB0, rgB), ("dSm", e_dSm, dSm0, rdSm)):
+        err0 = (got0.double().cpu() - ref).abs()
+        print(f"E={E} {name}: max err {float(err.max()):.3e}, two launches {float(err0.max()):.3e}")
+        assert float(err.max()) <= 2 * float(err0.max())
+    # the running gradient of the shared radial basis joins in the same launch
+    run = c.base.clone()
+    gB2, dSm2 = c.adjoint(c.G, gB_accum=run)
+    assert gB2 is run and torch.equal(run, c.base + gB) and torch.equal(dSm2, dSm)
+
+
+@pytest.mark.parametrize("E", [17, 50])
+def test_adjoint_zero_and_scaled_rows(E):
+    c = case(E)
+    e = 3
+    G = c.G.clone()
+    G[e] = 0.0
+    G[int(c.inv[e])] = 0.0            # both terms of edge 3's cotangent vanish
+    G[1] = 0.0                         # and an edge whose direct term vanishes next to a live swapped one
+    gB, dSm = c.adjoint(G)
+    _check_adjoint(c, G, gB, dSm, "zero rows")
+    assert float(gB[e].abs().max()) == 0.0 and float(dSm[e].abs().max()) == 0.0
+    scale = torch.ones(E, 1, device=DEV)
+    scale[0::3], scale[1::3] = 1e-20, 1e20
+    G = c.G * scale
+    gB, dSm = c.adjoint(G)
+    _check_adjoint(c, G, gB, dSm, "rows x 1e-20 / 1e+20")       # the bound is linear in G: row by row at each row's own size
+
+
+def test_rows_do_not_depend_on_their_position():
+    c, h = case(50), head_of_50()
+    n = CLOSED
+    assert torch.equal(h.Sm, c.Sm[:n])
+    for a, b in zip(h.z + h.y, c.z + c.y):
+        assert torch.equal(a, b[:n])
+    gB, dSm = c.adjoint(c.G)
+    gBh, dSmh = h.adjoint(h.G)
+    assert torch.equal(gBh, gB[:n]) and torch.equal(dSmh, dSm[:n])
+
+
+def test_other_shapes_are_refused():
+    c = case(16)
+    with pytest.raises(RuntimeError, match="fp16 planes"):
+        K.bil_fused_fwd(c.Y, c.x, c.Bm, c.W2T, c.sp, ALPHA, up=dict(planes=c.up_f, act=True, alpha=ALPHA_UP))
+    lib = K._lib.load()
+    p = K._lib.ptr
+    z = torch.empty(16, N, device=DEV)
+    code = lib.gn_bil_up_fwd_f32(p(c.Y), p(c.x), p(c.sp.expand.idx32), p(c.sp.seg_off), p(c.Bm), p(c.planes_T), p(c.up_f),
+                                 p(torch.empty_like(c.Sm)), p(z), p(z), p(z), p(z), 16, S, C, I, O, 64, ALPHA, ALPHA_UP, 1,
+                                 K._lib.stream())
+    assert code == 1            # hipErrorInvalidValue: an up width other than 128
+    code = lib.gn_bil_up_bwd_f32(p(c.G), p(c.swap_ri.inverse.idx32), p(z), p(z), p(c.up_b), None, p(c.Sm), p(c.Bm),
+                                 p(torch.empty(16, S, I, device=DEV)), p(torch.empty_like(c.Sm)), 16, S, C, I, O, N, ALPHA,
+                                 ALPHA_UP, 1, 0, K._lib.stream())
+    assert code == 1            # no pre-split planes of the bilinear weight
+
+
+# ------------------------------------------------------------------------------------------------------------------ model
+T_CFG = dict(num_spherical=7, num_radial=6, num_blocks=1, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
+             emb_size_quad=32, emb_size_rbf=16, emb_size_cbf=16, emb_size_sbf=32, emb_size_bil_trip=64, emb_size_bil_quad=32,
+             num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True)
+
+
+@pytest.fixture(scope="module")
+def t_case():
+    from gemnet_pytorch_amd.model.gemnet import GemNet
+    from gemnet_pytorch_amd.synthetic import make_molecule
+    sizes = [8, 8]
+    mols = [make_molecule(n, 200 + i) for i, n in enumerate(sizes)]
+    R, Z = np.concatenate([m["R"] for m in mols]), np.concatenate([m["Z"] for m in mols])
+    idx = IO.build_indices(R, np.array(sizes), 5.0, 10.0, True)
+    inputs = {k: torch.tensor(v) for k, v in idx.items()}
+    inputs.update(Z=torch.tensor(Z).long(), R=torch.tensor(R), N=torch.tensor(sizes))
+    params = GO.make_params(T_CFG, 1, GO.load_scale_factors(SCALE_FILE))
+    E_ref, F_ref = GO.forward(T_CFG, params, inputs)          # float64 oracle, once
+    model = GemNet(**T_CFG, scale_file=SCALE_FILE)
+    model.load_state_dict(GO.expand_to_reference_state_dict({k: v.float() for k, v in params.items()}))
+    model = model.to(DEV).eval()
+    return model, {k: v.to(DEV) for k, v in inputs.items()}, E_ref.detach().double(), F_ref.detach().double()
+
+
+def _run(model, inputs, on, monkeypatch):
+    monkeypatch.setattr(ops, "USE_BIL_UP", on)
+    n = ops.BIL_UP_CALLS
+    E, F = model(inputs)
+    torch.cuda.synchronize()
+    return E.detach(), F.detach(), ops.BIL_UP_CALLS - n
+
+
+@pytest.mark.parametrize("on", [True, False])
+def test_model_matches_the_float64_oracle_with_the_switch_on_and_off(t_case, on, monkeypatch):
+    model, inputs, E_ref, F_ref = t_case
+    E, F, n = _run(model, inputs, on, monkeypatch)
+    assert n == (1 if on else 0)
+    f_mae = float((F.double().cpu() - F_ref).abs().mean())
+    f_mean = float(F_ref.abs().mean())
+    e_err = float((E.double().cpu().reshape(E_ref.shape) - E_ref).abs().max())
+    print(f"GEMNET_BIL_UP={int(on)}: force MAE {f_mae:.3e} at mean |F_ref| {f_mean:.3e}, energy err {e_err:.3e} "
+          f"(max |E_ref| {float(E_ref.abs().max()):.3f})")
+    assert f_mae <= 1e-5 * f_mean                                  # the golden bar: 1e-5 eV/A at mean |F| = 1
+    assert e_err <= 2e-5 * max(1.0, float(E_ref.abs().max()))
+
+
+def test_captured_replay_equals_eager_bitwise_and_is_ordered(t_case, monkeypatch):
+    model, inputs, _, _ = t_case
+    monkeypatch.setattr(ops, "USE_BIL_UP", True)
+    model.requires_grad_(False)
+    try:
+        E0, F0 = (t.detach().clone() for t in model(inputs))
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            model(inputs)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        n = ops.BIL_UP_CALLS
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            with hbcheck.record() as rec:
+                Eg, Fg = model(inputs)
+        assert ops.BIL_UP_CALLS == n + 1
+        races, summary = rec.races(), rec.summary()
+        print(rec.format(races))
+        assert not races and summary["unresolved_pointers"] == 0 and summary["unrecorded_nodes"] == 0
+        for _ in range(10):
+            graph.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(Eg, E0) and torch.equal(Fg, F0)
+    finally:
+        model.requires_grad_(True)
+
+
+def test_split6_model_keeps_the_two_launches(t_case, monkeypatch):
+    model, inputs, _, _ = t_case
+    monkeypatch.setattr(model, "matmul_precision", "split6")
+    E1, F1, n1 = _run(model, inputs, True, monkeypatch)
+    E0, F0, n0 = _run(model, inputs, False, monkeypatch)
+    assert n1 == 0 and n0 == 0 and torch.equal(E1, E0) and torch.equal(F1, F0)

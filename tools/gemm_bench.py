@@ -24,6 +24,24 @@ def timeit(fn, iters=200):
     return s.elapsed_time(e) * 1e3 / (iters // 20 * 20)  # us
 
 
+def graph_best(fn, launches=200, replays=3):
+    """us per call: `launches` calls captured into one graph, the best of `replays` replays."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(launches):
+            fn()
+    g.replay(); torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(replays):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+        best = min(best, s.elapsed_time(e) * 1e3 / launches)
+    return best
+
+
 def main():
     CFGS = {0: "64x128 2x2 k32", 1: "32x128 1x4 k32", 6: "64x128 2x2 k64", 7: "32x128 1x4 k64", 8: "64x128 2x4 k32",
             9: "64x128 2x4 k64", 12: "128x128 4x2 k32", 13: "128x128 4x4 k32", 14: "32x128 8w 16x16 k32", 15: "32x128 8w 16x16 k64",

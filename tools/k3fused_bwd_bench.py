@@ -51,3 +51,48 @@ for name, u, v in zip(("gB", "dSm"), a, b):
     print(f"{name}: max err {float((u - v).abs().max()):.2e} (|ref| max {float(u.abs().max()):.2f})")
 print(f"product (K3-adjoint GEMM + project_bwd): {timeit(product):7.2f} us")
 print(f"fused   (one launch)                   : {timeit(fused):7.2f} us")
+
+
+# ---- the library's launches at the same shape: the pair adjoint program ("h3") followed by gn_bil_fused_bwd_f32 on the fp16
+# planes against the one launch that carries the pair adjoint as phase 0 (gn_bil_up_bwd_f32)
+from tools.gemm_bench import graph_best
+W_ac = torch.randn(128, 64, device="cuda", generator=gen) / 8
+W_ca = torch.randn(128, 64, device="cuda", generator=gen) / 8
+G = torch.randn(E, 128, device="cuda", generator=gen)
+z_ac = torch.randn(E, 128, device="cuda", generator=gen)
+z_ca = torch.randn(E, 128, device="cuda", generator=gen)
+inv = plan.id_swap.inverse.idx32
+planes = K.pack_weight_split(W2, fmt=1)
+up_planes = K.pack_weight_split(torch.cat([W_ac, W_ca], 0).t().contiguous(), fmt=1)
+Wt = [W_ac.t().contiguous(), W_ca.t().contiguous()]
+pk = [K.pack_weight_split(W, fmt=1) for W in Wt]
+gx = torch.empty(E, 64, device="cuda")
+a_up = 2 ** -0.5
+
+
+def bwd_only():
+    return K.bil_fused_bwd(gx, W2, Sm, Bm, alpha, W2_planes=planes)
+
+
+def two_launches():
+    prog = K.ChainProgram(E)
+    prog.load(1, G, rows=inv, y2=0, alpha2=a_up, Z2=z_ac, mode2=0)
+    prog.gemm(Wt[0], packed=pk[0], a_slot=0, y_slot=2)
+    prog.load(1, G, y2=0, alpha2=a_up, Z2=z_ca, mode2=0)
+    prog.gemm(Wt[1], packed=pk[1], a_slot=0, y_slot=-1, res=2, beta=1.0, out=gx)
+    K.chain(prog, mode="h3")
+    return bwd_only()
+
+
+def one_launch():
+    return K.bil_fused_bwd(G, W2, Sm, Bm, alpha, W2_planes=planes,
+                           up=dict(planes=up_planes, inv=inv, z_ac=z_ac, z_ca=z_ca, act=True, alpha=a_up))
+
+
+a, b = two_launches(), one_launch()
+torch.cuda.synchronize()
+for name, u, v in zip(("gB", "dSm"), a, b):
+    print(f"up pair adjoint {name}: max diff {float((u - v).abs().max()):.2e} (|ref| max {float(u.abs().max()):.2f})")
+print(f"bil_fused_bwd, fp16 planes (one launch)             : {graph_best(bwd_only):7.2f} us")
+print(f"pair adjoint program + bil_fused_bwd (two launches) : {graph_best(two_launches):7.2f} us")
+print(f"bil_fused_bwd carrying the pair adjoint (one launch): {graph_best(one_launch):7.2f} us")
