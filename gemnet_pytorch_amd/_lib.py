@@ -176,6 +176,8 @@ SIGNATURES = {
     "gn_angle_vec_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "gn_angle_vec_jvp_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "gn_pbc_force_stress_adj_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i64, _vp],
+    # the force head of the direct-force model (csrc/direct_force.hip)
+    "gn_direct_force_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp],
 }
 
 _lib = None

@@ -908,6 +908,30 @@ def pbc_force_stress_adj(gF, gS, V, id_c, id_a, batch_seg, cell, scale=-1.0):
     return gG
 
 
+def direct_force(terms, V, id_swap, perm, seg_off, n_atoms, out=None):
+    """-> F (n_atoms, T, 3): the force head of the direct-force model in one launch (gn_direct_force_f32).  terms (K,E,T): the
+    force magnitudes of the K output blocks; V (E,3): edge vectors, not normalised; id_swap (E) int32 or None (uncoupled);
+    perm (int32 or None) / seg_off (n_atoms + 1): the CSR of id_a.  `out`: written in place (every row is written)."""
+    require_device(terms, V, seg_off)
+    terms, V = _f32c(terms), _f32c(V)
+    if terms.dim() != 3 or V.shape != (terms.shape[1], 3):
+        raise ValueError(f"terms (K,E,T) and V (E,3) expected; got {tuple(terms.shape)} and {tuple(V.shape)}")
+    K, E, T = (int(s) for s in terms.shape)
+    for t in (id_swap, perm, seg_off):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise TypeError("id_swap, perm and seg_off must be contiguous int32")
+    if seg_off.shape[0] != int(n_atoms) + 1 or (id_swap is not None and id_swap.shape[0] != E) or \
+            (perm is not None and perm.shape[0] != E):
+        raise ValueError("index arrays do not fit (E, n_atoms)")
+    if out is None:
+        out = torch.empty((int(n_atoms), T, 3), device=terms.device, dtype=torch.float32)
+    elif out.shape != (int(n_atoms), T, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 (n_atoms, T, 3) tensor")
+    check(_lib.load().gn_direct_force_f32(ptr(terms), ptr(V), ptr(id_swap), ptr(perm), ptr(seg_off), ptr(out), int(n_atoms), E,
+                                          K, T, stream()), "gn_direct_force_f32")
+    return out
+
+
 class ChainProgram:
     """A program for gn_chain_f32: ops over the three LDS slots of a row tile (see include/gemnet_hip.h).
     Operands named `mul/res/res2` are either an int (LDS slot) or a tensor (global (M,N))."""

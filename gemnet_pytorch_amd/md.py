@@ -89,6 +89,8 @@ def predict_periodic(model, inputs, stress=False, to_host=False):
         raise RuntimeError("periodic structures run on a HIP device only (no CPU fallback); DeviceMolecule.to('cuda')")
     if not model.triplets_only:
         raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+    if stress and getattr(model, "direct_forces", False):
+        raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
     pbc = np.asarray(inputs["pbc"].cpu().numpy(), dtype=bool).reshape(-1, 3)
     lk = inputs.layout_key
     if lk is None:

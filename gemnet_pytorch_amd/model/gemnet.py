@@ -96,6 +96,9 @@ class GemNet(torch.nn.Module):
         # opt-in: a periodic batch (inputs["cell"]) with a second-order force graph returns (E, F[, S]) with an autograd graph
         # to the parameters (_forward_periodic_train; training.periodic.PeriodicTrainStep sets it).  False: such a call raises
         self.periodic_training = False
+        # opt-in: a direct-force model (`direct_forces=True`) serves periodic batches on the constant-weight inference path
+        # (_forward_periodic_direct: no autograd, forces (A,1,3), no stress).  False: such a call raises
+        self.periodic_direct_forces = False
         # arithmetic of the LDS-resident Dense stacks: None = the package default ("h3": fp32 operands as two fp16 planes,
         # three products), "split6" = three bf16 planes / six products (fp32 exponent range), "f32" = the f32-input MFMA — all
         # three at fp32 accuracy (force MAE 1e-6 .. 4e-6 eV/A against float64).  Single-plane bf16 / three-product modes exist
@@ -204,8 +207,9 @@ class GemNet(torch.nn.Module):
         return angle_cab, angle_abd, angle_cabd
 
     # ---------------------------------------------------------------------------------- forward
-    def _energy(self, R, plan, V=None):
-        """V: the (E,3) edge vectors of a periodic batch (pbc.edge_vectors; the leaf the force and stress are taken from)."""
+    def _energy(self, R, plan, V=None, force_terms=False):
+        """V: the (E,3) edge vectors of a periodic batch (pbc.edge_vectors; the leaf the force and stress are taken from).
+        `force_terms` (direct forces): return the output blocks' per-edge force terms as a list instead of their sum."""
         T = self.triplets_only
         b3 = self.cbf_basis3
         # Output blocks on a side stream (all model kinds, inference and force training; the round-3 restrictions are gone,
@@ -450,8 +454,14 @@ class GemNet(torch.nn.Module):
             E_a, F_ca = ops.output_group(group, group_ms + [m], rbf_out, plan.id_a, s=INV_SQRT_2), 0
         else:
             E_a, F_ca = outs[-1][0], outs[0][1]
-            for _, F in outs[1:]:
-                F_ca = F_ca + F
+            if force_terms:
+                F_ca = [F for _, F in outs]
+                if side is not None:
+                    for F in F_ca:       # produced on the side stream, consumed by the force head on this one
+                        F.record_stream(torch.cuda.current_stream())
+            else:
+                for _, F in outs[1:]:
+                    F_ca = F_ca + F
 
         E_mol = ops.segsum_rows(E_a, plan.batch_seg)                      # (nMolecules, num_targets)
         if not self.extensive:
@@ -495,6 +505,8 @@ class GemNet(torch.nn.Module):
         """E, F as the reference's `GemNet.forward` (gemnet.py:453-615).
         Periodic batches (`cell` (B,3,3) + `cell_offsets` (E,3), pbc.py; GemNet-T, eval-mode forces by autograd): the edge
         vectors carry the image shift; `stress=True` returns (E, F, S) with S (B,3,3) = dE/d(strain) / |det cell| (eV/A^3).
+        A direct-force model (`direct_forces=True`) serves periodic batches with `periodic_direct_forces = True` (opt-in, inference
+        only): (E, F) with F (A,1,3) as on molecules, no autograd, no stress (`stress=True` raises); without the switch it raises.
         With `periodic_training = True` a call that builds the second-order force graph (training mode with grad enabled, or
         `force_graph = True`) returns the same outputs with an autograd graph to the parameters; without it that call raises.
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
@@ -511,7 +523,7 @@ class GemNet(torch.nn.Module):
             raise ValueError("a periodic batch needs its neighbour list with 'cell_offsets' (pbc.PeriodicGraphBuilder)")
         inputs = self.with_indices(inputs)
         with ops.exclusive():
-            out = self._forward_guarded(inputs)
+            out = self._forward_guarded(inputs, stress)
         return out if (stress or not periodic) else out[:2]
 
     def with_indices(self, inputs):
@@ -530,8 +542,8 @@ class GemNet(torch.nn.Module):
             cutoff, int_cutoff = float(c[0]), float(c[1])
         return ensure_indices(inputs, cutoff, int_cutoff, self.triplets_only)
 
-    def _forward_guarded(self, inputs):
-        out = self._forward(inputs)
+    def _forward_guarded(self, inputs, stress=False):
+        out = self._forward(inputs, stress)
         R = inputs["R"]
         h3 = R.is_cuda and (self.matmul_precision or K_chain_mode()) == "h3"
         # (a padded batch — padded.py — names its real rows: the dummy molecule behind them is not the model's concern)
@@ -557,12 +569,12 @@ class GemNet(torch.nn.Module):
                 if flag is not None:
                     torch.cuda.current_stream().synchronize()
                     flag.reset()       # the eager pass reported it itself
-                out = self._forward(inputs)
+                out = self._forward(inputs, stress)
         return out
 
     PRECISIONS = (None, "h3", "split6", "f32")
 
-    def _forward(self, inputs):
+    def _forward(self, inputs, stress=False):
         R = inputs["R"]
         self._check_inputs(R)
         if self.matmul_precision not in self.PRECISIONS and not getattr(self, "_experimental_precision", False):
@@ -571,7 +583,7 @@ class GemNet(torch.nn.Module):
                              "BASELINE configs[4], docs/HISTORY.md section 14)")
         cell = inputs.get("cell")
         if cell is not None:
-            self._check_periodic(inputs)
+            self._check_periodic(inputs, stress)
         plan = GraphPlan.from_inputs(inputs, self.triplets_only)
         late = None
         pos_graph = False
@@ -616,6 +628,8 @@ class GemNet(torch.nn.Module):
         # (and widths the split-operand chain kernel takes in every sweep, see _train2_widths_ok: the CPU emulation takes any)
         t2 = (bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
               and (not R.is_cuda or self._train2_widths_ok()))
+        if cell is not None and self.direct_forces:
+            return self._forward_periodic_direct(R, plan, cell)      # (inference only: _check_periodic turned the rest away)
         if cell is not None:
             if graph and not getattr(self, "periodic_training", False):
                 raise NotImplementedError("periodic cells: forces by autograd on the first-order (eval) path only; training "
@@ -667,12 +681,18 @@ class GemNet(torch.nn.Module):
                        q.down_projection.weight.shape[0], q.up_projection_ca.weight.shape[1]]
         return all(int(w) % 16 == 0 for w in widths)
 
-    def _check_periodic(self, inputs):
+    def _check_periodic(self, inputs, stress=False):
         """What a cell is not supported with raises (no silent molecular result)."""
         if not self.triplets_only:
             raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
         if self.direct_forces:
-            raise NotImplementedError("periodic cells: forces by autograd only, not direct_forces")
+            if not getattr(self, "periodic_direct_forces", False):
+                raise NotImplementedError("periodic cells: forces by autograd only, not direct_forces")
+            if self.training:
+                raise NotImplementedError("periodic cells: direct-force periodic batches are inference only (model.eval())")
+            if stress:
+                raise NotImplementedError("periodic cells: a direct-force model has no stress (its forces are not the "
+                                          "gradient of its energy)")
         if self.num_targets != 1:
             raise NotImplementedError("periodic cells: one target only")
         if AutomaticFit.fitting_mode:
@@ -696,6 +716,20 @@ class GemNet(torch.nn.Module):
         F = pbc.forces(G, plan)
         S = pbc.stress(V.detach(), G, plan, cell)
         return E_mol.detach(), F, S
+
+    def _forward_periodic_direct(self, R, plan, cell):
+        """E, F (A,1,3) of a periodic batch from a direct-force model (`periodic_direct_forces`): nothing is differentiated, so
+        the pass runs without autograd and with constant weights (the LDS-resident Dense stacks, the fused aggregation), the
+        output blocks' force terms are stacked into one (K,E,1) array and the force head — sum over the blocks, the coupling of
+        the two directions of an edge through `plan.id_swap`, the unit vectors, the sum over the in-edges — is one launch
+        (pbc.direct_forces, csrc/direct_force.hip)."""
+        from .. import pbc
+        V = pbc.edge_vectors(R, plan, cell)
+        with torch.no_grad(), ops.weight_cache(self._wcache), ops.fused_first_order(True), ops.param_grads(False), \
+                ops.train2(False, None), ops.chain_mode(self.matmul_precision), ops.position_graph(False):
+            E_mol, terms, _ = self._energy(R.detach(), plan, V=V, force_terms=True)
+            F = pbc.direct_forces(torch.stack(terms), V, plan, self.forces_coupled)
+        return E_mol, F
 
     def _forward_periodic_train(self, R, plan, cell, t2):
         """E, F, S of a periodic batch with an autograd graph to the parameters (`periodic_training`): E under the context of

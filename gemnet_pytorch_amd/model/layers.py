@@ -244,8 +244,13 @@ class OutputBlock(AtomUpdateBlock):
                 x_F = x * (self.scale_rbf.value() / self.scale_sum.value())
             else:
                 x_F = self.scale_rbf(m, x)
-            for layer in self.seq_forces:
-                x_F = layer(x_F)
+            if ops.constant_weights() and self._stackable(self.seq_forces):
+                # (constant weights together with direct forces: the periodic direct-force path only — the molecular
+                #  direct-force model keeps trainable weights and the launches below)
+                x_F = self._mlp_stack(x_F, self.seq_forces)
+            else:
+                for layer in self.seq_forces:
+                    x_F = layer(x_F)
             x_F = self.out_forces(x_F)
         else:
             x_F = 0

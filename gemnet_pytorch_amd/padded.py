@@ -216,6 +216,8 @@ class PaddedGraphRunner:
         if self.quad and quad_caps is None:
             raise ValueError("quadruplet models need quad_caps = (eint_cap, i_cap, q_cap)")
         self.periodic = cell is not None
+        # (E, F, S) from a periodic autograd-force model; a direct-force one (GemNet.periodic_direct_forces) has no stress
+        self.with_stress = self.periodic and not getattr(model, "direct_forces", False)
         if self.periodic:
             if self.quad:
                 raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
@@ -444,6 +446,8 @@ class PaddedGraphRunner:
 
     def stress(self):
         """Stress (n_mol,3,3) of the last step of a periodic runner (the graph's static output buffer)."""
+        if self.periodic and not self.with_stress:
+            raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
         if not self.periodic or self.out is None:
             raise ValueError("stress needs a periodic runner that has run a step")
         return self.out[2].detach()[:self.n_mol]
@@ -611,7 +615,7 @@ class PaddedGraphRunner:
         if self.flag is not None:
             inputs["_range_flag"] = self.flag
         inputs.pop("_plan", None)
-        kw = dict(stress=True) if self.periodic else {}       # (E, F, S): the stress of the step stays readable (stress())
+        kw = dict(stress=True) if self.with_stress else {}    # (E, F, S): the stress of the step stays readable (stress())
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):          # warm-up off the default stream (autograd stream bookkeeping, lazy caches)

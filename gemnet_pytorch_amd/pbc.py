@@ -10,6 +10,9 @@ instead and takes forces and stress from `force_stress` below (csrc/pbc_train.hi
 Input keys of a periodic batch: `cell` (B,3,3), rows = lattice vectors; `cell_offsets` (E,3) integer: edge e = (c -> a) has
 V_e = R[a] - (R[c] + cell_offsets[e] @ cell[b(e)]).  The stress is dE/d(strain) / |det cell| (ASE's sign convention, eV/A^3).
 
+A direct-force model (`GemNet(direct_forces=True)` with `model.periodic_direct_forces = True`) runs the same geometry without
+autograd and ends in `direct_forces` below (csrc/direct_force.hip): E, F (A,1,3), no stress.
+
 The builder reads two sizes back per call.  For MD — a new list every step — the same list is built without a read-back inside a
 captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
 runtime.DynamicForceField(cell=...), md.predict_periodic.
@@ -197,6 +200,14 @@ def trip_basis(V, trip, S):
 def forces(G, plan):
     """F (A,3) from G = -dE/dV: F = segsum(G, id_a) - segsum(G, id_c)."""
     return K.segsum_multi([(G, *plan.id_a.csr, 1.0), (G, *plan.id_c.csr, -1.0)], plan.n_atoms)
+
+
+def direct_forces(terms, V, plan, coupled):
+    """F (A,T,3) of a direct-force model (gemnet.py:580-596) in one launch (gn_direct_force_f32): terms (K,E,T), the per-edge
+    force magnitudes of the K output blocks; V (E,3) = `edge_vectors`; `coupled`: average the two directions of every
+    undirected edge first (`plan.id_swap` pairs an edge with its negated-offset partner).  Inference only: no autograd."""
+    perm, seg = plan.id_a.csr
+    return K.direct_force(terms.detach(), V.detach(), plan.id_swap.idx32 if coupled else None, perm, seg, plan.n_atoms)
 
 
 def edge_structure(plan):

@@ -141,6 +141,8 @@ class ForceGraphs:
             if b.get("cell") is not None:     # periodic batch (pbc.py): fixed neighbour list, private cell buffer
                 b["cell"] = b["cell"].detach().float().clone()
         self.periodic = [b.get("cell") is not None for b in self.batches]
+        # a direct-force model (GemNet.periodic_direct_forces) has no stress: it is never asked for one
+        self.with_stress = [p and not getattr(model, "direct_forces", False) for p in self.periodic]
         dev = self.batches[0]["R"].device
         if dev.type != "cuda":
             raise RuntimeError("ForceGraphs needs a HIP device (no CPU fallback)")
@@ -155,17 +157,17 @@ class ForceGraphs:
         self.graphs, self.outputs = [], []
         model.eval()
         cur = torch.cuda.current_stream(dev)
-        for inputs, st in zip(self.batches, self.streams):
+        for inputs, st, stress in zip(self.batches, self.streams, self.with_stress):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 for _ in range(warmup):
-                    model(inputs, stress=inputs.get("cell") is not None)
+                    model(inputs, stress=stress)
             cur.wait_stream(st)
         torch.cuda.synchronize(dev)
-        for inputs, st in zip(self.batches, self.streams):
+        for inputs, st, stress in zip(self.batches, self.streams, self.with_stress):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=st):
-                out = model(dict(inputs, _range_flag=self.flag), stress=inputs.get("cell") is not None)
+                out = model(dict(inputs, _range_flag=self.flag), stress=stress)
             self.graphs.append(g)
             self.outputs.append(out)
         torch.cuda.synchronize(dev)
@@ -183,6 +185,8 @@ class ForceGraphs:
         """Concatenated stress (nStructures, 3, 3) of the last replay (periodic sub-batches only, sub-batch order)."""
         if not all(self.periodic):
             raise ValueError("stress needs every sub-batch to be periodic")
+        if not all(self.with_stress):
+            raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
         return torch.cat([o[2] for o in self.outputs])
 
     def replay(self):
@@ -364,6 +368,8 @@ class DynamicForceField:
 
     def stress(self):
         """Stress (B,3,3) of the last step of a periodic force field (valid until the next call)."""
+        if self.periodic and getattr(self.model, "direct_forces", False):
+            raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
         if not self.periodic or self.runner is None:
             raise ValueError("stress needs a periodic force field that has run a step")
         return self.runner.stress()

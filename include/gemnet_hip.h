@@ -801,6 +801,22 @@ int gn_angle_vec_jvp_f32(const float* V, const float* tV, const float* g, const 
 int gn_pbc_force_stress_adj_f32(const float* gF, const float* gS, const float* V, const int32_t* id_c, const int32_t* id_a,
                                 const int32_t* batch_seg, const float* cell, float scale, float* gG, int64_t E, void* stream);
 
+/* ---- the force head of the direct-force model (csrc/direct_force.hip; additive, ABI 15) ---------------------------------------
+ * gemnet.py:580-596 in one launch.  terms (K,E,T) contiguous: the per-edge force magnitudes of the K output blocks
+ * (1 <= K <= GN_DIRECT_FORCE_MAX_BLOCKS, 1 <= T <= GN_DIRECT_FORCE_MAX_TARGETS, else hipErrorInvalidValue); V (E,3): the edge
+ * vectors, NOT normalised (gn_pbc_edge_vec_f32); id_swap (E): the partner of every edge in the other direction, or NULL for
+ * uncoupled forces (an entry outside [0, E) makes the edge its own partner); perm / seg_off (n_atoms + 1): the CSR of id_a
+ * (gn_csr_build_i32; perm NULL = edges sorted by id_a).
+ *   c[e,t]   = sum_k terms[k,e,t];   with id_swap:  c[e,t] <- (c[e,t] + c[id_swap[e],t]) / 2
+ *   F[a,t,:] = sum_{e in seg(a)} c[e,t] V_e / |V_e|                                                 F (n_atoms,T,3)
+ * No atomics; every row of F is written exactly once (atoms without in-edges: exact zeros); no (E,T,3) temporary.  The order
+ * of addition of a row is a function of that atom's own segment (its length and CSR order) only: bit-reproducible, and
+ * unchanged when edges of other atoms are appended.  n_atoms = 0 returns 0 without a launch; n_edges = 0 writes zeros. */
+#define GN_DIRECT_FORCE_MAX_BLOCKS 8
+#define GN_DIRECT_FORCE_MAX_TARGETS 8
+int gn_direct_force_f32(const float* terms, const float* V, const int32_t* id_swap, const int32_t* perm, const int32_t* seg_off,
+                        float* F, int64_t n_atoms, int64_t n_edges, int K, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,11 @@ captured after the first.
 `--train` times the TRAINING step instead (training/periodic.PeriodicTrainStep: energy + force + stress loss, rho_stress > 0, fused
 optimizer) on the same box, eager (`train_eager_ms`) and replayed from its captured graph (`train_graph_ms`), next to the
 molecular `TrainStep` on the same atoms without a cell (`train_molecular_*_ms`: fewer edges, no stress).
+`--direct` times a DIRECT-FORCE model of the same architecture (`direct_forces=True`, GemNet.periodic_direct_forces: no backward
+pass, forces from the edge head of csrc/direct_force.hip, no stress) on the same structures — `direct_*_ms`: eager call, fixed-list
+replay, MD step with `exact=False` and `exact=True` — beside the autograd-force model (`autograd_*_ms`) timed in the same process:
+the two alternate in rounds and the median round is reported (`*_rounds`: every round).  `--direct --eager-only` runs nothing but
+eager periodic direct-force calls (for a kernel trace: launches per call = calls of a kernel / (warmup + steps)).
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -55,17 +60,21 @@ def timed(fn, steps, warmup):
     return t0.elapsed_time(t1) / steps
 
 
-def make_model(cutoff=5.0):
-    """The 4-block, 128-wide GemNet-T of this tool (seeded weights, fitted scale factors), on the host."""
+def make_model(cutoff=5.0, direct=False, coupled=False):
+    """The 4-block, 128-wide GemNet-T of this tool (seeded weights, fitted scale factors), on the host; `direct`: the
+    direct-force model of the same architecture with the periodic switch set."""
     from gemnet_pytorch_amd.model.gemnet import GemNet
     from oracle import gemnet_oracle as GO
     cfg = dict(num_spherical=7, num_radial=6, num_blocks=4, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
                emb_size_quad=32, emb_size_rbf=16, emb_size_cbf=16, emb_size_sbf=32, emb_size_bil_quad=32, emb_size_bil_trip=64,
                num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True, cutoff=cutoff)
+    if direct:
+        cfg.update(direct_forces=True, forces_coupled=bool(coupled))
     scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
     params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
     model = GemNet(**cfg, scale_file=scale_file)
     model.load_state_dict(GO.expand_to_reference_state_dict(params))
+    model.periodic_direct_forces = bool(direct)
     return model
 
 
@@ -98,6 +107,56 @@ def train_times(per, mol, args):
     return out
 
 
+def alternated(fns, steps, warmup, rounds=3):
+    """{name: fn} timed in turns, `rounds` times each -> {name: (median ms, [ms of every round])}."""
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, steps, warmup))
+    return {k: (float(np.median(v)), [round(x, 4) for x in v]) for k, v in times.items()}
+
+
+def direct_times(per, R, A, Zd, Nd, celld, args):
+    """The direct-force model beside the autograd-force model: eager, fixed-list replay, MD step (exact=False / True)."""
+    from gemnet_pytorch_amd.runtime import DynamicForceField, ForceGraphs
+    models = {"direct": make_model(args.cutoff, direct=True, coupled=args.coupled).to("cuda").eval(),
+              "autograd": make_model(args.cutoff).to("cuda").eval()}
+    stress = {"direct": False, "autograd": True}
+    out = {"forces_coupled": bool(args.coupled)}
+    if args.eager_only:
+        for _ in range(args.warmup + args.steps):
+            models["direct"](per)
+        torch.cuda.synchronize()
+        out["eager_calls"] = args.warmup + args.steps
+        return out
+
+    def record(tag, res):
+        for k, (med, rounds) in res.items():
+            out[f"{k}_{tag}_ms"], out[f"{k}_{tag}_rounds"] = med, rounds
+
+    record("eager", alternated({k: (lambda m=m, k=k: m(per, stress=stress[k])) for k, m in models.items()},
+                               args.steps, args.warmup))
+    graphs = {k: ForceGraphs(m, [per]) for k, m in models.items()}
+    record("graph", alternated({k: g.replay for k, g in graphs.items()}, args.steps, args.warmup))
+    walk = random_walk(R, args.steps + args.warmup)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % len(walk)
+        return walk[state["i"]]
+
+    fields = {k: DynamicForceField(m, Zd, [A], args.cutoff, 10.0, cell=celld) for k, m in models.items()}
+    for ff in fields.values():
+        ff(walk[0])
+    record("md_graph", alternated({k: (lambda ff=ff: ff(nxt(), exact=False)) for k, ff in fields.items()},
+                                  args.steps, args.warmup))
+    torch.cuda.synchronize()
+    record("md_graph_exact", alternated({k: (lambda ff=ff: ff(nxt())) for k, ff in fields.items()}, args.steps, args.warmup))
+    out["recaptures"] = {k: int(ff.recaptures) for k, ff in fields.items()}
+    out["md_index_failed"] = {k: bool(ff.index_failed()) for k, ff in fields.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=4)
@@ -105,6 +164,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cutoff", type=float, default=5.0)
     ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
+    ap.add_argument("--direct", action="store_true", help="time a direct-force model beside the autograd-force model")
+    ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
+    ap.add_argument("--eager-only", action="store_true", help="--direct: only eager direct-force calls (for a kernel trace)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -129,6 +191,10 @@ def main():
            "triplets_molecular": int(mol["id3_reduce_ca"].shape[0])}
     if args.train:
         out.update(train_times(per, mol, args))
+        print(json.dumps(out))
+        return
+    if args.direct:
+        out.update(direct_times(per, R, A, Zd, Nd, celld, args))
         print(json.dumps(out))
         return
     out["eager_periodic_ms"] = timed(lambda: model(per, stress=True), args.steps, args.warmup)
