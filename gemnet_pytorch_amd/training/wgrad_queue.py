@@ -51,6 +51,42 @@ def _rowmajor(t):
     return t if (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]) else t.contiguous()
 
 
+def build_tables(entries):
+    """The device tables of one grouped launch (include/gemnet_hip.h: gn_tn_problem, gn_tn_target) from plain numbers.
+
+    entries: (target, x_addr, y_addr, M, N, K, ldx, ldy, alpha) per product, target = (address, rows, cols, ld) of the region
+    of a `.grad` that receives alpha X^T Y (X (K,M) with row pitch ldx, Y (K,N) with row pitch ldy).  Returns
+    (probs, targets, slice_off, total_wg, total_fold_wg, ws_floats).  A product with an empty contraction or an empty output
+    adds nothing and gets no row (as gn_gemm_tn_f32 defines it); a target reached by such products alone gets none either.
+    Slices of one target are listed in entry order: the fold is deterministic."""
+    entries = [e for e in entries if e[3] > 0 and e[4] > 0 and e[5] > 0]
+    probs = np.zeros(len(entries), dtype=PROB)
+    by_param = {}
+    wg = 0
+    ws_off = 0
+    for i, (tgt, x_addr, y_addr, M, N, K, ldx, ldy, alpha) in enumerate(entries):
+        splitk = max(1, min(64, K // SPLIT_ROWS))
+        kchunk = (-(-K // splitk) + 15) // 16 * 16
+        splitk = -(-K // kchunk)
+        tiles = -(-M // 64) * -(-N // 64)
+        probs[i] = (x_addr, y_addr, M, N, K, ldx, ldy, splitk, kchunk, wg, ws_off, alpha, 0)
+        # keyed by the target REGION: fresh view objects of one weight block must fold into one accumulator
+        tgt = tuple(tgt)
+        by_param.setdefault(tgt, (tgt, []))[1].extend(ws_off + z * M * N for z in range(splitk))
+        wg += tiles * splitk
+        ws_off += splitk * M * N
+    targets = np.zeros(len(by_param), dtype=TARGET)
+    slices = []
+    fold_wg = 0
+    for j, ((addr, rows, cols, ld), offs) in enumerate(by_param.values()):
+        strided = ld != cols
+        targets[j] = (addr, rows * cols, len(slices), len(slices) + len(offs), fold_wg, cols if strided else 0,
+                      ld if strided else 0, 0)
+        slices.extend(offs)
+        fold_wg += -(-(rows * cols) // 64)
+    return probs, targets, np.asarray(slices, dtype=np.int64), wg, fold_wg, ws_off
+
+
 class _TableSlot:
     """One pinned host table + its device copy + the event that marks the copy's completion."""
 
@@ -118,34 +154,15 @@ class WeightGradQueue:
         items, self.items = self.items, []
         if not items:
             return
+        entries = []
+        for tgt, X, Y, _, alpha in items:
+            assert Y.shape[0] == X.shape[0]
+            entries.append((tgt, X.data_ptr(), Y.data_ptr(), X.shape[1], Y.shape[1], X.shape[0], X.stride(0), Y.stride(0),
+                            alpha))
+        probs, targets, slice_off, wg, fold_wg, ws_off = build_tables(entries)
+        if len(probs) == 0:
+            return              # nothing but empty contractions: they add nothing
         dev = items[0][1].device
-        probs = np.zeros(len(items), dtype=PROB)
-        by_param = {}
-        wg = 0
-        ws_off = 0
-        for i, (tgt, X, Y, _, alpha) in enumerate(items):
-            K, M = X.shape
-            N = Y.shape[1]
-            assert Y.shape[0] == K
-            splitk = max(1, min(64, K // SPLIT_ROWS))
-            kchunk = (-(-K // splitk) + 15) // 16 * 16
-            splitk = -(-K // kchunk)
-            tiles = -(-M // 64) * -(-N // 64)
-            probs[i] = (X.data_ptr(), Y.data_ptr(), M, N, K, X.stride(0), Y.stride(0), splitk, kchunk, wg, ws_off, alpha, 0)
-            # keyed by the target REGION: fresh view objects of one weight block must fold into one accumulator
-            by_param.setdefault(tgt, (tgt, []))[1].extend(ws_off + z * M * N for z in range(splitk))
-            wg += tiles * splitk
-            ws_off += splitk * M * N
-        targets = np.zeros(len(by_param), dtype=TARGET)
-        slices = []
-        fold_wg = 0
-        for j, ((addr, rows, cols, ld), offs) in enumerate(by_param.values()):
-            strided = ld != cols
-            targets[j] = (addr, rows * cols, len(slices), len(slices) + len(offs), fold_wg, cols if strided else 0,
-                          ld if strided else 0, 0)
-            slices.extend(offs)
-            fold_wg += -(-(rows * cols) // 64)
-        slice_off = np.asarray(slices, dtype=np.int64)
         blob = probs.tobytes() + targets.tobytes() + slice_off.tobytes()
         nbytes = len(blob)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -160,10 +177,10 @@ class WeightGradQueue:
         # the operand addresses sit in the device table: tell a recorder (hbcheck.py) what this launch reads and writes
         if _lib.TRACE is not None:
             _lib.note(reads=[x for it in items for x in it[1:3]],
-                      writes=[(a, 4 * ((rows - 1) * ld + cols)) for (a, rows, cols, ld), _ in by_param.values()])
+                      writes=[(a, 4 * ((rows - 1) * ld + cols)) for a, rows, cols, ld in dict.fromkeys(it[0] for it in items)])
         o_t = probs.nbytes
         o_s = o_t + targets.nbytes
-        check(_lib.load().gn_gemm_tn_grouped_f32(base, len(items), wg, base + o_t, len(by_param), fold_wg, base + o_s,
+        check(_lib.load().gn_gemm_tn_grouped_f32(base, len(probs), wg, base + o_t, len(targets), fold_wg, base + o_s,
                                                  ptr(ws), stream()), "gn_gemm_tn_grouped_f32")
         # operands stay allocated until the launches have been enqueued after them in stream order (eager: the
         # caching allocator is stream-ordered) or, for a captured graph, for as long as the graph may be replayed

@@ -280,8 +280,11 @@ def test_layer_stacks_match_per_layer_path(golden_model, monkeypatch, mode, e_ba
 
 
 def test_fused_trainer_step_matches_torch_optimizers(golden_model):
-    """N3: rescale + clip + AdamW/Adam(amsgrad) + EMA in two launches == the reference sequence built from
-    scale_shared_grads, clip_grad_norm_, torch.optim and ExponentialMovingAverage (three steps)."""
+    """N3: rescale + clip + AdamW/Adam(amsgrad) + EMA in two launches follows the reference sequence built from
+    scale_shared_grads, clip_grad_norm_, torch.optim and ExponentialMovingAverage over three steps of a whole model.
+    This is the INTEGRATION check (the packing, the step counter, the clip, the EMA views reach the kernel): at 2e-4 of
+    max|p| it cannot see the weight decay (3 lr wd = 6e-5), which parameters decay, eps, amsgrad or a few per cent of one
+    update.  Those are pinned against float64 in test_gpu_trainer_kernels.py."""
     import copy
     from gemnet_pytorch_amd.training.ddp import TrainStep, make_optimizer
     from gemnet_pytorch_amd.training.ema_decay import ExponentialMovingAverage
