@@ -193,7 +193,8 @@ class SegmentPlan:
             e_rank = inv - seg64[atom_of_edge]                # position of an edge in its atom's list
             r = self.reduce.idx32.to(torch.int64)
             a_q = atom_of_edge[r]
-            flat = g_off[a_q] + e_rank[r] * nJ[a_q] + (self.expand.idx32.to(torch.int64) - j_off[a_q])
+            j_loc = self.expand.idx32.to(torch.int64) - j_off[a_q]
+            flat = g_off[a_q] + e_rank[r] * nJ[a_q] + j_loc
             nt = (nJ + self.ROW_TILE - 1) // self.ROW_TILE
             t_off = torch.zeros(A + 1, dtype=torch.int64, device=dev)
             torch.cumsum(nt, 0, out=t_off[1:])
@@ -208,7 +209,18 @@ class SegmentPlan:
                 self._row_grid = ()
                 return None
             qmap = torch.full((max(g_total, 1),), -1, dtype=torch.int32, device=dev)
-            qmap[flat] = torch.arange(self.size, device=dev, dtype=torch.int32)
+            q = torch.arange(self.size, device=dev, dtype=torch.int32)
+            if static is None:
+                qmap[flat] = q
+            else:
+                # a padded batch (padded.py): a pad quadruplet may pair a reduce edge of one dummy group with an intermediate
+                # triplet of another, and several pad quadruplets may share one (edge, row) pair.  The first kind has no cell in
+                # its atom's grid (its `flat` would name a cell of another edge, row or atom): left out.  Of the second kind
+                # the largest number stays, whatever the order of the writes — an assignment with duplicate indices has no
+                # defined winner on the device.  Real quadruplets are neither: their cells are what they are without padding.
+                valid = (j_loc >= 0) & (j_loc < nJ[a_q])
+                qmap.scatter_reduce_(0, torch.where(valid, flat, torch.zeros_like(flat)),
+                                     torch.where(valid, q, torch.full_like(q, -1)), "amax", include_self=True)
             t = torch.arange(n_tasks, device=dev, dtype=torch.int64)
             task_atom = torch.searchsorted(t_off[1:].contiguous(), t, right=True)
             real = task_atom < A

@@ -2,6 +2,7 @@
 their own, and — on the CPU emulation of the launchers, float64 — the padded batch gives the real molecules the energies
 and forces of the unpadded one."""
 import numpy as np
+import pytest
 import torch
 
 import cpu_kernels
@@ -365,3 +366,57 @@ def test_dummy_molecule_geometry_scales_with_the_bond_length():
             flat = P.reshape(-1, 3)
             dist = (flat[:, None] - flat[None]).norm(dim=2) + torch.eye(flat.shape[0], dtype=torch.float64) * 1e9
             assert float(dist.min()) >= 0.99 * bond
+
+
+@pytest.mark.parametrize("G", [1, 2, 3])
+@pytest.mark.parametrize("extra", [(6, 0, 1, 1, 1), (12, 6, 4, 5, 9), (20, 2, 2, 7, 3), (36, 50, 6, 30, 400), (48, 300, 9, 40, 700),
+                                   (12, 6, 2, 12, 300)])
+def test_row_grid_of_padded_quadruplet_batches(golden_model2, G, extra):
+    """The dense per-atom grid [reduce edges into a][expand rows of a] of quadruplet numbers that the quadruplet x-adjoint reads
+    (graph.SegmentPlan.row_grid), built with the STATIC capacities of a padded batch.  Pad quadruplets may pair a reduce edge
+    of one dummy group with an intermediate triplet of another (their target atoms then differ, and the pad intermediate
+    triplets need not be sorted by atom) and many of them share one (edge, row) pair.  Whatever the padding does:
+      * every real quadruplet sits in the grid exactly once;
+      * every cell that names a quadruplet lies in the range of an atom, and that quadruplet's reduce edge IS the cell's edge
+        of that atom and its expand row the cell's row (nothing is written into another edge's, row's or atom's cell);
+      * the grid of the batch fits the static capacity;
+      * a cell that several quadruplets claim holds the largest of them (no dependence on the order of the writes)."""
+    from gemnet_pytorch_amd.graph import GraphPlan
+    cfg, params, inputs = load_case(golden_model2, "q2s")
+    padded, A, n_mol = _padded_quad_inputs(inputs, G, extra)
+    Q = int(inputs["id4_reduce_ca"].shape[0])
+    plan = GraphPlan(padded, False)
+    perm, seg, j_off, qmap, g_off, task_atom, task_row0, n_tasks = plan.quad.row_grid
+    seg, j_off, g_off, cells = seg.long(), j_off.long(), g_off.long(), qmap.long()
+    nA = plan.n_atoms
+    assert int(g_off[-1]) <= qmap.numel() and qmap.numel() == 64 * plan.quad.n_expand
+    pos = torch.nonzero(cells >= 0)[:, 0]
+    q = cells[pos]
+    assert int(q.max()) < plan.quad.size
+    assert bool((torch.bincount(q[q < Q], minlength=Q) == 1).all())          # every real quadruplet, once
+    assert int(torch.bincount(q).max()) == 1                                 # no quadruplet twice
+    assert int(pos.max()) < int(g_off[-1])
+    a = torch.searchsorted(g_off[1:].contiguous(), pos, right=True)
+    nJ = (j_off[1:] - j_off[:-1])[a]
+    loc = pos - g_off[a]
+    edges = perm.long() if perm is not None else torch.arange(plan.n_edges)
+    red, exp = plan.quad.reduce.idx64[q], plan.quad.expand.idx64[q]
+    assert torch.equal(edges[seg[a] + loc // nJ], red) and torch.equal(j_off[a] + loc % nJ, exp)
+    assert torch.equal(plan.id_a.idx64[red], a)
+    # the largest claimant of every (edge, row) pair that has a cell; the quadruplets without a cell are pad quadruplets
+    key = plan.quad.reduce.idx64 * plan.quad.n_expand + plan.quad.expand.idx64
+    winner = torch.full((int(key.max()) + 1,), -1, dtype=torch.int64).scatter_reduce_(
+        0, key, torch.arange(plan.quad.size), "amax", include_self=True)
+    assert torch.equal(winner[red * plan.quad.n_expand + exp], q)
+    absent = torch.ones(plan.quad.size, dtype=torch.bool)
+    absent[q] = False
+    assert not bool(absent[:Q].any())
+    # the task table covers every expand row of every atom once (64-row tiles), slots beyond carry atom -1
+    ta, tr = task_atom.long(), task_row0.long()
+    real = ta >= 0
+    rows = torch.zeros(plan.quad.n_expand, dtype=torch.int64)
+    for t_a, t_r in zip(ta[real].tolist(), tr[real].tolist()):
+        n = min(64, int(j_off[t_a + 1] - j_off[t_a]) - t_r)
+        assert n > 0
+        rows[int(j_off[t_a]) + t_r: int(j_off[t_a]) + t_r + n] += 1
+    assert bool((rows == 1).all()) and int(real.sum()) <= n_tasks == ta.numel()
