@@ -106,19 +106,13 @@ struct grouped_row {
   float y[S];
 };
 
+// (the body of one group: shared by the kernel below and, for groups beyond 32 rows, by the matrix-core kernel)
 template <int S>
-__global__ __launch_bounds__(1024) void bil_reduce_t_grouped_kernel(
+__device__ __forceinline__ void bil_reduce_t_group_rows(
     const float* __restrict__ Y, const float* __restrict__ dSm, const int32_t* __restrict__ grp_rows,
-    const int32_t* __restrict__ grp_off, const int2* __restrict__ grp_kseg, const int32_t* __restrict__ permT,
-    const int32_t* __restrict__ rposT, float* __restrict__ dx, int max_rows) {
+    const int2* __restrict__ grp_kseg, const int32_t* __restrict__ permT, const int32_t* __restrict__ rposT,
+    float* __restrict__ dx, float* gtile, int r0, int n) {
   constexpr int C = 64, SC = S * C, NV = SC / 4;
-  extern __shared__ float gtile[];  // [rows of the group][S*C]
-  const int g = blockIdx.x;
-  const int r0 = grp_off[g], n = grp_off[g + 1] - r0;
-  if (n <= 0) return;
-  // the tile was sized for `max_rows` rows — a caller-supplied bound when the plan is built inside a hipGraph
-  // (padded.py: largest in-degree of an atom).  A group beyond it would write past the LDS allocation: abort loudly.
-  if (n > max_rows) __builtin_trap();
   for (int i = threadIdx.x; i < n * NV; i += 1024) {
     const int l = i / NV, v = i - l * NV;
     const float4 d = reinterpret_cast<const float4*>(dSm + (int64_t)grp_rows[r0 + l] * SC)[v];
@@ -173,6 +167,171 @@ __global__ __launch_bounds__(1024) void bil_reduce_t_grouped_kernel(
   for (int l = w; l < n; l += 32) {
     finish_row(ra), finish_row(rb);
     open_row(ra, l + 32), open_row(rb, l + 48);
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(1024) void bil_reduce_t_grouped_kernel(
+    const float* __restrict__ Y, const float* __restrict__ dSm, const int32_t* __restrict__ grp_rows,
+    const int32_t* __restrict__ grp_off, const int2* __restrict__ grp_kseg, const int32_t* __restrict__ permT,
+    const int32_t* __restrict__ rposT, float* __restrict__ dx, int max_rows) {
+  extern __shared__ float gtile[];  // [rows of the group][S*C]
+  const int g = blockIdx.x;
+  const int r0 = grp_off[g], n = grp_off[g + 1] - r0;
+  if (n <= 0) return;
+  // the tile was sized for `max_rows` rows — a caller-supplied bound when the plan is built inside a hipGraph
+  // (padded.py: largest in-degree of an atom).  A group beyond it would write past the LDS allocation: abort loudly.
+  if (n > max_rows) __builtin_trap();
+  bil_reduce_t_group_rows<S>(Y, dSm, grp_rows, grp_kseg, permT, rposT, dx, gtile, r0, n);
+}
+
+// The same adjoint of one atom as a dense product on the matrix cores (S = 7, C = 64, groups of n <= 32 rows):
+//   dX_a (n x 64) = Ymat_a^T (n x 7n) . dSm_a (7n x 64),   Ymat_a[(c, s), b] = Y[t(c, b), s], 0 where c -> a <- b has no triplet,
+// b = local rank of the expand row, c = local rank of the reduce edge.  v_mfma_f32_16x16x4_f32 (exact f32 products, f32
+// accumulate): M = expand rows in tiles of 16, N = 4 tiles of 16 channels, K = (c, s) in ascending c, then s — one accumulator
+// chain per output tile, so a row's sum has ONE order whatever the launch.  Wave w < 8 owns the output tile (w >> 2, w & 3).
+//   B operand: the parked dSm tile IS the (7n x 64) matrix, row k = 7 c + s.  The 16-column block of row k sits XORed with
+//     k & 1 (a lane group of ds_read_b32 spans two k's of one column block: the swizzle puts them on disjoint banks).
+//   A operand: an LDS image [16 or 32 rows b][lda] behind the n tile rows, zero-filled, then scattered from Y.  Up to n = 29
+//     it holds all of K (lda = 7 n rounded up to 16, + 2); for n = 30..32 that would pass 80 KiB — one workgroup per CU —
+//     so K goes in two chunks of 16 reduce edges (lda = 114) with the accumulators kept across them.  lda = 2 x odd: the
+//     16 rows x 2 k's of a lane group fall on 32 different banks.
+//   K is padded to a multiple of 16 with the image's zeros on the A side and the group's LAST real tile row on the B side:
+//     a zero only ever meets a value of dSm, never LDS that was not written.
+// Index staging: the plan's flat list of the group's transposed entries (graph.SegmentPlan.group_entries: triplet number and
+// packed (b, c) per entry, the rows of a group back to back) — every thread takes one entry: (entry, Y) are two load rounds per
+// WORKGROUP, under the tile fill, instead of three per row.  Entries that repeat a (b, c) pair (the pad triplets of a padded
+// batch, padded.py) are adjacent in the list; the first of a run sums the run's Y rows in list order and scatters the sum.
+// Groups beyond 32 rows run the scalar body above in the same launch: the path depends on the group's own size only.
+typedef float v4f_b __attribute__((ext_vector_type(4)));
+#ifndef GN_XA_ONE
+#define GN_XA_ONE 29     // largest group whose image holds all of K (0: chunks of 16 for every group, the variant it was measured against)
+#endif
+constexpr int XA_ROWS = 32, XA_ONE = GN_XA_ONE, XA_KC = 16;
+constexpr int xa_lda(int kc) { return ((7 * kc + 15) & ~15) + 2; }
+constexpr size_t xa_lds(int n) { return ((size_t)n * 7 * 64 + (size_t)32 * xa_lda(n <= XA_ONE ? n : XA_KC)) * sizeof(float); }
+// the largest need of a matrix group: 78 848 B at n = 29 (n = 32: 71 936 B)
+constexpr size_t XA_LDS = xa_lds(XA_ONE) > xa_lds(XA_ROWS) ? xa_lds(XA_ONE) : xa_lds(XA_ROWS);
+static_assert(XA_ONE < XA_ROWS && XA_LDS >= xa_lds(XA_ONE + 1) && XA_LDS <= 80 * 1024, "two workgroups per CU");
+
+__global__ __launch_bounds__(1024) void bil_x_adjoint_atoms_kernel(
+    const float* __restrict__ Y, const float* __restrict__ dSm, const int32_t* __restrict__ grp_rows,
+    const int32_t* __restrict__ grp_off, const int2* __restrict__ grp_kseg, const int32_t* __restrict__ permT,
+    const int32_t* __restrict__ rposT, const int32_t* __restrict__ ent_off, const int32_t* __restrict__ ent_t,
+    const int32_t* __restrict__ ent_bc, float* __restrict__ dx, int max_rows) {
+  constexpr int S = 7, C = 64, SC = S * C, NV = SC / 4;
+  extern __shared__ float gtile[];  // [rows of the group][S*C] | Ymat image [16 or 32][lda]
+  const int g = blockIdx.x;
+  const int r0 = grp_off[g], n = grp_off[g + 1] - r0;
+  if (n <= 0) return;
+  if (n > max_rows) __builtin_trap();   // (as above: the tile was sized for max_rows rows)
+  if (n > XA_ROWS) {
+    bil_reduce_t_group_rows<S>(Y, dSm, grp_rows, grp_kseg, permT, rposT, dx, gtile, r0, n);
+    return;
+  }
+  const int kc = n <= XA_ONE ? n : XA_KC;          // reduce edges per K chunk
+  const int lda = xa_lda(kc);
+  float* aimg = gtile + n * SC;
+  const int tid = threadIdx.x;
+  const int e0 = ent_off[g], e1 = ent_off[g + 1];
+  // round 1: this thread's entry, its predecessor (is it the first of a run of equal (b, c)?) and its triplet
+  const int i0 = e0 + tid;
+  const bool on0 = i0 < e1;
+  const int bc0 = on0 ? ent_bc[i0] : -1;
+  const int bcp = (on0 && tid > 0) ? ent_bc[i0 - 1] : -1;
+  const int t0 = on0 ? ent_t[i0] : 0;
+  // the tile fill: n * NV float4 (<= 3584), at most four per thread, all in flight together
+  float4 d[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = tid + 1024 * u;
+    d[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < n * NV) {
+      const int l = i / NV;
+      d[u] = reinterpret_cast<const float4*>(dSm + (int64_t)grp_rows[r0 + l] * SC)[i - l * NV];
+    }
+  }
+  // round 2: Y of the entry (and of the rest of its run)
+  auto sum_run = [&](int i, int bc, int t, float (&y)[S]) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) y[s] = Y[(int64_t)t * S + s];
+    for (int j = i + 1; j < e1 && ent_bc[j] == bc; ++j) {
+      const int tj = ent_t[j];
+#pragma unroll
+      for (int s = 0; s < S; ++s) y[s] += Y[(int64_t)tj * S + s];
+    }
+  };
+  float y0[S];
+  const bool lead0 = on0 && bc0 != bcp;
+  if (lead0) sum_run(i0, bc0, t0, y0);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = tid + 1024 * u;
+    if (i < n * NV) {
+      const int k = i >> 4, v = i & 15;
+      reinterpret_cast<float4*>(gtile)[k * 16 + (v ^ ((k & 1) << 2))] = d[u];
+    }
+  }
+  auto zero_image = [&]() {
+    for (int i = tid; i < (n > 16 ? 8 : 4) * lda; i += 1024) reinterpret_cast<float4*>(aimg)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto scatter = [&](int bc, const float (&y)[S], int ch) {
+    const int b = bc & 0xffff, c = (int)((unsigned)bc >> 16);
+    if (b < n && c < n && (c >= kc) == (ch != 0)) {
+      float* a = aimg + b * lda + (c - (ch ? kc : 0)) * S;
+#pragma unroll
+      for (int s = 0; s < S; ++s) a[s] = y[s];
+    }
+  };
+  zero_image();
+  __syncthreads();
+  const int lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int mt = w >> 2, nt = w & 3;
+  const bool mm = w < 8 && 16 * mt < n;
+  const int kmax = S * n - 1;
+  v4f_b acc = (v4f_b){0.f, 0.f, 0.f, 0.f};
+  const int nch = n > kc ? 2 : 1;
+  for (int ch = 0; ch < nch; ++ch) {
+    if (ch) {
+      __syncthreads();   // the previous chunk's image has been read
+      zero_image();
+      __syncthreads();
+    }
+    if (lead0) scatter(bc0, y0, ch);
+    for (int i = i0 + 1024; i < e1; i += 1024) {   // (more than 1024 entries: only with repeated pairs)
+      const int bc = ent_bc[i];
+      if (ent_bc[i - 1] == bc) continue;
+      float y[S];
+      sum_run(i, bc, ent_t[i], y);
+      scatter(bc, y, ch);
+    }
+    __syncthreads();
+    if (mm) {
+      // K steps four at a time, their eight operands in flight together (the image's zeros reach to the next multiple of 16,
+      // so rounding the steps up to four adds exact zeros)
+      const int kquads = (S * min(kc, n - kc * ch) + 15) >> 4;
+      const float* ap = aimg + (16 * mt + l15) * lda + lg;
+      const int kb = S * kc * ch + lg, col = 16 * nt + l15;
+      for (int q = 0; q < kquads; ++q) {
+        float a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = min(kb + 16 * q + 4 * u, kmax);
+          a[u] = ap[16 * q + 4 * u];
+          b[u] = gtile[k * C + (col ^ ((k & 1) << 4))];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], acc, 0, 0, 0);
+      }
+    }
+  }
+  if (mm) {   // D layout: col = l15 (channel within the tile), row = 4 lg + r (expand row within the tile)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = 16 * mt + 4 * lg + r;
+      if (m < n) dx[(int64_t)grp_rows[r0 + m] * C + 16 * nt + l15] = acc[r];
+    }
   }
 }
 
@@ -346,7 +505,6 @@ __global__ __launch_bounds__(256) void bil_reduce_project_kernel(
 // reads Y[t + lg][16 mt + l15] (16 lanes = 64 contiguous bytes of one Y row) and x[g(t + lg)][16 nt + l15] — so the
 // per-quadruplet cost drops from 49 scalar loads + 49 FMAs per lane to 7 loads + 8 MFMAs per 4 quadruplets.
 // K2 (P = B[e]^T Sm, 32 x 49 x 32) runs on the same cores with Sm passed through LDS.
-typedef float v4f_b __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void bil_reduce_project_mfma49_kernel(
     const float* __restrict__ Y, const float* __restrict__ x, const int32_t* __restrict__ expand_idx,
@@ -1417,6 +1575,31 @@ extern "C" int gn_bil_reduce_t_grouped_f32(const float* Y, const float* dSm, con
   }
   hipLaunchKernelGGL(bil_reduce_t_grouped_kernel<7>, dim3((unsigned)G), dim3(1024), lds, st, Y, dSm, grp_rows, grp_off,
                      reinterpret_cast<const int2*>(grp_kseg), permT, rposT, dx, max_rows);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_bil_x_adjoint_atoms_f32(const float* Y, const float* dSm, const int32_t* grp_rows,
+                                          const int32_t* grp_off, const int32_t* grp_kseg, const int32_t* permT,
+                                          const int32_t* rposT, const int32_t* ent_off, const int32_t* ent_t,
+                                          const int32_t* ent_bc, float* dx, int64_t G, int max_rows, int S, int C,
+                                          void* stream) {
+  if (G <= 0) return 0;
+  if (C != 64 || S != 7 || max_rows < 1) return (int)hipErrorInvalidValue;
+  // both paths always fit: the scalar body needs max_rows tile rows, the matrix path its tile and image at n = 32
+  const size_t rows_lds = (size_t)max_rows * S * C * sizeof(float);
+  const size_t lds = rows_lds > XA_LDS ? rows_lds : XA_LDS;
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static bool lds_set = false;
+  if (!lds_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bil_x_adjoint_atoms_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    lds_set = true;
+  }
+  hipLaunchKernelGGL(bil_x_adjoint_atoms_kernel, dim3((unsigned)G), dim3(1024), lds, st, Y, dSm, grp_rows, grp_off,
+                     reinterpret_cast<const int2*>(grp_kseg), permT, rposT, ent_off, ent_t, ent_bc, dx, max_rows);
   GN_LAUNCH_CHECK();
   return 0;
 }

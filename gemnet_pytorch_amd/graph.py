@@ -265,7 +265,57 @@ class SegmentPlan:
             else:
                 max_rows = int((off[1:] - off[:-1]).max().item()) if rows.shape[0] else 0
             self._groups = (rows.to(torch.int32).contiguous(), off, kseg, rposT, max_rows)
+            self._group_entries = None
+            from . import kernels as _K
+            if _K.USE_XADJ_MFMA:
+                # built with the groups, on their stream (GraphPlan.warm): the x-adjoint launch reads both
+                self._group_entries = _group_entry_list(rows, off, rank, key, kseg, permT, self.expand.idx64, rposT)
         return self._groups
+
+    @property
+    def group_entries(self):
+        """(ent_off, ent_t, ent_bc) for gn_bil_x_adjoint_atoms_f32, or None without row groups: the transposed entries of every
+        group as one flat list — the transposed segments of the group's rows back to back, in group order; per entry the
+        triplet number and b | c << 16, the local ranks of its expand row (b) and reduce row (c).  Device-side tensor ops of
+        static shapes only: a plan built inside a capture builds it there."""
+        if self.groups is None:
+            return None
+        if self._group_entries is None:
+            rows, off, kseg, rposT, _ = self._groups
+            key = self._row_group
+            rows64 = rows.to(torch.int64)
+            rank = torch.empty_like(rows64)
+            rank[rows64] = torch.arange(rows64.shape[0], device=rows.device) - off.to(torch.int64)[key[rows64]]
+            permT, _segT = self.expand.csr
+            self._group_entries = _group_entry_list(rows64, off, rank, key, kseg, permT, self.expand.idx64, rposT)
+        return self._group_entries
+
+
+def _group_entry_list(rows, off, rank, key, kseg, permT, expand_idx, rposT):
+    """The flat per-group entry list of `SegmentPlan.group_entries`.  rows: the rows in group order (int64), off: the groups'
+    offsets into it, rank / key: local rank and group of every row, kseg: the transposed segment of every row of `rows`,
+    permT: the transposed order of the entries (None: the entries are sorted by expand row already), rposT: the local rank of
+    every transposed entry's reduce row."""
+    dev = rows.device
+    T = int(rposT.shape[0])
+    G = int(off.shape[0]) - 1
+    k0 = kseg[:, 0].to(torch.int64)
+    length = kseg[:, 1].to(torch.int64) - k0
+    start = torch.cumsum(length, 0) - length            # first slot of every row of `rows` in the flat list
+    t_of_k = torch.arange(T, device=dev, dtype=torch.int64) if permT is None else permT.to(torch.int64)
+    j = expand_idx[t_of_k].to(torch.int64)               # expand row of every transposed entry
+    off64 = off.to(torch.int64)
+    p = off64[key[j].to(torch.int64)] + rank[j]          # position of that row in `rows`
+    slot = start[p] + (torch.arange(T, device=dev, dtype=torch.int64) - k0[p])
+    ent_t = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    ent_bc = torch.zeros(max(T, 1), dtype=torch.int32, device=dev)
+    ent_t[slot] = t_of_k.to(torch.int32)
+    ent_bc[slot] = (rank[j] | (rposT.to(torch.int64) << 16)).to(torch.int32)
+    # a group's entries start where its first row's do; an empty group at the end starts at T
+    start_ext = torch.cat([start, torch.full((1,), T, dtype=torch.int64, device=dev)])
+    ent_off = start_ext[off64].to(torch.int32).contiguous()
+    assert ent_off.shape[0] == G + 1
+    return ent_off, ent_t, ent_bc
 
 
 class GraphPlan:

@@ -539,6 +539,12 @@ ANG_F16_MASK = int(os.environ.get("GEMNET_ANG_F16", "7")) & 7
 USE_EXPAND_POS = os.environ.get("GEMNET_EXPAND_POS", "0") == "1"
 
 
+# The triplet x-adjoint per atom on the matrix cores (gn_bil_x_adjoint_atoms_f32: groups of <= 32 rows as one dense product
+# on v_mfma_f32_16x16x4_f32, index staging from the plan's flat entry list; larger groups keep the scalar body in the same
+# launch).  GEMNET_XADJ_MFMA=0: the scalar grouped launch (gn_bil_reduce_t_grouped_f32) for every group.
+USE_XADJ_MFMA = os.environ.get("GEMNET_XADJ_MFMA", "1") == "1"
+
+
 def bil_reduce_t(Y, D, sp):
     """dx[j,c] = sum_{t: g(t)=j} sum_s Y[t,s] D[r(t),s,c].
     Angle form (GemNet-Q): the row-stationary kernel when the plan carries the per-atom grid (USE_ROW_GRID, the default: no
@@ -584,6 +590,12 @@ def bil_reduce_t(Y, D, sp):
         # triplets: both edges end in the same atom — that atom's dSm blocks are parked in LDS once
         rows, off, kseg, rposT, max_rows = grp
         dx = torch.empty((sp.n_expand, C), device=Y.device, dtype=torch.float32)
+        if USE_XADJ_MFMA:
+            ent_off, ent_t, ent_bc = sp.group_entries
+            check(_lib.load().gn_bil_x_adjoint_atoms_f32(ptr(Y), ptr(D), ptr(rows), ptr(off), ptr(kseg), ptr(permT), ptr(rposT),
+                                                         ptr(ent_off), ptr(ent_t), ptr(ent_bc), ptr(dx), off.shape[0] - 1,
+                                                         max_rows, S, C, stream()), "gn_bil_x_adjoint_atoms_f32")
+            return dx
         check(_lib.load().gn_bil_reduce_t_grouped_f32(ptr(Y), ptr(D), ptr(rows), ptr(off), ptr(kseg), ptr(permT),
                                                       ptr(rposT), ptr(dx), off.shape[0] - 1, max_rows, S, C, stream()),
               "gn_bil_reduce_t_grouped_f32")

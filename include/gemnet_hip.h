@@ -475,6 +475,17 @@ int gn_bil_reduce_t_f32(const float* Y, const float* dSm, const int32_t* reduce_
 int gn_bil_reduce_t_grouped_f32(const float* Y, const float* dSm, const int32_t* grp_rows, const int32_t* grp_off,
                                 const int32_t* grp_kseg, const int32_t* permT, const int32_t* rposT, float* dx,
                                 int64_t G, int max_rows, int S, int C, void* stream);
+/* The grouped adjoint with groups of at most 32 rows contracted on the matrix cores (v_mfma_f32_16x16x4_f32, fp32 in and
+ * out): dX_g (n x C) = Ymat_g^T (n x S n) . dSm_g (S n x C), Ymat_g[(c, s), b] = Y[t, s] for the entry t that pairs the rows
+ * of local ranks c (reduce) and b (expand), 0 where there is none; entries repeating a pair are summed.  Larger groups run the
+ * scalar body of gn_bil_reduce_t_grouped_f32 in the same launch, bit-identical to it: the path depends on the group's own
+ * size only, never on max_rows, the grid or the other groups.  ent_off[g]..ent_off[g+1] = the group's transposed entries
+ * (the transposed segments of its rows back to back, in group order); ent_t[i] = the entry's triplet, ent_bc[i] =
+ * b | c << 16.  LDS = max(max_rows*S*C*4, 78 848 B) <= 160 KB, else hipErrorInvalidValue.  S = 7 and C = 64 only. */
+int gn_bil_x_adjoint_atoms_f32(const float* Y, const float* dSm, const int32_t* grp_rows, const int32_t* grp_off,
+                               const int32_t* grp_kseg, const int32_t* permT, const int32_t* rposT,
+                               const int32_t* ent_off, const int32_t* ent_t, const int32_t* ent_bc, float* dx,
+                               int64_t G, int max_rows, int S, int C, void* stream);
 /* dxt[t,c] = sum_s Y[t,s] * dSm[r(t),s,c]: the per-triplet/quadruplet rows of the adjoint above (dx[j] = sum of
  * dxt over the transposed segment of j: gn_segsum_rows_f32), grouped by reduce edge so that dSm[e] is read once
  * per edge instead of once per quadruplet (the S = 49 tensor basis: 56 GB -> 4 GB of traffic at B = 32). */

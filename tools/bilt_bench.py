@@ -6,7 +6,7 @@ import torch
 from gemnet_pytorch_amd import kernels as K
 from gemnet_pytorch_amd.graph import GraphPlan, SegmentPlan
 from gemnet_pytorch_amd.kernels import ptr, stream
-from tools.gemm_bench import timeit
+from tools.gemm_bench import graph_best, timeit
 import bench
 
 _exp = os.path.join(os.path.dirname(os.path.abspath(__file__)), "exp")
@@ -35,7 +35,11 @@ dx = torch.empty(E, 64, device="cuda")
 plain = SegmentPlan(inputs["id3_reduce_ca"], inputs["id3_expand_ba"], E, E)
 ref = K.bil_reduce_t(Y, D, plain)
 print(f"ungrouped product kernel : {timeit(lambda: K.bil_reduce_t(Y, D, plain)):7.2f} us")
-print(f"grouped product kernel   : {timeit(lambda: K.bil_reduce_t(Y, D, sp)):7.2f} us   err {float((K.bil_reduce_t(Y, D, sp) - ref).abs().max()):.2e}")
+for on, name in ((False, "grouped product kernel   "), (True, "per-atom MFMA kernel     ")):
+    K.USE_XADJ_MFMA = on          # (read at call time: GEMNET_XADJ_MFMA only sets its initial value)
+    err = float((K.bil_reduce_t(Y, D, sp) - ref).abs().max())
+    print(f"{name}: {graph_best(lambda: K.bil_reduce_t(Y, D, sp)):7.2f} us (200 launches in one graph, best of 3)   err {err:.2e}")
+K.USE_XADJ_MFMA = False
 
 
 def grouped(mode, nt, lds_rows):
