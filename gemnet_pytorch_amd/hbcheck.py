@@ -13,7 +13,7 @@ bisection with a proof obligation:
 How it gets the facts (nothing is modelled; all of it is read back from the runtime):
   * memory accesses of OUR launches: every launcher passes its operands through `_lib.ptr()` and calls the library through
     `_lib.load()`; with a recorder installed both report here.  Which pointer argument is read and which is written comes
-    from the `const` qualifiers of include/gemnet_hip.h (parsed below, struct fields included); launches whose operands sit
+    from the `const` qualifiers of include/gemnet_hip.h (read by _abi.py, struct fields included); launches whose operands sit
     in device-resident tables (grouped weight gradients / grouped weight packing) declare them with `note()`.
   * memory accesses of ATen operations (the autograd engine's gradient sums, copies, fills, the loss): a
     TorchDispatchMode — it follows the engine into its worker thread — reports inputs (reads), outputs and mutated
@@ -34,59 +34,11 @@ import bisect
 import contextlib
 import ctypes
 import os
-import re
 import traceback
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_HEADER = os.path.join(os.path.dirname(_HERE), "include", "gemnet_hip.h")
-
-
-# ------------------------------------------------------------------------------------------ the C ABI, from the header
-def _strip_comments(text):
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"//[^\n]*", " ", text)
-
-
-def _param_kind(decl):
-    """One parameter / field declaration -> (name, kind): kind 'r' / 'w' (pointer to const / to mutable data),
-    'ra' (host array of pointers to const data), 'struct:<type>' (pointer to a struct), 'stream', or None (a value)."""
-    decl = decl.strip()
-    m = re.match(r"(.*?)([A-Za-z_]\w*)\s*(\[\w*\])?$", decl, flags=re.S)
-    typ, name = m.group(1).strip(), m.group(2)
-    stars = typ.count("*")
-    if stars == 0:
-        return name, None
-    if name == "stream":
-        return name, "stream"
-    base = typ.replace("*", " ").replace("const", " ").split()
-    if stars == 2:
-        return name, "ra" if typ.lstrip().startswith("const") else "wa"
-    if base and base[0].startswith("gn_") and base[0] not in ("gn_pack_job", "gn_tn_problem", "gn_tn_target"):
-        return name, "struct:" + base[0]
-    return name, "r" if re.match(r"const\b", typ) else "w"
-
-
-def parse_header(path=_HEADER):
-    """-> (functions {name: [(param, kind)]}, structs {name: [(field, kind)]}) of the C ABI."""
-    text = _strip_comments(open(path).read())
-    structs = {}
-    for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
-        fields = []
-        for stmt in m.group(1).split(";"):
-            stmt = stmt.strip()
-            if not stmt:
-                continue
-            if "*" not in stmt:      # `int M, N, K` — values
-                continue
-            fields.append(_param_kind(stmt))
-        structs[m.group(2)] = fields
-    funcs = {}
-    for m in re.finditer(r"\b(?:int|int64_t)\s+(gn_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        params = [p for p in (q.strip() for q in m.group(2).split(",")) if p and p != "void"]
-        funcs[m.group(1)] = [_param_kind(p) for p in params]
-    return funcs, structs
+from ._abi import parse_header   # noqa: F401  (the C ABI's read / write kinds come from include/gemnet_hip.h)
 
 
 # ------------------------------------------------------------------------------------------------- HIP graph read-back

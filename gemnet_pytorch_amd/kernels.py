@@ -13,7 +13,8 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import GN_CHAIN_MAX_OPS, GemmArgs, addr, check, ptr, require_device, stream
+from ._lib import (GN_ANG_F16, GN_CHAIN_MAX_OPS, GN_CHAIN_ROW, GN_CHAIN_WIDE, GN_SPLIT_F16X2_ROW, GemmArgs, addr, check, ptr,
+                   require_device, stream)
 
 
 def _f32c(t):
@@ -529,7 +530,6 @@ ATOM_BLOCK_MAX_ROWS = 848
 # Which angle-form kernels run their products on the fp16 matrix pipe (`arith` = GN_ANG_F16 of the launch): bit 0 = K1 of
 # bil_reduce_project (only under the "h3" Dense arithmetic: x unscaled), bit 1 = the angle gradient bil_dy_multi, bit 2 = the
 # x-adjoint bil_expand (both under an exact per-edge scale: any magnitude).  Read-only configuration (A/B runs, tests).
-GN_ANG_F16 = 1
 ANG_F16_MASK = int(os.environ.get("GEMNET_ANG_F16", "7")) & 7
 
 
@@ -1151,9 +1151,6 @@ def use_mode(mode):
 # row blocks on 1 024 SIMDs put two 16-row waves on one SIMD of every CU, and a wave's ds_read_b128 stream of weight fragments
 # runs at ~28 B/clk) — selectable, not the default.
 CHAIN_LAYOUT = os.environ.get("GEMNET_CHAIN_LAYOUT", "tall")
-GN_CHAIN_WIDE = 0x100
-GN_CHAIN_ROW = 0x200
-GN_SPLIT_F16X2_ROW = 2
 # per-launch tuning of the wide layout (GN_CHAIN_WIDE_ROWS / GN_CHAIN_WIDE_STAGGER bits of `nprod`; 0 = automatic / none)
 WIDE_TILE_ROWS = int(os.environ.get("GN_CHAIN_TILE_ROWS", "0"))
 WIDE_STAGGER = int(os.environ.get("GN_CHAIN_STAGGER", "0"))
@@ -1196,9 +1193,7 @@ def pack_job_table(entries):
     format of each job is the one its buffer was first packed in (`packed._gn_fmt`).
     -> (table tensor, total_units).  Host -> device copy: not inside a stream capture."""
     import numpy as np
-    JOB = np.dtype([("W", "<u8"), ("out", "<u8"), ("N", "<i4"), ("K", "<i4"), ("ldw", "<i4"), ("trans", "<i4"),
-                    ("unit_begin", "<i4"), ("fmt", "<i4")])
-    assert JOB.itemsize == 40
+    JOB = np.dtype(_lib.ABI.structs["gn_pack_job"])
     jobs = np.zeros(len(entries), dtype=JOB)
     unit = 0
     for i, (W, trans, packed) in enumerate(entries):

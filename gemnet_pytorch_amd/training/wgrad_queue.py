@@ -14,11 +14,7 @@ import torch
 from .. import _lib
 from .._lib import check, ptr, stream
 
-PROB = np.dtype([("X", "<u8"), ("Y", "<u8"), ("M", "<i4"), ("N", "<i4"), ("K", "<i4"), ("ldx", "<i4"), ("ldy", "<i4"),
-                 ("splitk", "<i4"), ("kchunk", "<i4"), ("wg_begin", "<i4"), ("ws_off", "<i8"), ("alpha", "<f4"), ("pad", "<i4")])
-TARGET = np.dtype([("out", "<u8"), ("n", "<i8"), ("slice_begin", "<i4"), ("slice_end", "<i4"), ("wg_begin", "<i4"),
-                   ("cols", "<i4"), ("ld", "<i4"), ("pad", "<i4")])
-assert PROB.itemsize == 64 and TARGET.itemsize == 40
+PROB, TARGET = (np.dtype(_lib.ABI.structs[n]) for n in ("gn_tn_problem", "gn_tn_target"))
 # rows of the contraction per split-K slice.  A step queues ~480 products at once (1 900 output tiles of 64 x 64: the grid
 # is full without any split), and every slice costs a (M, N) partial written and folded again: see profiles/r3_ab.txt
 import os as _os
