@@ -114,18 +114,31 @@ def param_spec(cfg):
     return spec
 
 
-def make_params(cfg, seed, scale_factors=None, dtype=torch.float64):
+def _standardized(w, axes):
+    """The standardisation the reference applies to every initialised weight (initializers.py:4-17): zero mean and unit
+    (unbiased) variance over the input axes, per output unit."""
+    mean = w.mean(axis=axes, keepdims=True)
+    var = w.var(axis=axes, ddof=1, keepdims=True)
+    return (w - mean) / np.sqrt(var + 1e-6)
+
+
+def make_params(cfg, seed, scale_factors=None, dtype=torch.float64, standardize=False):
     """Builder-owned deterministic weights (NOT reference-initialised): N(0, 1/fan_in) for
     dense/bilinear weights, U(-sqrt3, sqrt3) embeddings, frequencies n*pi*(1+small jitter),
-    scale factors from the json dict (1.0 when the name is absent)."""
+    scale factors from the json dict (1.0 when the name is absent).
+    standardize=True: the same draws, then every dense/bilinear weight is standardised over its input axes as the
+    reference's initialiser does (initializers.py:4-17,31-38) before the fan_in^-1/2: without it the row means of the
+    random weights make the activations of a 4-block model grow 5-13x per interaction block."""
     rs = np.random.RandomState(seed)
     scale_factors = scale_factors or {}
     out = {}
     for name, shape, kind in param_spec(cfg):
         if kind == "dense":
-            w = rs.standard_normal(shape) / math.sqrt(shape[1])
+            w = rs.standard_normal(shape)
+            w = (_standardized(w, 1) if standardize else w) / math.sqrt(shape[1])
         elif kind == "eff":
-            w = rs.standard_normal(shape) / math.sqrt(shape[0] * shape[1])
+            w = rs.standard_normal(shape)
+            w = (_standardized(w, (0, 1)) if standardize else w) / math.sqrt(shape[0] * shape[1])
         elif kind == "emb":
             w = rs.uniform(-math.sqrt(3), math.sqrt(3), size=shape)
         elif kind == "freq":
@@ -137,6 +150,17 @@ def make_params(cfg, seed, scale_factors=None, dtype=torch.float64):
             raise ValueError(kind)
         out[name] = torch.tensor(np.asarray(w, dtype=np.float32).astype(np.float64), dtype=dtype)
     return out
+
+
+def direct_twin_params(cfg, seed, scale_factors=None, dtype=torch.float64):
+    """(cfg, params) of the `direct_forces=True` twin of a standardised model: every parameter the two share is the model's
+    own (`make_params(cfg, seed, standardize=True)`), the direct-force-only ones (force heads, `OutBlock_*_had`) come from
+    `make_params(cfg_direct, seed + 100, standardize=True)`.  The reference's scale-factor fit runs on such a twin: its `fit()`
+    raises on tensors that require grad, which the autograd-force model's activations do (fit_scaling.py:119)."""
+    cfg_d = dict(cfg, direct_forces=True)
+    params = make_params(cfg_d, seed + 100, scale_factors, dtype, standardize=True)
+    params.update(make_params(cfg, seed, scale_factors, dtype, standardize=True))
+    return cfg_d, params
 
 
 def load_scale_factors(path):

@@ -1,5 +1,7 @@
 """Shared by the BASELINE-size golden tests (tests/golden/fullsize.npz + fullsize_index.json, written by
-tests/golden/make_golden.py::golden_fullsize from the REFERENCE in float64): the four workloads and the index digest."""
+tests/golden/make_golden.py::golden_fullsize from the REFERENCE in float64): the four workloads and the index digest; and the
+well-conditioned 64-atom fixtures `t64f` / `q64f` (fullsize64.npz + scaling_fit64.json, ::golden_fullsize64 / ::golden_scaling64:
+standardised generator weights, scale factors fitted by the reference's own procedure on the molecule itself)."""
 import ast
 import hashlib
 import json
@@ -20,6 +22,25 @@ def load_fullsize():
     return dict(np.load(os.path.join(GOLDEN, "fullsize.npz")))
 
 
+FIT64 = {"t64f": "T", "q64f": "Q"}
+
+
+def load_fullsize64():
+    return dict(np.load(os.path.join(GOLDEN, "fullsize64.npz")))
+
+
+def load_fit64():
+    with open(os.path.join(GOLDEN, "scaling_fit64.json")) as f:
+        return json.load(f)
+
+
+def write_fit64(tag, path):
+    """The fitted factors of a fixture ("t64f" / "q64f") or of its direct-force twin ("T" / "Q") as a scale file."""
+    with open(path, "w") as f:
+        json.dump(dict(comment="tests/golden/scaling_fit64.json", **load_fit64()[FIT64.get(tag, tag)]["fitted"]), f)
+    return str(path)
+
+
 def load_digests():
     with open(os.path.join(GOLDEN, "fullsize_index.json")) as f:
         return json.load(f)
@@ -27,7 +48,7 @@ def load_digests():
 
 def dataset(tag):
     """The generated inputs of a fixture, from the seeded generator (the npz holds them too: asserted equal by the tests)."""
-    if tag in ("t64s", "q64s"):
+    if tag in ("t64s", "q64s", "t64f", "q64f"):
         m = make_molecule(64, 4000)
         return dict(N=np.array([64], np.int32), Z=m["Z"], R=m["R"], E=np.zeros(1, np.float32), F=np.zeros_like(m["R"]))
     if tag == "tB32" or tag == "idxB32.Q":
@@ -40,12 +61,15 @@ def dataset(tag):
 
 
 def triplets_only(tag):
-    return tag in ("t64s", "tB32", "idx32.T")
+    return tag in ("t64s", "t64f", "tB32", "idx32.T")
 
 
 def params_of(g, tag, dtype=torch.float32):
     cfg = ast.literal_eval(str(g[f"{tag}.cfg"]))
-    params = GO.make_params(cfg, int(g[f"{tag}.seed"]), GO.load_scale_factors(SCALE_FILE), dtype=dtype)
+    if tag in FIT64:
+        params = GO.make_params(cfg, int(g[f"{tag}.seed"]), load_fit64()[FIT64[tag]]["fitted"], dtype=dtype, standardize=True)
+    else:
+        params = GO.make_params(cfg, int(g[f"{tag}.seed"]), GO.load_scale_factors(SCALE_FILE), dtype=dtype)
     sc = float(g[f"{tag}.out_scale"])
     return cfg, {k: (v * sc if k.endswith(HEAD_KEYS) else v) for k, v in params.items()}
 

@@ -640,10 +640,21 @@ def _index_digest(idx, triplets_only):
             for k, v in sorted(can.items())}
 
 
-def run_fullsize(cfg, seed, ds, tag, out, digests, with_grads=False):
+def _act_max_hooks(model, store):
+    """Forward hooks (returning None) on the interaction blocks: max|h|, max|m| leaving each block -> store[i] = [h, m]."""
+    def hook(i):
+        def fn(mod, args, output):
+            store[i] = [float(output[0].detach().abs().max()), float(output[1].detach().abs().max())]
+        return fn
+    return [blk.register_forward_hook(hook(i)) for i, blk in enumerate(model.int_blocks)]
+
+
+def run_fullsize(cfg, seed, ds, tag, out, digests, with_grads=False, scale_file=SCALE_FILE, standardize=False, act_max=False):
     """Reference forward+force in float64 on a generated dataset `ds` (all its molecules in ONE batch); the output
     heads rescaled to mean|F| = 1 eV/A.  Only E, F, the head scale and the (seeded, regenerable) positions are stored;
-    the reference's index arrays go into `digests` as sizes + SHA-256 of their canonical form."""
+    the reference's index arrays go into `digests` as sizes + SHA-256 of their canonical form.
+    act_max: also `<tag>.act_max` / `.act_max32` (num_blocks, 2) = max|h|, max|m| leaving every interaction block in the
+    float64 / float32 run."""
     import time
     to = cfg["triplets_only"]
     t0 = time.time()
@@ -651,11 +662,11 @@ def run_fullsize(cfg, seed, ds, tag, out, digests, with_grads=False):
     batch = dc[list(range(len(ds["N"])))]
     t_idx = time.time() - t0
     digests[tag] = _index_digest({k: batch[k].numpy() for k in dc.index_keys}, to)
-    sf = GO.load_scale_factors(SCALE_FILE)
-    params = GO.make_params(cfg, seed, sf, dtype=torch.float64)
+    sf = GO.load_scale_factors(scale_file)
+    params = GO.make_params(cfg, seed, sf, dtype=torch.float64, standardize=standardize)
     inputs = {k: v for k, v in batch.items() if k not in ("E", "F")}
     inputs["R"] = inputs["R"].double()
-    model = GemNet(**cfg, scale_file=SCALE_FILE).double()
+    model = GemNet(**cfg, scale_file=scale_file).double()
     model.load_state_dict(GO.expand_to_reference_state_dict(params), strict=True)
     model.train()
     t0 = time.time()
@@ -664,7 +675,11 @@ def run_fullsize(cfg, seed, ds, tag, out, digests, with_grads=False):
     scale = 1.0 / float(F0.detach().abs().mean())
     del F0
     model.load_state_dict(GO.expand_to_reference_state_dict(scale_heads(params, scale)), strict=True)
+    acts, acts32 = {}, {}
+    hooks = _act_max_hooks(model, acts) if act_max else []
     E, F = model(dict(inputs))
+    for h in hooks:
+        h.remove()
     out[f"{tag}.seed"], out[f"{tag}.cfg"], out[f"{tag}.out_scale"] = np.array(seed), np.array(repr(cfg)), np.array(scale)
     out[f"{tag}.N"], out[f"{tag}.Z"], out[f"{tag}.R"] = ds["N"], ds["Z"], ds["R"]
     out[f"{tag}.E"], out[f"{tag}.F"] = E.detach().numpy(), F.detach().numpy()
@@ -681,14 +696,20 @@ def run_fullsize(cfg, seed, ds, tag, out, digests, with_grads=False):
         model.zero_grad(set_to_none=True)
     # the reference's OWN float32 path (its default dtype) on the same weights and inputs: what "the reference PyTorch CPU
     # path" returns, and how far fp32 rounding alone takes it from the float64 result on this fixture
-    model32 = GemNet(**cfg, scale_file=SCALE_FILE)
+    model32 = GemNet(**cfg, scale_file=scale_file)
     model32.load_state_dict(GO.expand_to_reference_state_dict({k: v.float() for k, v in scale_heads(params, scale).items()}),
                             strict=True)
     model32.train()
     in32 = dict(inputs)
     in32["R"] = in32["R"].float()
+    if act_max:
+        _act_max_hooks(model32, acts32)
     E32, F32 = model32(in32)
     out[f"{tag}.E32"], out[f"{tag}.F32"] = E32.detach().numpy(), F32.detach().numpy()
+    if act_max:
+        out[f"{tag}.act_max"] = np.array([acts[i] for i in range(cfg["num_blocks"])])
+        out[f"{tag}.act_max32"] = np.array([acts32[i] for i in range(cfg["num_blocks"])])
+        print(tag, "max|h|, max|m| leaving the interaction blocks (float64):", out[f"{tag}.act_max"].tolist(), flush=True)
     noise = float((F32.detach().double() - F.detach()).abs().mean())
     print(tag, "E", E.detach().numpy().ravel()[:3], "mean|F|", float(F.detach().abs().mean()), "out_scale", scale,
           {k: int(batch[k].shape[0]) for k in ("id_a", "id3_reduce_ca") + (() if to else ("id4_reduce_ca",))},
@@ -724,6 +745,99 @@ def golden_fullsize():
     print("fullsize.npz", len(out), "arrays; fullsize_index.json", len(digests), "digests")
 
 
+# ------------------------------------------- G9: well-conditioned 64-atom fixtures (standardised weights, fitted factors)
+FIT64 = (("T", True, 7, "t64f"), ("Q", False, 8, "q64f"))
+
+
+def _one64(seed=None):
+    """make_molecule(64, 4000) as a one-molecule dataset; with `seed`, training targets E ~ N(0, 1) (drawn first) and
+    F ~ N(0, 1) from RandomState(seed)."""
+    m64 = make_molecule(64, 4000)
+    E, F = np.zeros(1, np.float32), np.zeros_like(m64["R"])
+    if seed is not None:
+        rs = np.random.RandomState(seed)
+        E = rs.standard_normal(1).astype(np.float32)
+        F = rs.standard_normal(m64["R"].shape).astype(np.float32)
+    return dict(N=np.array([64], np.int32), Z=m64["Z"], R=m64["R"], E=E, F=F)
+
+
+def golden_scaling64():
+    """-> scaling_fit64.json: the scale factors of the published 4-block widths fitted by the REFERENCE GemNet / Trainer /
+    AutomaticFit (float64, as golden_scaling drives them) on ONE batch — the 64-atom molecule of t64s / q64s — for the
+    direct-force twin (GO.direct_twin_params) of the standardised-weight models of golden_fullsize64.  Names and floats only."""
+    import json
+    import tempfile
+    import time
+    from gemnet.model.layers.scaling import AutomaticFit
+    from gemnet.model.utils import write_json
+    from gemnet.training.trainer import Trainer
+    from gemnet.training.metrics import Metrics
+    result = {}
+    ds = _one64()
+    for tag, to, seed, _ in FIT64:
+        t0 = time.time()
+        cfg, params = GO.direct_twin_params(cfg_full(to, 4), seed)
+        dc = _MemContainer(dict(ds), 5.0, 10.0, to)
+        b = dc[[0]]
+        inputs = {k: v for k, v in b.items() if k not in ("E", "F")}
+        inputs["R"] = inputs["R"].double()
+        targets = {"E": b["E"].double(), "F": b["F"].double()}
+
+        def stream():
+            while True:
+                yield inputs, targets
+
+        with tempfile.TemporaryDirectory() as tmp:
+            scale_file = os.path.join(tmp, "scaling.json")
+            write_json(scale_file, {"comment": "golden"})
+            AutomaticFit.set2fitmode()
+            model = GemNet(**cfg, scale_file=scale_file).double()
+            model.load_state_dict(GO.expand_to_reference_state_dict(params), strict=True)
+            trainer = Trainer(model)
+            metrics = Metrics("train", trainer.tracked_metrics, None)
+            it = stream()
+            order = []
+            while not AutomaticFit.fitting_completed():
+                trainer.test_on_batch(it, metrics)
+                order.append(AutomaticFit.activeVar._name)
+                AutomaticFit.activeVar.fit()
+            AutomaticFit.fitting_mode = False
+            with open(scale_file) as f:
+                fitted = json.load(f)
+        fitted.pop("comment")
+        result[tag] = dict(fitted=fitted, order=order)
+        print(tag, len(fitted), f"factors in {time.time() - t0:.0f} s", fitted, flush=True)
+    with open(os.path.join(HERE, "scaling_fit64.json"), "w") as f:
+        json.dump(result, f, indent=1)
+
+
+def golden_fullsize64(tags=None):
+    """-> fullsize64.npz: `t64f` / `q64f`, the 64-atom molecule of t64s / q64s under the published 4-block configurations with
+    STANDARDISED generator weights (GO.make_params(standardize=True)) and the scale factors of scaling_fit64.json: reference
+    E, F (float64, heads rescaled to mean|F| = 1), its float32 E, F, the activation maxima leaving every interaction block in
+    both runs, and the training step (loss.backward() through the force) on targets drawn from RandomState(seed)."""
+    import json
+    import tempfile
+    import time
+    with open(os.path.join(HERE, "scaling_fit64.json")) as f:
+        fit = json.load(f)
+    path = os.path.join(HERE, "fullsize64.npz")
+    out = dict(np.load(path)) if tags and os.path.exists(path) else {}
+    for name, to, seed, tag in FIT64:
+        if tags and tag not in tags:
+            continue
+        t0 = time.time()
+        with tempfile.TemporaryDirectory() as tmp:
+            scale_file = os.path.join(tmp, "scaling.json")
+            with open(scale_file, "w") as f:
+                json.dump(dict(comment="scaling_fit64.json", **fit[name]["fitted"]), f)
+            run_fullsize(cfg_full(to, 4), seed, _one64(seed), tag, out, {}, with_grads=True, scale_file=scale_file,
+                         standardize=True, act_max=True)
+        print(tag, f"{time.time() - t0:.0f} s", flush=True)
+    np.savez_compressed(path, **out)
+    print("fullsize64.npz", len(out), "arrays")
+
+
 # ----------------------------------------------------- G8: periodic cluster-oracle results (no reference code involved)
 PBC_CASES = ("cubic1", "bcc", "bcc_pert", "thin", "skewed", "skewed_lh")
 
@@ -757,7 +871,7 @@ def golden_pbc_cases():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["basis", "indices", "models", "models2", "keys", "trainer", "scaling", "tfnames", "fullsize", "pbc"]
+    which = sys.argv[1:] or ["basis", "indices", "models", "models2", "keys", "trainer", "scaling", "tfnames", "fullsize", "scaling64", "fullsize64", "pbc"]
     if "tfnames" in which:
         golden_tfnames()
     if "scaling" in which:
@@ -776,5 +890,9 @@ if __name__ == "__main__":
         golden_keys()
     if "fullsize" in which:
         golden_fullsize()
+    if "scaling64" in which:
+        golden_scaling64()
+    if "fullsize64" in which:
+        golden_fullsize64([w for w in which if w in ("t64f", "q64f")])
     if "pbc" in which:
         golden_pbc_cases()

@@ -4,6 +4,9 @@ rescaled to mean|F| = 1 eV/A so that the north-star bar — force MAE <= 1e-5 eV
   t64s / q64s  one 64-atom molecule (configs[4]'s molecule size; 2.04 M quadruplets), GemNet-T / GemNet-Q
   tB32         the 32 x 32-atom GemNet-T batch of configs[1] — the headline workload of bench.py, rank 0
   qB4          a 4 x 32-atom GemNet-Q batch (configs[2])
+  t64f / q64f  the same 64-atom molecule with standardised generator weights and scale factors fitted by the reference's own
+               procedure on it (tests/golden/fullsize64.npz, scaling_fit64.json): activations stay below 25 through all four
+               blocks, so the default fp16-plane arithmetic runs without its fall-back and the bar needs no LOOSE entry
 Inputs come from the seeded generator through the product's own DataContainer (host index builder) AND through the device
 index builder (csrc/index_gpu.hip); both builders are also checked bit-exactly against the reference's index arrays
 (sizes + SHA-256 of the canonical form, tests/golden/fullsize_index.json; training/data_container.py:244-489)."""
@@ -12,7 +15,10 @@ import pytest
 import torch
 
 from conftest import SCALE_FILE, check_grad_probes
-from fullsize_common import dataset, digest, load_digests, load_fullsize, params_of, triplets_only
+import warnings
+
+from fullsize_common import (FIT64, dataset, digest, load_digests, load_fullsize, load_fullsize64, params_of, triplets_only,
+                             write_fit64)
 from oracle import gemnet_oracle as GO
 from gemnet_pytorch_amd.model.gemnet import GemNet
 from gemnet_pytorch_amd.training.data_container import DataContainer
@@ -68,6 +74,129 @@ def test_energy_force_parity_at_baseline_sizes(g, tag, builder):
     else:
         assert f_mae <= FORCE_TOL
     assert e_err <= 2e-5 * max(1.0, float(np.abs(Eref).max()))
+
+
+# ------------------------------------------------------------------ the conditioned 64-atom fixtures t64f / q64f
+@pytest.fixture(scope="module")
+def g64():
+    return load_fullsize64()
+
+
+@pytest.fixture(scope="module")
+def inputs64():
+    """Index arrays of the one molecule, built once per (tag, builder) and left unchanged."""
+    cache = {}
+
+    def get(tag, builder="host"):
+        if (tag, builder) not in cache:
+            cache[tag, builder] = _inputs(tag, builder)
+        return dict(cache[tag, builder])
+    return get
+
+
+def _model64(g64, tag, tmp_path):
+    cfg, params = params_of(g64, tag)
+    model = GemNet(**cfg, scale_file=write_fit64(tag, tmp_path / "scaling.json"))
+    model.load_state_dict(GO.expand_to_reference_state_dict(params), strict=True)
+    return model.to(DEV)
+
+
+def _check64(g64, tag, what, model, inputs):
+    """E / F of one pass under `warnings -> error`: the force bar is max(1e-5, the reference's own float32 error on the fixture),
+    the energy bar 2e-5 max(1, max|E_ref|); no fall-back from the arithmetic the pass started in."""
+    before = model.matmul_precision
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        E, F = model(inputs)
+    assert model.matmul_precision is before
+    Eref, Fref = g64[f"{tag}.E"], g64[f"{tag}.F"]
+    assert tuple(F.shape) == Fref.shape and abs(float(np.abs(Fref).mean()) - 1.0) < 1e-9
+    f_mae = float(np.abs(F.detach().cpu().numpy() - Fref).mean())
+    f_max = float(np.abs(F.detach().cpu().numpy() - Fref).max())
+    e_err = float(np.abs(E.detach().cpu().numpy().reshape(Eref.shape) - Eref).max())
+    ref32 = float(np.abs(g64[f"{tag}.F32"].astype(np.float64) - Fref).mean())
+    bar = max(FORCE_TOL, ref32)
+    print(f"{tag} [{what}]: force MAE {f_mae:.3e} eV/A (max {f_max:.3e}) at mean|F_ref| = 1, bar {bar:.3e} (the reference's "
+          f"float32 path vs its float64: {ref32:.3e}); energy err {e_err:.3e} (max|E_ref| {float(np.abs(Eref).max()):.3f})")
+    assert np.isfinite(f_mae) and f_mae <= bar
+    assert e_err <= 2e-5 * max(1.0, float(np.abs(Eref).max()))
+    return f_mae
+
+
+@pytest.mark.parametrize("builder", ["host", "device"])
+@pytest.mark.parametrize("tag", ["t64f", "q64f"])
+def test_energy_force_parity_at_64_atoms_in_the_default_arithmetic(g64, inputs64, tag, builder, tmp_path):
+    """configs[4]'s molecule size on the conditioned fixtures, default arithmetic (fp16 planes), both index builders: no
+    RuntimeWarning, no fall-back to the bf16 planes, the bar without a LOOSE entry."""
+    assert tag not in LOOSE
+    model = _model64(g64, tag, tmp_path).eval()
+    assert model.matmul_precision is None
+    _check64(g64, tag, f"{builder} indices, default arithmetic", model, inputs64(tag, builder))
+    assert model.matmul_precision is None
+
+
+@pytest.mark.parametrize("mode", ["f32", "split6", "h3", "h3-row"])
+@pytest.mark.parametrize("tag", ["t64f", "q64f"])
+def test_arithmetic_modes_at_64_atoms(g64, inputs64, tag, mode, tmp_path, monkeypatch):
+    """The same fixtures with the Dense stacks on the f32 MFMA, on six bf16-plane products, on the fp16 planes and on the
+    fp16 planes under a fresh row scale per GEMM (the row-resident layout, csrc/chain4.hip): every mode under the same bar."""
+    from gemnet_pytorch_amd import kernels as K
+    monkeypatch.setattr(K, "DEFAULT_CHAIN_MODE", mode.split("-")[0])
+    monkeypatch.setattr(K, "CHAIN_LAYOUT", "row" if mode == "h3-row" else "tall")
+    model = _model64(g64, tag, tmp_path).eval()
+    _check64(g64, tag, mode, model, inputs64(tag))
+    assert model.matmul_precision is None
+
+
+@pytest.mark.parametrize("tag", ["t64f", "q64f"])
+def test_activation_maxima_at_64_atoms(g64, inputs64, tag, tmp_path):
+    """max|h| and max|m| leaving each of the four interaction blocks on the device (default arithmetic) against the reference's
+    float64 run: within 8x the deviation of the reference's own float32 run of the same number, floor 1e-6 (float32
+    resolution).  Pins intermediates of the 4-block model, which E and F see only through the output heads."""
+    model = _model64(g64, tag, tmp_path).eval()
+    got = {}
+    hooks = [blk.register_forward_hook(
+        lambda mod, args, out, i=i: got.__setitem__(i, [float(out[0].detach().abs().max()), float(out[1].detach().abs().max())]))
+        for i, blk in enumerate(model.int_blocks)]
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        model(inputs64(tag))
+    for h in hooks:
+        h.remove()
+    assert model.matmul_precision is None and sorted(got) == [0, 1, 2, 3]
+    ref, ref32 = g64[f"{tag}.act_max"], g64[f"{tag}.act_max32"]
+    dev = np.abs(np.array([got[i] for i in range(4)]) - ref) / ref
+    bar = np.maximum(1e-6, 8 * np.abs(ref32 - ref) / ref)
+    print(f"{tag}: max|h|, max|m| leaving the interaction blocks {[got[i] for i in range(4)]}; relative deviation from the float64 "
+          f"reference {dev.tolist()}, bars {bar.tolist()}")
+    assert (dev <= bar).all(), (dev / bar).tolist()
+
+
+@pytest.mark.parametrize("tag", ["t64f", "q64f"])
+def test_training_gradients_at_64_atoms(g64, inputs64, tag, tmp_path):
+    """test_training_gradients_at_baseline_batch_sizes on the 64-atom molecule (2.04 M quadruplets in one molecule): loss (2e-5),
+    every parameter's gradient norm and four +-1 probe projections (2e-3 GemNet-T, 4e-3 GemNet-Q) against the reference's float64
+    `loss.backward()` through the force."""
+    if f"{tag}.grad_names" not in g64:
+        pytest.fail(f"{tag}: the fixture holds no gradients")
+    model = _model64(g64, tag, tmp_path).train()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        E, F = model(inputs64(tag))
+    assert model.matmul_precision is None
+    loss = GO.training_loss(E[:, :1], F, torch.tensor(g64[f"{tag}.Et"], device=DEV), torch.tensor(g64[f"{tag}.Ft"], device=DEV))
+    print(f"{tag}: loss {loss.item():.6f} (reference {float(g64[f'{tag}.loss']):.6f})")
+    np.testing.assert_allclose(loss.item(), float(g64[f"{tag}.loss"]), rtol=2e-5)
+    loss.backward()
+    named = dict(model.named_parameters())
+    names = [str(n) for n in g64[f"{tag}.grad_names"]]
+    norms = np.array([0.0 if named[n].grad is None else float(named[n].grad.norm()) for n in names])
+    ref = g64[f"{tag}.grad_norms"]
+    rtol = 4e-3 if tag == "q64f" else 2e-3
+    print(f"{tag}: worst gradient-norm deviation {float((np.abs(norms - ref) / np.maximum(ref, 1e-30)).max()):.2e} (bar {rtol:g})")
+    np.testing.assert_allclose(norms, ref, rtol=rtol, atol=1e-6 * float(ref.max()))
+    worst = check_grad_probes(g64, tag, {n: named[n].grad for n in names}, rtol=rtol)
+    print(f"{tag}: {len(names)} parameter gradients, worst probe error / ({rtol:g} ||g_ref||) = {worst:.3f}")
 
 
 @pytest.mark.parametrize("tag", ["t64s", "q64s", "tB32", "qB4", "idx32.T", "idx32.Q", "idxB32.Q"])
