@@ -62,6 +62,42 @@ __global__ __launch_bounds__(THREADS) void direct_force_kernel(const float* __re
   if (live && g < 3) F[row * 3 + g] = g == 0 ? fx : (g == 1 ? fy : fz);
 }
 
+// The adjoint of the head (gn_direct_force_bwd_f32): d/dterms[k] is the same (E,T) array for every k,
+//   h[e,t] = < gF[id_a[e],t,:], V_e / |V_e| >,   g[e,t] = h[e,t]  or, coupled,  (h[e,t] + h[id_swap[e],t]) / 2.
+// Gather form: one thread owns one (e,t), reads the cotangent row of the edge's target atom (and of its partner's), and writes
+// g[e,t] exactly once.  No atomics, no LDS; an edge's result depends on itself and its partner only, so rows are bit-reproducible
+// and unchanged by pad edges appended behind the list.  h is ONE inlined routine with its contraction pinned by explicit fmaf, used
+// for the edge and for its partner: the two threads of a pair add the same two numbers, so g[e] == g[id_swap[e]] bit for bit (the
+// adjoint's form of "coupled forces sum to zero").  No index becomes an address: a partner outside [0, E) is the edge itself (as in
+// the forward; with an involution this is the exact transpose), a target atom outside [0, n_atoms) contributes h = 0.
+__device__ __forceinline__ float edge_cotangent(const float* __restrict__ gF, const float* __restrict__ V,
+                                                const int32_t* __restrict__ id_a, const int64_t e, const int t, const int T,
+                                                const int64_t n_atoms) {
+  const int64_t a = id_a[e];
+  if (a < 0 || a >= n_atoms) return 0.f;
+  const float vx = V[3 * e], vy = V[3 * e + 1], vz = V[3 * e + 2];
+  const float d = sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
+  const float* __restrict__ row = gF + (a * T + t) * 3;
+  return fmaf(row[2], vz / d, fmaf(row[1], vy / d, row[0] * (vx / d)));
+}
+
+__global__ __launch_bounds__(THREADS) void direct_force_bwd_kernel(const float* __restrict__ gF, const float* __restrict__ V,
+                                                                   const int32_t* __restrict__ id_swap,
+                                                                   const int32_t* __restrict__ id_a, float* __restrict__ g,
+                                                                   const int64_t n_atoms, const int64_t E, const int T) {
+  const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;      // i = e * T + t
+  if (i >= E * T) return;
+  const int64_t e = i / T;
+  const int t = (int)(i - e * T);
+  float h = edge_cotangent(gF, V, id_a, e, t, T, n_atoms);
+  if (id_swap) {
+    int64_t s = id_swap[e];
+    if (s < 0 || s >= E) s = e;
+    h = 0.5f * (h + edge_cotangent(gF, V, id_a, s, t, T, n_atoms));
+  }
+  g[i] = h;
+}
+
 }  // namespace
 
 extern "C" int gn_direct_force_f32(const float* terms, const float* V, const int32_t* id_swap, const int32_t* perm,
@@ -76,6 +112,17 @@ extern "C" int gn_direct_force_f32(const float* terms, const float* V, const int
   if (blocks >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(direct_force_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), terms, V,
                      id_swap, perm, seg_off, F, n_rows, n_edges, K, T);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_direct_force_bwd_f32(const float* gF, const float* V, const int32_t* id_swap, const int32_t* id_a, float* g,
+                                       int64_t n_atoms, int64_t n_edges, int T, void* stream) {
+  if (T < 1 || T > GN_DIRECT_FORCE_MAX_TARGETS || n_edges < 0 || n_edges >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+  if (n_edges == 0) return 0;
+  const int64_t blocks = (n_edges * T + THREADS - 1) / THREADS;      // < 2^26
+  hipLaunchKernelGGL(direct_force_bwd_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), gF, V,
+                     id_swap, id_a, g, n_atoms, n_edges, T);
   GN_LAUNCH_CHECK();
   return 0;
 }

@@ -944,6 +944,29 @@ def direct_force(terms, V, id_swap, perm, seg_off, n_atoms, out=None):
     return out
 
 
+def direct_force_bwd(gF, V, id_swap, id_a, n_atoms, out=None):
+    """-> g (E, T): the adjoint of `direct_force` w.r.t. every one of its K term planes, in one launch (gn_direct_force_bwd_f32).
+    gF (n_atoms, T, 3): the cotangent of F; V (E,3): edge vectors, not normalised; id_swap (E) int32 or None (uncoupled); id_a (E)
+    int32: the target atom of every edge.  `out`: written in place (every element is written)."""
+    require_device(gF, V, id_a)
+    gF, V = _f32c(gF), _f32c(V)
+    if gF.dim() != 3 or gF.shape[0] != int(n_atoms) or gF.shape[2] != 3 or V.dim() != 2 or V.shape[1] != 3:
+        raise ValueError(f"gF (n_atoms,T,3) and V (E,3) expected; got {tuple(gF.shape)} and {tuple(V.shape)}")
+    E, T = int(V.shape[0]), int(gF.shape[1])
+    for t in (id_swap, id_a):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise TypeError("id_swap and id_a must be contiguous int32")
+    if id_a.shape[0] != E or (id_swap is not None and id_swap.shape[0] != E):
+        raise ValueError("index arrays do not fit E")
+    if out is None:
+        out = torch.empty((E, T), device=V.device, dtype=torch.float32)
+    elif out.shape != (E, T) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 (E, T) tensor")
+    check(_lib.load().gn_direct_force_bwd_f32(ptr(gF), ptr(V), ptr(id_swap), ptr(id_a), ptr(out), int(n_atoms), E, T, stream()),
+          "gn_direct_force_bwd_f32")
+    return out
+
+
 class ChainProgram:
     """A program for gn_chain_f32: ops over the three LDS slots of a row tile (see include/gemnet_hip.h).
     Operands named `mul/res/res2` are either an int (LDS slot) or a tensor (global (M,N))."""

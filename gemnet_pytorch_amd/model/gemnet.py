@@ -505,8 +505,10 @@ class GemNet(torch.nn.Module):
         """E, F as the reference's `GemNet.forward` (gemnet.py:453-615).
         Periodic batches (`cell` (B,3,3) + `cell_offsets` (E,3), pbc.py; GemNet-T, eval-mode forces by autograd): the edge
         vectors carry the image shift; `stress=True` returns (E, F, S) with S (B,3,3) = dE/d(strain) / |det cell| (eV/A^3).
-        A direct-force model (`direct_forces=True`) serves periodic batches with `periodic_direct_forces = True` (opt-in, inference
-        only): (E, F) with F (A,1,3) as on molecules, no autograd, no stress (`stress=True` raises); without the switch it raises.
+        A direct-force model (`direct_forces=True`) serves periodic batches with `periodic_direct_forces = True` (opt-in): (E, F)
+        with F (A,1,3) as on molecules, no stress (`stress=True` raises); without the switch it raises.  Eval mode: no autograd.
+        Training mode needs `periodic_training = True` as well (else it raises) and returns (E, F) with a first-order autograd
+        graph to the parameters (`_forward_periodic_direct_train`).
         With `periodic_training = True` a call that builds the second-order force graph (training mode with grad enabled, or
         `force_graph = True`) returns the same outputs with an autograd graph to the parameters; without it that call raises.
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
@@ -629,7 +631,10 @@ class GemNet(torch.nn.Module):
         t2 = (bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
               and (not R.is_cuda or self._train2_widths_ok()))
         if cell is not None and self.direct_forces:
-            return self._forward_periodic_direct(R, plan, cell)      # (inference only: _check_periodic turned the rest away)
+            # (training mode: `periodic_training` is on — _check_periodic turned the rest away; eval mode never looks at it)
+            if self.training:
+                return self._forward_periodic_direct_train(R, plan, cell)
+            return self._forward_periodic_direct(R, plan, cell)
         if cell is not None:
             if graph and not getattr(self, "periodic_training", False):
                 raise NotImplementedError("periodic cells: forces by autograd on the first-order (eval) path only; training "
@@ -688,7 +693,7 @@ class GemNet(torch.nn.Module):
         if self.direct_forces:
             if not getattr(self, "periodic_direct_forces", False):
                 raise NotImplementedError("periodic cells: forces by autograd only, not direct_forces")
-            if self.training:
+            if self.training and not getattr(self, "periodic_training", False):
                 raise NotImplementedError("periodic cells: direct-force periodic batches are inference only (model.eval())")
             if stress:
                 raise NotImplementedError("periodic cells: a direct-force model has no stress (its forces are not the "
@@ -729,6 +734,31 @@ class GemNet(torch.nn.Module):
                 ops.train2(False, None), ops.chain_mode(self.matmul_precision), ops.position_graph(False):
             E_mol, terms, _ = self._energy(R.detach(), plan, V=V, force_terms=True)
             F = pbc.direct_forces(torch.stack(terms), V, plan, self.forces_coupled)
+        return E_mol, F
+
+    def _forward_periodic_direct_train(self, R, plan, cell):
+        """E, F (A,1,3) of a periodic batch from a direct-force model in training mode (`periodic_direct_forces` and
+        `periodic_training`), both with an autograd graph to the parameters.  Nothing is differentiated twice: the training
+        step of a direct-force model is one first-order backward.  Two forms with parameter gradients:
+          * widths the split-operand chain kernel takes (`_train2_widths_ok`; any width on the host emulation), arithmetic not
+            "f32": the Dense stacks as single-launch chain programs with trainable weights (ops_train.stack under
+            `ops.train2`: its first sweep and first adjoint only, the weight gradients through the grouped queue of the train
+            step) — 4 x fewer launches than one GEMM per Dense;
+          * other widths, `matmul_precision = "f32"`, GEMNET_TRAIN2=0: the fused single-launch layers of the molecular
+            direct-force training branch (`fused_first_order(True)`), one launch per Dense and per weight gradient.
+        `force_graph = True` selects the composite closure instead (ATen on V: the A/B reference, as for molecules).  V is a
+        constant: positions and cell never join an autograd graph.  The force head is `pbc.direct_forces_train`:
+        `_forward_periodic_direct`'s one launch, and one launch of its adjoint in the backward.  Under torch.no_grad() the same
+        pass records no graph; the constant-weight inference caches are not consulted."""
+        from .. import pbc
+        V = pbc.edge_vectors(R, plan, cell)
+        mode = self.matmul_precision or K_chain_mode()
+        t2 = (not self.force_graph and ops.USE_TRAIN2 and mode != "f32" and (not R.is_cuda or self._train2_widths_ok()))
+        with ops.weight_cache(self._wcache), ops.fused_first_order(not self.force_graph and not t2), ops.param_grads(True), \
+                ops.train2(t2, self._packs if (t2 and R.is_cuda) else None), ops.chain_mode(self.matmul_precision), \
+                ops.position_graph(False):
+            E_mol, terms, _ = self._energy(R.detach(), plan, V=V, force_terms=True)
+            F = pbc.direct_forces_train(terms, V, plan, self.forces_coupled)
         return E_mol, F
 
     def _forward_periodic_train(self, R, plan, cell, t2):

@@ -11,7 +11,9 @@ Input keys of a periodic batch: `cell` (B,3,3), rows = lattice vectors; `cell_of
 V_e = R[a] - (R[c] + cell_offsets[e] @ cell[b(e)]).  The stress is dE/d(strain) / |det cell| (ASE's sign convention, eV/A^3).
 
 A direct-force model (`GemNet(direct_forces=True)` with `model.periodic_direct_forces = True`) runs the same geometry without
-autograd and ends in `direct_forces` below (csrc/direct_force.hip): E, F (A,1,3), no stress.
+autograd and ends in `direct_forces` below (csrc/direct_force.hip): E, F (A,1,3), no stress.  In training mode (with
+`model.periodic_training = True` as well) the same pass keeps its graph to the parameters and ends in `direct_forces_train`,
+whose backward is the adjoint kernel of the head: one first-order `loss.backward()` (training.periodic.PeriodicTrainStep).
 
 The builder reads two sizes back per call.  For MD — a new list every step — the same list is built without a read-back inside a
 captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
@@ -128,7 +130,8 @@ def edge_vectors(R, plan, cell):
 
 
 class _EdgeBasisVec(torch.autograd.Function):
-    """V -> D, rbf, rad (one launch); adjoint: dE/dV per edge (first order, weights constant)."""
+    """V -> D, rbf, rad (one launch); adjoint: dE/dV per edge (first order), and — while parameter gradients are on
+    (ops.param_grads: direct-force training) — the gradient of the Bessel frequencies, as ops._EdgeBasis forms it."""
 
     @staticmethod
     def forward(ctx, V, freq, z, nrm, cutoff, p):
@@ -140,22 +143,27 @@ class _EdgeBasisVec(torch.autograd.Function):
         fr = freq.detach().float().contiguous()
         check(_lib.load().gn_edge_basis_vec_fwd_f32(ptr(V), ptr(fr), ptr(z), ptr(nrm), ptr(D), ptr(rbf), ptr(rad), E, NR, S,
                                                     cutoff, p, stream()), "gn_edge_basis_vec_fwd_f32")
-        ctx.save_for_backward(V, fr, z, nrm)
+        ctx.save_for_backward(V, fr, z, nrm, D)
         ctx.cfg = (cutoff, p)
         return D, rbf, rad
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gD, g_rbf, g_rad):
-        V, fr, z, nrm = ctx.saved_tensors
+        from . import ops
+        V, fr, z, nrm, D = ctx.saved_tensors
         cutoff, p = ctx.cfg
         S, NR = z.shape
         E = V.shape[0]
         c = lambda t: None if t is None else t.float().contiguous()
-        W = torch.empty((E, 3), device=V.device, dtype=torch.float32)
-        check(_lib.load().gn_edge_basis_vec_bwd_f32(ptr(c(gD)), ptr(c(g_rbf)), ptr(c(g_rad)), ptr(V), ptr(fr), ptr(z), ptr(nrm),
-                                                    ptr(W), E, NR, S, cutoff, p, stream()), "gn_edge_basis_vec_bwd_f32")
-        return W, None, None, None, None, None
+        W = gf = None
+        if ctx.needs_input_grad[0]:
+            W = torch.empty((E, 3), device=V.device, dtype=torch.float32)
+            check(_lib.load().gn_edge_basis_vec_bwd_f32(ptr(c(gD)), ptr(c(g_rbf)), ptr(c(g_rad)), ptr(V), ptr(fr), ptr(z), ptr(nrm),
+                                                        ptr(W), E, NR, S, cutoff, p, stream()), "gn_edge_basis_vec_bwd_f32")
+        if ctx.needs_input_grad[1] and ops._PARAM_GRADS and g_rbf is not None:
+            gf = (g_rbf * K.bessel_rbf(D, fr, cutoff, p, 0, 1)).sum(dim=0)
+        return W, gf, None, None, None, None
 
 
 def edge_basis(V, freq, z, nrm, cutoff, p):
@@ -208,6 +216,40 @@ def direct_forces(terms, V, plan, coupled):
     undirected edge first (`plan.id_swap` pairs an edge with its negated-offset partner).  Inference only: no autograd."""
     perm, seg = plan.id_a.csr
     return K.direct_force(terms.detach(), V.detach(), plan.id_swap.idx32 if coupled else None, perm, seg, plan.n_atoms)
+
+
+class _DirectForces(torch.autograd.Function):
+    """The K (E,T) force terms of the output blocks -> F (A,T,3): `direct_forces` with a graph to the terms.  V, the coupling and
+    the CSR are constants (positions and cell never join an autograd graph).  Backward: ONE launch of the head's adjoint
+    (gn_direct_force_bwd_f32); d/dterms[k] is the same (E,T) array for every k and the SAME tensor is returned K times.  That is
+    safe here: term k has exactly one consumer (this Function), so the engine hands the tensor straight to the backward of the
+    Dense that produced the term (ops._FusedDense / ops._MM) without accumulating into it, and those only read their cotangent —
+    the running sums of ops.accumulate_gradient are written into buffers of their own (GradSink.target), the weight-gradient
+    queue reads, and AccumulateGrad adds into the flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, V, plan, coupled, *terms):
+        ctx.set_materialize_grads(False)
+        perm, seg = plan.id_a.csr
+        ctx.swap = plan.id_swap.idx32 if coupled else None
+        ctx.plan, ctx.n_terms = plan, len(terms)
+        ctx.save_for_backward(V)
+        return K.direct_force(torch.stack([t.detach() for t in terms]), V.detach(), ctx.swap, perm, seg, plan.n_atoms)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF):
+        if gF is None:
+            return (None,) * (3 + ctx.n_terms)
+        (V,) = ctx.saved_tensors
+        g = K.direct_force_bwd(gF, V, ctx.swap, ctx.plan.id_a.idx32, ctx.plan.n_atoms)
+        return (None, None, None) + (g,) * ctx.n_terms
+
+
+def direct_forces_train(terms_list, V, plan, coupled):
+    """F (A,T,3) of a direct-force model with an autograd graph to the K (E,T) tensors of `terms_list` (the force terms of the
+    output blocks): the forward is `direct_forces` on their stack, the backward one launch of its adjoint.  V gets no gradient."""
+    return _DirectForces.apply(V, plan, bool(coupled), *terms_list)
 
 
 def edge_structure(plan):

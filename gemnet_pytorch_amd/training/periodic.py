@@ -13,6 +13,14 @@ to the parameters).  Loss:
 with B the global structure count (all ranks); `targets["S"]` (B_local,3,3), dE/d(strain)/|det cell| in ASE's sign convention,
 is needed only when rho_stress > 0.  Eager steps, `capture()`, the fused optimizer, the range flag and `world_size > 1` are
 those of `TrainStep`.  A new neighbour list every training step (padded or in-graph-rebuilt lists) is not provided.
+
+A direct-force model (`GemNet(direct_forces=True)`, GemNet-dT) trains on the same batches: constructing the step opts the model
+in (`periodic_direct_forces` and `periodic_training`), the model returns (E, F (A,1,3)) from its first-order training layers (chain programs with
+trainable weights at the widths the chain kernel takes, else one launch per Dense) and the one-launch force head (`GemNet._forward_periodic_direct_train`, pbc.direct_forces_train), and the step is ONE first-order
+backward.  Such a model has no stress: `rho_stress > 0` raises at construction.
+
+    ts = PeriodicTrainStep(direct_model, rho_force=0.999, fused_optimizer=True)
+    loss = ts(inputs, dict(E=Et, F=Ft))
 """
 import torch
 
@@ -22,9 +30,14 @@ from .ddp import TrainStep
 class PeriodicTrainStep(TrainStep):
     def __init__(self, model, world_size=1, rho_force=0.999, grad_clip_max=10.0, optimizer=None, global_counts=None,
                  fused_optimizer=False, rho_stress=0.0):
+        if getattr(model, "direct_forces", False) and float(rho_stress) > 0:
+            raise ValueError("PeriodicTrainStep(rho_stress > 0): a direct-force model has no stress (its forces are not the "
+                             "gradient of its energy); train it with rho_stress = 0")
         super().__init__(model, world_size=world_size, rho_force=rho_force, grad_clip_max=grad_clip_max, optimizer=optimizer,
                          global_counts=global_counts, fused_optimizer=fused_optimizer)
         self.rho_stress = float(rho_stress)
+        if getattr(model, "direct_forces", False):
+            model.periodic_direct_forces = True
         model.periodic_training = True
         self._S = None
 
@@ -39,7 +52,10 @@ class PeriodicTrainStep(TrainStep):
         finally:
             inputs.pop("_range_flag", None)
         self._S = out[2] if want_S else None
-        return out[0], out[1]
+        E, F = out[0], out[1]
+        if F.dim() == 3:          # a direct-force model: (A,1,3), as TrainStep._outputs
+            F = F[:, 0]
+        return E, F
 
     def loss(self, E, F, targets):
         B, A = self._counts(E.shape[0], F.shape[0], E.device)

@@ -827,6 +827,16 @@ int gn_pbc_force_stress_adj_f32(const float* gF, const float* gS, const float* V
 #define GN_DIRECT_FORCE_MAX_TARGETS 8
 int gn_direct_force_f32(const float* terms, const float* V, const int32_t* id_swap, const int32_t* perm, const int32_t* seg_off,
                         float* F, int64_t n_atoms, int64_t n_edges, int K, int T, void* stream);
+/* The adjoint of gn_direct_force_f32 w.r.t. terms (training a direct-force model on periodic batches; additive, ABI 15).  gF
+ * (n_atoms,T,3): the cotangent of F; V, id_swap as above; id_a (E): the target atom of every edge.
+ *   h[e,t] = < gF[id_a[e],t,:], V_e / |V_e| >;   g[e,t] = h[e,t],  with id_swap:  (h[e,t] + h[id_swap[e],t]) / 2        g (E,T)
+ * d/dterms[k] = g for every k: ONE (E,T) array.  One thread per (e,t), no atomics; every element of g is written exactly once
+ * and depends on the edge and its partner only (bit-reproducible; unchanged by edges appended behind the list); with id_swap,
+ * g[e] == g[id_swap[e]] bit for bit.  An id_swap entry outside [0, E) makes the edge its own partner (with an involution the
+ * formula is the exact transpose of the forward), an id_a entry outside [0, n_atoms) contributes h = 0.  T outside
+ * 1..GN_DIRECT_FORCE_MAX_TARGETS or n_edges >= 2^31: hipErrorInvalidValue; n_edges = 0 returns 0 without a launch. */
+int gn_direct_force_bwd_f32(const float* gF, const float* V, const int32_t* id_swap, const int32_t* id_a, float* g,
+                            int64_t n_atoms, int64_t n_edges, int T, void* stream);
 
 #ifdef __cplusplus
 }

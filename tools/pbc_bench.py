@@ -15,6 +15,10 @@ pass, forces from the edge head of csrc/direct_force.hip, no stress) on the same
 replay, MD step with `exact=False` and `exact=True` — beside the autograd-force model (`autograd_*_ms`) timed in the same process:
 the two alternate in rounds and the median round is reported (`*_rounds`: every round).  `--direct --eager-only` runs nothing but
 eager periodic direct-force calls (for a kernel trace: launches per call = calls of a kernel / (warmup + steps)).
+`--train --direct` times the TRAINING step of the direct-force model (PeriodicTrainStep on a `direct_forces=True` model: energy +
+force loss, ONE first-order backward, fused optimizer) beside the autograd-force PeriodicTrainStep of `--train` in the same
+process, in alternating rounds — `direct_train_eager_ms` / `autograd_train_eager_ms`, `*_train_graph_ms` (captured step), `*_rounds`;
+with `--eager-only` nothing but eager direct-force training steps (for a kernel trace).
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -107,6 +111,39 @@ def train_times(per, mol, args):
     return out
 
 
+def train_direct_times(per, args):
+    """Eager and captured training step of the direct-force model beside the autograd-force model's (energy + force + stress
+    loss, as `--train`), alternating in one process; optimizer included."""
+    from gemnet_pytorch_amd.training.periodic import PeriodicTrainStep
+    g = torch.Generator().manual_seed(2)
+    A = per["R"].shape[0]
+    targets = {"E": torch.randn(1, 1, generator=g).cuda(), "F": torch.randn(A, 3, generator=g).cuda(),
+               "S": 0.01 * torch.randn(1, 3, 3, generator=g).cuda()}
+    steps = {"direct": PeriodicTrainStep(make_model(args.cutoff, direct=True, coupled=args.coupled).to("cuda"), fused_optimizer=True),
+             "autograd": PeriodicTrainStep(make_model(args.cutoff).to("cuda"), rho_stress=0.01, fused_optimizer=True)}
+    inputs = {k: dict(per) for k in steps}
+    out = {"forces_coupled": bool(args.coupled), "autograd_rho_stress": 0.01}
+    if args.eager_only:
+        for _ in range(args.warmup + args.steps):
+            steps["direct"](inputs["direct"], targets)
+        torch.cuda.synchronize()
+        out["eager_steps"] = args.warmup + args.steps
+        return out
+
+    def record(tag, res):
+        for k, (med, rounds) in res.items():
+            out[f"{k}_train_{tag}_ms"], out[f"{k}_train_{tag}_rounds"] = med, rounds
+
+    fns = {k: (lambda ts=ts, k=k: ts(inputs[k], targets)) for k, ts in steps.items()}
+    record("eager", alternated(fns, args.steps, args.warmup))
+    for k, ts in steps.items():
+        ts.capture(inputs[k], targets)
+    record("graph", alternated(fns, args.steps, args.warmup))
+    for k, ts in steps.items():
+        out[f"{k}_train_loss"] = float(ts.last_loss)
+    return out
+
+
 def alternated(fns, steps, warmup, rounds=3):
     """{name: fn} timed in turns, `rounds` times each -> {name: (median ms, [ms of every round])}."""
     times = {k: [] for k in fns}
@@ -166,7 +203,7 @@ def main():
     ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
     ap.add_argument("--direct", action="store_true", help="time a direct-force model beside the autograd-force model")
     ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
-    ap.add_argument("--eager-only", action="store_true", help="--direct: only eager direct-force calls (for a kernel trace)")
+    ap.add_argument("--eager-only", action="store_true", help="--direct: only eager direct-force calls / training steps (for a kernel trace)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -190,7 +227,7 @@ def main():
            "triplets_periodic": int(idx["id3_reduce_ca"].shape[0]), "edges_molecular": int(mol["id_a"].shape[0]),
            "triplets_molecular": int(mol["id3_reduce_ca"].shape[0])}
     if args.train:
-        out.update(train_times(per, mol, args))
+        out.update(train_direct_times(per, args) if args.direct else train_times(per, mol, args))
         print(json.dumps(out))
         return
     if args.direct:
