@@ -42,8 +42,8 @@ def load():
             f"{LIB_PATH} not found: build the HIP extension first "
             "(python -c 'import __graft_entry__ as g; g.build()').  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    # (no setters: since ABI 13 the arithmetic of the angle-form kernels and the tuning of the wide chain layout are arguments
-    #  of each launch — kernels.ANG_F16_MASK / WIDE_TILE_ROWS / WIDE_STAGGER hold the read-only host configuration)
+    # (no setters: since ABI 13 the arithmetic of the angle-form kernels is an argument of each launch —
+    #  kernels.ANG_F16_MASK holds the read-only host configuration)
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

@@ -852,28 +852,14 @@ extern "C" int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* st
   if (args->M <= 0 || args->n_ops <= 0) return 0;
   if (args->n_ops > GN_CHAIN_MAX_OPS) return (int)hipErrorInvalidValue;
   if (args->M > (1 << 24)) return (int)hipErrorInvalidValue;
-  // wide layout: tile height (GN_CHAIN_WIDE_ROWS) and start-up stagger (GN_CHAIN_WIDE_STAGGER) ride in the upper bits of `nprod`
-  // — per call, no library state (ABI 13)
   const bool row = nprod == (GN_CHAIN_F16X2 | GN_CHAIN_ROW);
   if (row) nprod = GN_CHAIN_F16X2;
-  const bool wide = (nprod & 0xfff) == (GN_CHAIN_F16X2 | GN_CHAIN_WIDE);
-  const int wide_rows = ((nprod >> 12) & 0xf) * 8, wide_stagger = (nprod >> 16) & 0xffff;
-  if (!wide && (nprod & ~0xfff)) return (int)hipErrorInvalidValue;
-  if (wide && wide_rows > 48) return (int)hipErrorInvalidValue;
-  if (nprod != 1 && nprod != 3 && nprod != 6 && nprod != GN_CHAIN_F16X2 && !wide) return (int)hipErrorInvalidValue;
+  if (nprod & ~0xfff) return (int)hipErrorInvalidValue;
+  if (nprod != 1 && nprod != 3 && nprod != 6 && nprod != GN_CHAIN_F16X2) return (int)hipErrorInvalidValue;
   if (const int e = chain_split_check(args)) return e;
   const bool adj = chain_split_is_adj(args);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (row) return gn_chain_row_dispatch(args, adj, st);     // chain4.hip (its weights: GN_SPLIT_F16X2_ROW)
-  if (wide) {      // chain3.hip: 4 waves x 32 columns, two workgroups per CU — it has no parking slot
-    bool park = false;
-    for (int i = 0; i < args->n_ops; ++i) {
-      const gn_chain_op& o = args->ops[i];
-      park = park || o.slot == 2 || (o.kind == GN_OP_GEMM && (o.mul_slot == 2 || o.res_slot == 2 || o.res2_slot == 2));
-    }
-    if (!park) return gn_chain_wide_dispatch(args, adj, wide_rows, wide_stagger, st);
-    nprod = GN_CHAIN_F16X2;
-  }
   if (nprod == GN_CHAIN_F16X2) return dispatch_adj<2, true>(args, adj, st);
   if (nprod == 6) return dispatch_adj<3>(args, adj, st);
   if (nprod == 3) return dispatch_adj<2>(args, adj, st);

@@ -1,5 +1,5 @@
 // Shared pieces of the split-operand chain kernels (chain2.hip: 8 waves x 16 columns, one workgroup per CU;
-// chain3.hip: 4 waves x 32 columns, several workgroups per CU): plane formats, LDS swizzle constants, small helpers.
+// chain4.hip: a wave owns 16 rows and all columns): plane formats, LDS swizzle constants, small helpers.
 #pragma once
 #include "common.h"
 
@@ -10,9 +10,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 
-// chain3.hip: the wide layout of the two-plane fp16 arithmetic (argument checks are done by the caller, gn_chain_split_f32)
-int gn_chain_wide_dispatch(const gn_chain_args* args, bool adj, int forced_tile_rows, int stagger, hipStream_t st);
-// chain4.hip: the row-resident layout (a wave owns 16 rows and all columns; weights packed with GN_SPLIT_F16X2_ROW)
+// chain4.hip: the row-resident layout (a wave owns 16 rows and all columns; weights packed with GN_SPLIT_F16X2_ROW);
+// argument checks are done by the caller, gn_chain_split_f32
 int gn_chain_row_dispatch(const gn_chain_args* args, bool adj, hipStream_t st);
 
 namespace gn_split {

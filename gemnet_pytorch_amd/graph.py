@@ -98,11 +98,6 @@ def _native_csr():
     return _K.USE_NATIVE_CSR
 
 
-def _atom_blocks_on():
-    from . import kernels as _K
-    return _K.USE_ATOM_BLOCKS
-
-
 class SegmentPlan:
     """Triplets (or quadruplets) t with reduce row r(t) (sorted) and expand row g(t)."""
 
@@ -114,16 +109,6 @@ class SegmentPlan:
         self.n_expand = int(n_expand)
 
     @property
-    def expand_pos(self):
-        """Inverse of the expand CSR's permutation (int32): position of item t in the order of its expand row."""
-        if getattr(self, "_expand_pos", None) is None:
-            perm, _ = self.expand.csr
-            pos = torch.empty_like(perm)
-            pos[perm.long()] = torch.arange(perm.shape[0], device=perm.device, dtype=perm.dtype)
-            self._expand_pos = pos
-        return self._expand_pos
-
-    @property
     def seg_off(self):
         return self.reduce.csr[1]
 
@@ -131,28 +116,10 @@ class SegmentPlan:
         """Declare the quadruplet structure of GemNet-Q (data_container.py:331-397): r(t) — a reduce edge c -> a — and g(t)
         — an intermediate triplet a <- b <- d — of every entry end in the same target atom, and the expand rows are sorted by
         that atom.  `reduce_atom`: target atom of every reduce row (a RowIndex: its CSR groups the edges by atom);
-        `expand_atom`: target atom of every expand row (non-decreasing).  Enables the fused per-atom x-adjoint
-        (gn_bil_expand_atoms_ang_f32: no per-quadruplet rows in memory)."""
+        `expand_atom`: target atom of every expand row (non-decreasing).  Enables the row-stationary x-adjoint
+        (`row_grid`, gn_bil_expand_rows_ang_f32: no per-quadruplet rows in memory)."""
         self._ab_src = (reduce_atom, expand_atom, int(n_atoms))
         self._ab_max_rows = None if max_rows is None else int(max_rows)     # static bound of the reduce edges per atom (padded.py)
-        self._atom_blocks = None
-
-    @property
-    def atom_blocks(self):
-        """(a_perm int32 | None, a_seg int32 (A+1), j_off int32 (A+1), max_J) or None.  Built once per batch; the maximum is
-        read back from the device (a host sync: `GraphPlan.warm` does it outside of any capture)."""
-        src = getattr(self, "_ab_src", None)
-        if src is None:
-            return None
-        if self._atom_blocks is None:
-            reduce_atom, expand_atom, A = src
-            perm, seg = reduce_atom.csr
-            cnt = torch.bincount(expand_atom, minlength=A)
-            j_off = torch.zeros(A + 1, dtype=torch.int64, device=cnt.device)
-            torch.cumsum(cnt, 0, out=j_off[1:])
-            max_J = int(cnt.max().item()) if cnt.numel() else 0
-            self._atom_blocks = (perm, seg.to(torch.int32).contiguous(), j_off.to(torch.int32).contiguous(), max_J)
-        return self._atom_blocks
 
     ROW_TILE = int(os.environ.get("GEMNET_ROW_TILE", "64"))      # expand rows per wave of gn_bil_expand_rows_ang_f32 (32 | 64)
 
@@ -370,10 +337,9 @@ class GraphPlan:
             self.intm_ab = RowIndex(exp_ab, self.n_int, is_sorted=True)
             self.quad = SegmentPlan(inputs["id4_reduce_ca"], inputs["id4_expand_abd"], self.n_edges, self.n_intm)
             # reduce edge c -> a and intermediate triplet a <- b <- d share the target atom a; the latter are sorted by it
-            # (only the fused per-atom x-adjoint reads it — kernels.USE_ATOM_BLOCKS, off by default: no gather / bincount /
-            #  host read-back per batch for a structure nobody consumes)
+            # (only the row-stationary x-adjoint reads it: no gather per batch for a structure nobody consumes)
             from . import kernels as _K
-            if _K.USE_ATOM_BLOCKS or _K.USE_ROW_GRID:
+            if _K.USE_ROW_GRID:
                 self.quad.set_atom_blocks(self.id_a, i_a[exp_ab], self.n_atoms, max_rows=inputs.get("max_in_degree"))
             A = self.n_atoms
             self.quad_geom = {
@@ -444,8 +410,6 @@ class GraphPlan:
                 self._late_event = ev
             else:
                 self.trip.groups
-            if not self.triplets_only and _atom_blocks_on():
-                self.quad.atom_blocks
             if not self.triplets_only:
                 from . import kernels as _K
                 if _K.USE_ROW_GRID:

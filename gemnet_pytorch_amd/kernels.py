@@ -13,7 +13,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (GN_ANG_F16, GN_CHAIN_MAX_OPS, GN_CHAIN_ROW, GN_CHAIN_WIDE, GN_SPLIT_F16X2_ROW, GemmArgs, addr, check, ptr,
+from ._lib import (GN_ANG_F16, GN_CHAIN_MAX_OPS, GN_CHAIN_ROW, GN_SPLIT_F16X2_ROW, GemmArgs, addr, check, ptr,
                    require_device, stream)
 
 
@@ -515,28 +515,15 @@ def bil_reduce(Y, x, sp):
     return Sm
 
 
-# The fused per-atom x-adjoint of the tensor basis (gn_bil_expand_atoms_ang_f32: one workgroup per target atom sums the atom's
-# expand rows in LDS, edge by edge — no 1.15 GB of per-quadruplet rows written and read back).  Exact and deterministic
-# (tests/test_gpu_kernels.py), but measured SLOWER than the two-pass form on MI355X (profiles/r4_q_atom_blocks.txt: the
-# bil_reduce_t family of a GemNet-Q step 3.39-3.54 ms against 3.18 ms): one workgroup per CU (its LDS holds the atom's rows)
-# walking ~18 edges behind a barrier each cannot hide what 20 independent waves per CU hide in the two-pass kernels.  Off by
-# default; GEMNET_ATOM_BLOCKS=1 selects it.
-USE_ATOM_BLOCKS = os.environ.get("GEMNET_ATOM_BLOCKS", "0") == "1"
-# Round 6: the same sum with the loops turned inside out (gn_bil_expand_rows_ang_f32: a WAVE owns 32 expand rows of one atom and
-# walks the atom's reduce edges with the accumulators in registers — no LDS accumulation, no barrier, rows written once; the
-# quadruplet of (edge, row) from a dense per-atom grid built with the index plan, graph.SegmentPlan.row_grid).
+# The x-adjoint of the tensor basis without per-quadruplet rows in memory (round 6, gn_bil_expand_rows_ang_f32: a WAVE owns 32
+# expand rows of one atom and walks the atom's reduce edges with the accumulators in registers — no LDS accumulation, no barrier,
+# rows written once; the quadruplet of (edge, row) from a dense per-atom grid built with the index plan,
+# graph.SegmentPlan.row_grid).  GEMNET_ROW_GRID=0: per-quadruplet rows + a segmented sum.
 USE_ROW_GRID = os.environ.get("GEMNET_ROW_GRID", "1") == "1"
-ATOM_BLOCK_MAX_ROWS = 848
 # Which angle-form kernels run their products on the fp16 matrix pipe (`arith` = GN_ANG_F16 of the launch): bit 0 = K1 of
 # bil_reduce_project (only under the "h3" Dense arithmetic: x unscaled), bit 1 = the angle gradient bil_dy_multi, bit 2 = the
 # x-adjoint bil_expand (both under an exact per-edge scale: any magnitude).  Read-only configuration (A/B runs, tests).
 ANG_F16_MASK = int(os.environ.get("GEMNET_ANG_F16", "7")) & 7
-
-
-# GemNet-Q x-adjoint: GEMNET_EXPAND_POS=1 writes the per-quadruplet rows in DESTINATION order (SegmentPlan.expand_pos) so that
-# the segmented sum reads them contiguously.  Measured (profiles/r5_expand_pos_ab.txt): 11.58-11.64 ms against 11.42-11.44 —
-# the scattered 128-byte row writes cost more than the contiguous reads save.  Off.
-USE_EXPAND_POS = os.environ.get("GEMNET_EXPAND_POS", "0") == "1"
 
 
 # The triplet x-adjoint per atom on the matrix cores (gn_bil_x_adjoint_atoms_f32: groups of <= 32 rows as one dense product
@@ -548,8 +535,10 @@ USE_XADJ_MFMA = os.environ.get("GEMNET_XADJ_MFMA", "1") == "1"
 def bil_reduce_t(Y, D, sp):
     """dx[j,c] = sum_{t: g(t)=j} sum_s Y[t,s] D[r(t),s,c].
     Angle form (GemNet-Q): the row-stationary kernel when the plan carries the per-atom grid (USE_ROW_GRID, the default: no
-    per-quadruplet rows in memory), else the per-atom workgroup of round 4 (USE_ATOM_BLOCKS), else per-quadruplet rows + a
-    segmented sum.  Spherical basis of the triplets: the atom-grouped kernel; other shapes: the scalar kernels."""
+    per-quadruplet rows in memory), else per-quadruplet rows + a segmented sum.  Spherical basis of the triplets: the
+    atom-grouped kernel; other shapes: the scalar kernels.
+    (Tried and removed: one workgroup per atom with its rows in LDS, and rows written in destination order — both slower,
+    profiles/r4_q_atom_blocks.txt, profiles/r5_expand_pos_ab.txt.)"""
     require_device(Y, D)
     Y, D = _f32c(Y), _f32c(D)
     S, C = D.shape[1], D.shape[2]
@@ -564,21 +553,10 @@ def bil_reduce_t(Y, D, sp):
                                                          (GN_ANG_F16 if ANG_F16_MASK & 4 else 0) | (sp.ROW_TILE << 8), stream()),
                   "gn_bil_expand_rows_ang_f32")
             return dx
-        ab = sp.atom_blocks if USE_ATOM_BLOCKS else None
-        if ab is not None and 0 < ab[3] <= ATOM_BLOCK_MAX_ROWS and C == 32:
-            # quadruplets: the rows of one target atom summed in LDS, no per-quadruplet rows in memory
-            a_perm, a_seg, j_off, max_J = ab
-            dx = torch.empty((sp.n_expand, C), device=Y.device, dtype=torch.float32)   # j_off partitions the rows: all written
-            check(_lib.load().gn_bil_expand_atoms_ang_f32(ptr(Y), ptr(D), ptr(sp.seg_off), ptr(sp.expand.idx32), ptr(a_perm),
-                                                          ptr(a_seg), ptr(j_off), ptr(dx), a_seg.shape[0] - 1, int(max_J), S, C,
-                                                          stream()), "gn_bil_expand_atoms_ang_f32")
-            return dx
         dxt = torch.empty((sp.size, C), device=Y.device, dtype=torch.float32)
-        pos = sp.expand_pos if USE_EXPAND_POS and permT is not None else None
         check(_lib.load().gn_bil_expand_ang_f32(ptr(Y), ptr(D), ptr(sp.seg_off), ptr(dxt), sp.n_reduce, S, C,
-                                                GN_ANG_F16 if ANG_F16_MASK & 4 else 0, ptr(pos), stream()), "gn_bil_expand_ang_f32")
-        # rows written in the order of their expand row: the sum reads them contiguously (same rows, same order of addition)
-        return segsum(dxt, None if pos is not None else permT, segT, sp.n_expand)
+                                                GN_ANG_F16 if ANG_F16_MASK & 4 else 0, stream()), "gn_bil_expand_ang_f32")
+        return segsum(dxt, permT, segT, sp.n_expand)
     if S > 8:
         # tensor basis: per-quadruplet rows grouped by reduce edge (dSm[e] read once per edge), then one CSR sum
         dxt = torch.empty((sp.size, C), device=Y.device, dtype=torch.float32)
@@ -1162,11 +1140,9 @@ def use_mode(mode):
 
 
 # Kernel layout of the "h3" launches: "tall" = csrc/chain2.hip (one 8-wave workgroup per CU on row tiles of <= 80 rows, a wave
-# owns 16 columns), "wide" = csrc/chain3.hip (workgroups of 4 waves x 32 columns on row tiles of <= 48 rows, two per CU;
-# GN_CHAIN_WIDE).  Same results bit for bit (tests/test_gpu_kernels.py).  Measured on MI355X (profiles/r4_chain_layouts.txt):
-# the edge-row programs take the same time in both (a wave of either layout does the same amount of work per op, and two
-# co-resident workgroups neither help nor disturb each other), the atom-row programs are 25-35 % slower in the wide one —
-# "tall" stays the default; programs that use the parking slot always take it (the library decides).
+# owns 16 columns): the default; programs that use the parking slot always take it (the library decides).
+# (Tried and removed: a "wide" layout of 4 waves x 32 columns, two workgroups per CU — bit-identical, never faster:
+# profiles/r4_chain_layouts.txt.)
 # "row" (round 6) = csrc/chain4.hip: a wave owns 16 ROWS and all columns, the slots are fp32 register arrays, the fp16 planes of
 # every GEMM operand are formed under a fresh row scale (no fp16 range limit on activations, no `h3_hazards`), only the weights
 # pass through LDS (GN_CHAIN_ROW; weights packed with GN_SPLIT_F16X2_ROW = 2).  Same arithmetic ("h3": two fp16 planes, three
@@ -1174,9 +1150,8 @@ def use_mode(mode):
 # row blocks on 1 024 SIMDs put two 16-row waves on one SIMD of every CU, and a wave's ds_read_b128 stream of weight fragments
 # runs at ~28 B/clk) — selectable, not the default.
 CHAIN_LAYOUT = os.environ.get("GEMNET_CHAIN_LAYOUT", "tall")
-# per-launch tuning of the wide layout (GN_CHAIN_WIDE_ROWS / GN_CHAIN_WIDE_STAGGER bits of `nprod`; 0 = automatic / none)
-WIDE_TILE_ROWS = int(os.environ.get("GN_CHAIN_TILE_ROWS", "0"))
-WIDE_STAGGER = int(os.environ.get("GN_CHAIN_STAGGER", "0"))
+if CHAIN_LAYOUT not in ("tall", "row"):
+    raise ValueError(f"GEMNET_CHAIN_LAYOUT must be 'tall' or 'row'; got {CHAIN_LAYOUT!r}")
 # The fp16 planes of "h3" cover the magnitudes the MODEL fixes (activations, first-order adjoints dE/d.): sweeps whose
 # scale follows the caller's loss (S3 / S4 and the energy-only final adjoint of force training, ops_train.py) run in this
 # mode instead when the stack's mode is "h3" — bf16 planes have the fp32 exponent range.
@@ -1523,10 +1498,6 @@ def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
     cbuf = (ctypes.c_char * args_size).from_buffer(buf)
     if row:
         nprod |= GN_CHAIN_ROW
-    elif nprod == CHAIN_MODES["h3"] and CHAIN_LAYOUT == "wide":
-        if WIDE_TILE_ROWS and (WIDE_TILE_ROWS % 8 or not 8 <= WIDE_TILE_ROWS <= 48):
-            raise ValueError("GN_CHAIN_TILE_ROWS: a multiple of 8 in 8..48")
-        nprod |= GN_CHAIN_WIDE | ((WIDE_TILE_ROWS // 8) << 12) | ((max(WIDE_STAGGER, 0) & 0xffff) << 16)
     if groups:
         if _lib.TRACE is not None:
             # the argument block names group 0's slab of every operand; the launch touches all `groups` slabs, `group_pitch`

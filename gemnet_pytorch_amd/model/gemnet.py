@@ -30,10 +30,6 @@ from .scaling import AutomaticFit
 
 
 _nullcontext = contextlib.nullcontext
-# A/B switch: one running gradient for rbf_out (five consumers on the side stream) instead of four engine-side adds.
-# Off: same-box A/B on MI355X (profiles/r3_ab.txt) 2.777 / 2.747 ms with it, 2.729 / 2.685 ms without — the chained
-# in-place sums order the output blocks' adjoints behind each other, the engine's adds did not.
-_RBF_OUT_ACC = os.environ.get("GEMNET_RBF_OUT_ACC", "0") == "1"
 _H3_GUARD = os.environ.get("GEMNET_H3_GUARD", "1") == "1"     # see GemNet.forward
 # Side-stream placement switches.  All three were forced off in round 3 because hipGraph replays stopped matching the eager
 # run with them; round 4 located the cause below the library — packed-FP32 instructions of the fused aggregation adjoint
@@ -258,8 +254,6 @@ class GemNet(torch.nn.Module):
             if fork and head:
                 # everything the side stream consumes of the head is rbf_out, and every output block orders itself behind
                 # the main stream before it reads it (out_block below)
-                if _RBF_OUT_ACC:
-                    rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
                 main.wait_event(ev_a)
                 for t in (sph3, h) + tuple(terms):
                     t.record_stream(main)
@@ -279,8 +273,6 @@ class GemNet(torch.nn.Module):
                 # (all consumers of the output blocks' radial projection run on the side stream: so does the projection)
                 if not _RBF_OUT_SIDE:
                     rbf_out = self.mlp_rbf_out(rbf)
-                if _RBF_OUT_ACC:
-                    rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
                 main.wait_event(ev_a)
                 for t in (sph3, h) + tuple(terms):
                     t.record_stream(main)
@@ -372,8 +364,6 @@ class GemNet(torch.nn.Module):
         if head:
             cbf3 = (ops.accumulate_gradient(rbf_W1_3), sph3)
             rbf_h = ops.accumulate_gradient(rbf_h)
-            if not fork and _RBF_OUT_ACC:
-                rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
         elif fork:
             main.wait_event(ev_b)
             for t in (rbf_W1_3, rbf_h):    # produced on the side stream, consumed (and summed: `stream=`) on the main one
@@ -384,8 +374,6 @@ class GemNet(torch.nn.Module):
             cbf3 = (ops.accumulate_gradient(self.mlp_cbf3(rad3)), sph3)
             rbf_h = ops.accumulate_gradient(self.mlp_rbf_h(rbf))
             rbf_out = self.mlp_rbf_out(rbf)
-            if _RBF_OUT_ACC:
-                rbf_out = ops.accumulate_gradient(rbf_out, stream=side)
 
         # OutputBlock i only feeds the final energy sum.  Two forms:
         #  * grouped (`_out_group_blocks`: GemNet-T force pass with constant weights, the published widths, one target):

@@ -653,7 +653,7 @@ class _RbfAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, rbf, W, ri, scale):
         perm, seg = ri.csr
-        ctx.acc_m, ctx.acc_rbf = _acc_join(m, cross=True), _acc_join(rbf)
+        ctx.acc_m, ctx.acc_rbf = _acc_join(m), _acc_join(rbf)
         ctx.save_for_backward(m, rbf, W)
         ctx.ri, ctx.scale = ri, scale
         return K.rbf_aggregate_fwd(m, rbf, W, perm, seg, ri.n_rows, scale)
@@ -702,10 +702,7 @@ class GradSink:
         self.buf = None
         self.pending = []   # (dSm_b, x_b) of the consumers whose Y gradient is deferred to one combined pass
         self.stream = None  # accumulate_gradient: HIP stream of the participating consumers
-        self.cross = False  # consumers on several streams take part (events order their writes, see enter / leave)
-        self.buf_stream = self.buf_event = None
         self.task = None    # id of the backward pass (autograd graph task) the running state belongs to
-        self.home = None    # HIP stream the shared tensor was produced on (= the stream its producer's backward runs on)
 
     def arrive(self):
         """Called once per consumer backward; returns True for the last consumer of this pass."""
@@ -740,26 +737,12 @@ class GradSink:
         return out, prev, last
 
     def enter(self):
-        """-> (running sum so far or None, is this the last consumer of the pass); pair with `leave`.
-        A consumer on ANOTHER stream than the one that wrote the running sum last (an output block on the side stream
-        followed by the interaction block on the main stream) first orders itself behind that write and tells the
-        allocator that the buffer is in use on its stream too."""
+        """-> (running sum so far or None, is this the last consumer of the pass); pair with `leave`."""
         last = self.arrive()
-        buf = self.buf
-        if buf is not None and self.cross and buf.is_cuda:
-            cur = torch.cuda.current_stream(buf.device)
-            if self.buf_stream is not None and self.buf_stream != cur.cuda_stream:
-                cur.wait_event(self.buf_event)
-                buf.record_stream(cur)
-        return buf, last
+        return self.buf, last
 
     def leave(self, out, last):
         self.buf = None if last else out
-        if self.cross and not last and out is not None and out.is_cuda:
-            cur = torch.cuda.current_stream(out.device)
-            self.buf_stream = cur.cuda_stream
-            self.buf_event = torch.cuda.Event()
-            self.buf_event.record(cur)
 
     def skip(self):
         """A consumer that has no contribution in this pass (undefined incoming gradient)."""
@@ -772,33 +755,7 @@ def share_gradient(t):
     """Mark tensor `t` (a non-leaf that requires grad) as shared between fused bilinear layers of one forward."""
     if t.requires_grad and _FUSED:
         t._gn_sink = GradSink()
-        if t.is_cuda:
-            t._gn_sink.home = torch.cuda.current_stream(t.device)
     return t
-
-
-# The combined Y gradient of all consumers of a shared basis (bil_dy_multi: 75 us at the headline shape) is launched by the
-# LAST consumer's backward, in front of the rest of that block's adjoint, although only the basis' own backward needs it.
-# When the basis was produced on another stream than the consumers run on (the forked head of GemNet.forward: autograd
-# replays the producer's backward on that stream), the launch goes to THAT stream: ordered in front of its consumer by
-# stream order, beside the block's remaining adjoint kernels instead of in front of them.
-USE_LATE_DY = os.environ.get("GEMNET_LATE_DY", "0") == "1"   # measured: profiles/r5_late_dy_ab.txt (no gain: off)
-
-
-def _on_home_stream(sink, inputs, fn):
-    home = sink.home
-    t0 = inputs[0]
-    if not (USE_LATE_DY and home is not None and t0.is_cuda):
-        return fn()
-    cur = torch.cuda.current_stream(t0.device)
-    if home.cuda_stream == cur.cuda_stream:
-        return fn()
-    home.wait_stream(cur)
-    with torch.cuda.stream(home):
-        out = fn()
-    for t in inputs:
-        t.record_stream(home)
-    return out
 
 
 USE_GRAD_ACC = os.environ.get("GEMNET_GRAD_ACC", "1") == "1"
@@ -822,25 +779,15 @@ def accumulate_gradient(t, stream=None):
     return t
 
 
-# Off by default: it removes five (E, 128) adds per step but the main-stream consumers then wait for the output block's
-# backward BEFORE they start instead of meeting it in one add at the end — same-box A/B on MI355X (profiles/r3_ab.txt):
-# 2.789 / 2.792 ms off vs 2.792 / 2.791 ms on.  No gain, so the simpler ordering stays.
-USE_CROSS_ACC = os.environ.get("GEMNET_CROSS_ACC", "0") == "1"
-
-
-def _acc_join(t, cross=False):
+def _acc_join(t):
     """Forward side of `accumulate_gradient`: register the calling fused op as a consumer of `t`.  A consumer on another
-    stream than the sink's only takes part when it asks for it (`cross`: the output block's aggregation of the block
-    input m — its backward runs first, on the side stream, and the main-stream consumers then add into its result behind
-    an event instead of through a separate elementwise add of the autograd engine)."""
+    stream than the sink's does not take part (None): its gradient reaches `t` through autograd."""
     acc = getattr(t, "_gn_acc", None)
     if acc is None:
         return None
     st = torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
     if acc.stream != st:
-        if not (cross and USE_CROSS_ACC and constant_weights()):
-            return None
-        acc.cross = True
+        return None
     acc.consumers += 1
     return acc
 
@@ -917,7 +864,7 @@ def _bilinear_backward(ctx, saved, g, need, up=None):
         gsph = None
         if last:
             ds, xs = [d for d, _ in sink.pending], [xx for _, xx in sink.pending]
-            gsph = _on_home_stream(sink, ds + xs + [sph], lambda: K.bil_dy_multi(ds, xs, sp, ang=sph if ctx.ang else None))
+            gsph = K.bil_dy_multi(ds, xs, sp, ang=sph if ctx.ang else None)
             sink.pending = []
     elif sink is not None and need[1]:
         # the Y gradient is summed across the consumers of `sph` inside the kernel (see GradSink)
@@ -1534,7 +1481,7 @@ class _OutputGroup(torch.autograd.Function):
         G = len(ms)
         perm, seg = ri.csr
         A = ri.n_rows
-        ctx.acc_m = [_acc_join(m, cross=True) for m in ms]
+        ctx.acc_m = [_acc_join(m) for m in ms]
         ctx.acc_rbf = _acc_join(rbf)
         W_rbf = [contiguous_weight(b["W_rbf"]) for b in blocks]
         scales = _stacked_form("ogs", [b["scale"] for b in blocks],

@@ -155,13 +155,6 @@ int gn_chain_f32(const gn_chain_args* args, void* stream);
  * their dot product: meant for activations and first-order adjoints, whose scale the model fixes — not for sweeps whose
  * scale follows the loss.  `W` must have been packed with fmt = GN_SPLIT_F16X2. */
 #define GN_CHAIN_F16X2 2
-/* nprod = GN_CHAIN_F16X2 | GN_CHAIN_WIDE: the same arithmetic in the "wide" kernel layout (csrc/chain3.hip): workgroups of 4
- * waves x 32 output columns over row tiles of gn_chain_wide_tile_rows(M) rows (a multiple of 8, at most 48), two workgroups
- * per CU — one workgroup's epilogue / LOAD / weight wait runs under the other's MFMA phase.  Same results bit for bit. */
-#define GN_CHAIN_WIDE 0x100
-/* Per-launch tuning of the wide layout, OR-ed into `nprod` (ABI 13: until ABI 12 two process-global setters):
- * GN_CHAIN_WIDE_ROWS(r), r a multiple of 8 in 8..48, fixes the tile height (0 = gn_chain_wide_tile_rows(M));
- * GN_CHAIN_WIDE_STAGGER(u) starts the second workgroup of a CU u x 64 cycles late (0 = none). */
 /* nprod = GN_CHAIN_F16X2 | GN_CHAIN_ROW (ABI 15; csrc/chain4.hip): the same programs with a wave owning 16 ROWS and all
  * columns — the slots are fp32 register arrays (exact residual stream), the fp16 planes of a GEMM's operand are formed per
  * GEMM under a fresh power-of-two row scale (no range limit on activations, no restriction on programs that add global
@@ -169,8 +162,6 @@ int gn_chain_f32(const gn_chain_args* args, void* stream);
  * `W` must have been packed with fmt = GN_SPLIT_F16X2_ROW; additionally K % 16 == 0 and width % 16 == 0.
  * Same results as GN_CHAIN_F16X2 to fp32 rounding (not bit for bit: the K order inside a dot product differs). */
 #define GN_CHAIN_ROW 0x200
-#define GN_CHAIN_WIDE_ROWS(r) ((((r) / 8) & 0xf) << 12)
-#define GN_CHAIN_WIDE_STAGGER(u) (((u) & 0xffff) << 16)
 /* A program must start with a GN_OP_LOAD (the kernel's prologue relies on that op's barrier); else hipErrorInvalidValue. */
 int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream);
 /* Grouped launch: the SAME program for `groups` <= GN_CHAIN_MAX_GROUPS independent row ranges with their own weights, in one
@@ -188,8 +179,6 @@ int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream);
 #define GN_CHAIN_MAX_GROUPS 8
 #define GN_CHAIN_GROUP_TILE_ROWS 32
 int gn_chain_split_grouped_f32(const gn_chain_args* args, int nprod, int groups, int group_pitch, int tile_rows, void* stream);
-/* the automatic tile height of the wide layout for M rows (a pure function) */
-int gn_chain_wide_tile_rows(int M);
 /* W (N,K) fp32 with row pitch ldw — or, trans != 0, the (K,N) matrix whose transpose is the weight — -> three bf16
  * planes in MFMA-fragment order; `out` holds gn_pack_weight_split_bytes(N,K) bytes (16-byte aligned). */
 int gn_pack_weight_split(const float* W, int N, int K, int ldw, int trans, void* out, void* stream);
@@ -301,11 +290,9 @@ int gn_quad_angles_bwd_ld_f32(const float* g_ang, const float* R, const int32_t*
 int gn_bil_reduce_project_ang_f32(const float* ang, const float* x, const int32_t* expand_idx, const int32_t* seg_off,
                                   const float* B, float* Sm, float* P, int64_t E, int S, int C, int I, int arith,
                                   void* stream);
-/* per-quadruplet x-adjoint rows as gn_bil_expand_f32, Y given as angles.  row_pos (optional, ABI 14): dxt row that receives
- * quadruplet q — its position in the order of the EXPAND rows, so that gn_segsum_rows_f32 reads contiguous rows (perm = NULL)
- * instead of gathering 128-byte rows through the permutation; the same rows are summed in the same order. */
+/* per-quadruplet x-adjoint rows as gn_bil_expand_f32, Y given as angles */
 int gn_bil_expand_ang_f32(const float* ang, const float* dSm, const int32_t* seg_off, float* dxt, int64_t E, int S, int C,
-                          int arith, const int32_t* row_pos, void* stream);
+                          int arith, void* stream);
 /* The x-adjoint of the quadruplet layer WITHOUT per-quadruplet rows in memory (ABI 15; csrc/bilinear_ang.hip,
  * bil_expand_rows_ang_kernel): dx[j] = sum_{q: g(q) = j} Y[q] dSm[r(q)] (interaction_block.py:517-566, backward through the
  * gather of x) with a wave owning 32 expand rows of one target atom and walking that atom's reduce edges, accumulators in
@@ -339,17 +326,6 @@ int gn_bil_expand_rows_ang_tan_f32(const float* ang, const float* tang, const fl
                                    const int32_t* a_seg, const int32_t* j_off, const int32_t* qmap, const int32_t* g_off,
                                    const int32_t* task_atom, const int32_t* task_row0, int64_t n_tasks, float* dx, int S, int C,
                                    int tile, void* stream);
-/* The same x-adjoint SUMMED over the expand rows, without the per-quadruplet rows in memory: dx[j] = sum_{q: g(q) = j}
- * Y[q] dSm[r(q)].  Needs the quadruplet structure of GemNet (data_container.py:331-397): reduce edge and expand row of a
- * quadruplet end in the same target atom, and the expand rows (intermediate triplets) are sorted by that atom —
- * a_perm / a_seg: the reduce edges grouped by target atom (CSR over n_atoms; a_perm NULL = already grouped), j_off: first
- * expand row of every atom (n_atoms + 1).  One workgroup per atom keeps its rows in LDS: max_J >= the largest
- * j_off[a+1] - j_off[a], (max_J * 32 + 13 568) * 4 bytes <= 160 KB (max_J <= 848), else hipErrorInvalidValue (the caller
- * uses gn_bil_expand_ang_f32 + gn_segsum_rows_f32); an atom with more rows than max_J traps.  Deterministic (the edges of
- * an atom are summed in a_perm order).  Every row of dx that belongs to an atom is written; S = 49, C = 32. */
-int gn_bil_expand_atoms_ang_f32(const float* ang, const float* dSm, const int32_t* seg_off, const int32_t* expand_idx,
-                                const int32_t* a_perm, const int32_t* a_seg, const int32_t* j_off, float* dx,
-                                int64_t n_atoms, int max_J, int S, int C, void* stream);
 /* gradient w.r.t. the two angles of all nb <= 4 blocks sharing the basis (gn_bil_dy_multi_f32 contracted with dY/d angle) */
 int gn_bil_dy_multi_ang_f32(const float* const* dSm_list, const float* const* x_list, int nb, const float* ang,
                             const int32_t* expand_idx, const int32_t* seg_off, float* g_ang, int64_t E, int S, int C,

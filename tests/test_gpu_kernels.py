@@ -331,7 +331,7 @@ def test_trip_basis_fused_fwd_bwd_including_collinear():
 
 def _stack_programs(M, width, g, dev, park=True):
     """A residual-stack-like program with every op kind, slots aliasing and slot/global operands.
-    park=False: the same without the register parking slot (such programs take the wide kernel layout, csrc/chain3.hip)."""
+    park=False: the same without the register parking slot."""
     def mk(*shape):
         return rnd(g, *shape)
     x, W0, W1, W2 = mk(M, 64), mk(width, 64) / 8, mk(width, width) / 11, mk(width, width) / 11
@@ -362,7 +362,7 @@ def _stack_programs(M, width, g, dev, park=True):
 def _adjoint_programs(M, width, g, dev, park=True):
     """The fused-epilogue features of the adjoint programs: LOAD with scale + second tensor, a global mul with
     activation-derivative mode, second outputs (from the final value and from the pre-mul value, to a slot aliasing
-    the A operand and to global memory).  park=False: without the register parking slot (wide kernel layout)."""
+    the A operand and to global memory).  park=False: without the register parking slot."""
     def mk(*shape):
         return rnd(g, *shape)
     gin, W1, W2 = mk(M, width), mk(width, width) / 11, mk(width, width) / 11
@@ -459,40 +459,6 @@ def test_chain_kernel_vs_interpreter(M, width, mode, monkeypatch):
             worst = max(worst, err)
             assert err <= 2 * tol, (getattr(maker, '__name__', 'no-park variant'), k, err)
     print(f"chain {mode} M={M} width={width}: max err / scale = {worst:.2e}")
-
-
-@pytest.mark.parametrize("tile_rows", [0, 8, 24, 40, 48])
-@pytest.mark.parametrize("M,width", [(1000, 128), (33, 64), (18122, 128), (5000, 128), (9000, 64)])
-def test_wide_chain_layout_equals_tall_layout_bitwise(M, width, tile_rows):
-    """csrc/chain3.hip (4 waves x 32 columns, row tiles of any multiple of 8 rows up to 48, two workgroups per CU) against
-    csrc/chain2.hip (8 waves x 16 columns): the same products accumulated in the same order — every output bit for bit, for
-    forward stacks (activations, gathered adds, pre-activation / stored-derivative outputs) and first-order adjoint programs
-    (row scales, second outputs), ragged last tiles and half-used MFMA row blocks included."""
-    checked = 0
-    default_layout, default_rows = K.CHAIN_LAYOUT, K.WIDE_TILE_ROWS
-    try:
-        import functools
-        for maker in (functools.partial(_stack_programs, park=False), functools.partial(_adjoint_programs, park=False),
-                      _adjoint_programs):
-            outs = {}
-            for layout in ("tall", "wide"):
-                g = torch.Generator().manual_seed(M)
-                build = maker(M, width, g, DEV)
-                p_dev, o_dev = build(lambda t: f32(t), lambda i: i.to(DEV))
-                if K.h3_hazards(p_dev):
-                    break
-                K.CHAIN_LAYOUT = layout
-                K.WIDE_TILE_ROWS = tile_rows if layout == "wide" else 0     # GN_CHAIN_WIDE_ROWS bits of this launch's `nprod`
-                K.chain(p_dev, mode="h3")
-                torch.cuda.synchronize()
-                outs[layout] = o_dev
-            if len(outs) == 2:
-                for k in outs["tall"]:
-                    assert torch.equal(outs["tall"][k], outs["wide"][k]), (k, tile_rows)
-                    checked += 1
-    finally:
-        K.CHAIN_LAYOUT, K.WIDE_TILE_ROWS = default_layout, default_rows
-    assert checked >= 10
 
 
 def test_source_terms_are_rejected_by_the_f32_chain_kernel():
@@ -1080,41 +1046,6 @@ def test_quad_angles_tangent_kernel():
     rhs = float((Gc * tR[qc.long()]).sum() + (Gb * tR[qb.long()]).sum() + (Gd * tR[qd.long()]).sum()
                 - ((Gc + Gb + Gd) * tR[qa.long()]).sum())
     assert abs(lhs - rhs) <= 1e-4 * max(abs(lhs), abs(rhs), 1.0), (lhs, rhs)
-
-
-@pytest.mark.parametrize("n_mol,n_atoms", [(3, 12), (2, 32)])
-def test_fused_per_atom_x_adjoint_of_the_tensor_basis(n_mol, n_atoms, monkeypatch):
-    """gn_bil_expand_atoms_ang_f32 — one workgroup per target atom, the atom's expand rows summed in LDS edge by edge, no
-    per-quadruplet rows in memory — on the real quadruplet structure of a GemNet-Q batch (the only structure it is defined
-    for: reduce edge and intermediate triplet of a quadruplet end in the same atom) against the float64 restatement on the
-    explicit (Q, 49) harmonics and against the two-pass form (gn_bil_expand_ang_f32 + segmented sum); run twice: bitwise."""
-    from gemnet_pytorch_amd.graph import GraphPlan
-    from gemnet_pytorch_amd.synthetic import make_dataset
-    from gemnet_pytorch_amd.training.data_container import DataContainer
-    ds = make_dataset(n_mol, n_atoms, config=2)
-    b = DataContainer.from_arrays(dict(ds), 5.0, 10.0, triplets_only=False)[list(range(n_mol))]
-    inputs = {k: v for k, v in b.items() if k not in ("E", "F")}
-    monkeypatch.setattr(K, "USE_ATOM_BLOCKS", True)      # (the plan only builds the per-atom structure for its one consumer)
-    cpu = GraphPlan.from_inputs(dict(inputs), False).quad
-    dev_plan = GraphPlan.from_inputs({k: v.to(DEV) for k, v in inputs.items()}, False).warm()
-    dev = dev_plan.quad
-    a_perm, a_seg, j_off, max_J = dev.atom_blocks
-    assert 0 < max_J <= K.ATOM_BLOCK_MAX_ROWS and int(j_off[-1]) == dev.n_expand
-    g = torch.Generator().manual_seed(n_atoms)
-    Q, S, C = cpu.size, 49, 32
-    th, ph = torch.rand(Q, generator=g, dtype=torch.float64) * 3.1, torch.rand(Q, generator=g, dtype=torch.float64) * 3.1
-    ang = torch.stack([torch.sin(th), torch.cos(th), torch.sin(ph), torch.cos(ph)], 1)
-    D = rnd(g, dev.n_reduce, S, C)
-    ref = CK.bil_reduce_t(ang, D, cpu)
-    monkeypatch.setattr(K, "USE_ATOM_BLOCKS", True)
-    got = K.bil_reduce_t(f32(ang), f32(D), dev)
-    close(got, ref, atol=2e-5 * max(1.0, float(ref.abs().max())))
-    assert torch.equal(got, K.bil_reduce_t(f32(ang), f32(D), dev))
-    monkeypatch.setattr(K, "USE_ATOM_BLOCKS", False)
-    two_pass = K.bil_reduce_t(f32(ang), f32(D), dev)
-    close(got, two_pass.double().cpu(), atol=2e-5 * max(1.0, float(ref.abs().max())))
-    print(f"{n_mol} x {n_atoms}: {Q} quadruplets, max |J_a| {max_J}; fused vs float64 {float((got.double().cpu() - ref).abs().max()):.2e}, "
-          f"two-pass vs float64 {float((two_pass.double().cpu() - ref).abs().max()):.2e}")
 
 
 @pytest.mark.parametrize("arith_f16", [True, False], ids=["fp16-planes", "f32-mfma"])

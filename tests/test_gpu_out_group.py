@@ -295,7 +295,7 @@ def test_captured_replay_of_the_grouped_path_equals_eager_bitwise(t_case, monkey
 
 
 @gpu
-@pytest.mark.parametrize("kind", ["direct", "Q", "training", "f32", "wide", "no-aggregate"])
+@pytest.mark.parametrize("kind", ["direct", "Q", "training", "f32", "row", "no-aggregate"])
 def test_other_passes_keep_one_set_of_launches_per_block(kind, monkeypatch):
     """Model kinds, and a chain arithmetic / kernel layout / aggregation switch without the grouped launches: the decision is
     taken before the first interaction block, so these passes are the GEMNET_OUT_GROUP=0 pass, launch for launch."""
@@ -310,8 +310,8 @@ def test_other_passes_keep_one_set_of_launches_per_block(kind, monkeypatch):
         model = model.train()
     elif kind == "f32":
         model.matmul_precision = "f32"
-    elif kind == "wide":
-        monkeypatch.setattr(K, "CHAIN_LAYOUT", "wide")
+    elif kind == "row":
+        monkeypatch.setattr(K, "CHAIN_LAYOUT", "row")
     elif kind == "no-aggregate":
         monkeypatch.setattr(ops, "USE_AGGREGATE", False)
     E1, F1, n1 = _run(model, inputs, True, monkeypatch)

@@ -10,7 +10,7 @@ from gemnet_pytorch_amd import kernels as K
 
 
 # the queries: every other declared function launches on exactly one `stream`
-NO_STREAM = {"gn_abi_version", "gn_error_string", "gn_chain_wide_tile_rows", "gn_optim_blocks", "gn_csr_ws_bytes",
+NO_STREAM = {"gn_abi_version", "gn_error_string", "gn_optim_blocks", "gn_csr_ws_bytes",
              "gn_index_gpu_ws_bytes", "gn_pbc_index_ws_bytes", "gn_pack_weight_split_bytes", "gn_gemm_tn_splitk"}
 
 

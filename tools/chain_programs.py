@@ -1,5 +1,5 @@
 """Per-program time of every chain launch of one GemNet-T (or, argument Q, GemNet-Q) forward+force step (GPU box), per kernel
-layout of the "h3" arithmetic: tall = csrc/chain2.hip, wide = csrc/chain3.hip, row = csrc/chain4.hip (the default).
+layout of the "h3" arithmetic: tall = csrc/chain2.hip, row = csrc/chain4.hip.
 LAYOUTS=tall,row (default) selects the columns; the model is rebuilt per layout (the packed-weight format differs)."""
 import os, sys, collections, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

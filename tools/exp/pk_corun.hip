@@ -4,7 +4,7 @@
 //   cd tools/exp && sh pk_corun.sh            (builds both variants, dumps the ISA of the victim kernel, runs them on gfx950)
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DGN_AGG_PK -I ../../include pk_corun.hip \
 //         ../../gemnet_pytorch_amd/csrc/aggregate.hip ../../gemnet_pytorch_amd/csrc/chain2.hip \
-//         ../../gemnet_pytorch_amd/csrc/chain3.hip -o pk_corun_pk         (victim WITH v_pk_*_f32: the failing form)
+//         ../../gemnet_pytorch_amd/csrc/chain4.hip -o pk_corun_pk         (victim WITH v_pk_*_f32: the failing form)
 //   ... the same without -DGN_AGG_PK -> pk_corun_nopk                      (victim compiled with no-packed-fp32-ops: passes)
 //
 // What it does: constant inputs; branch A of a two-branch hipGraph = six Dense-stack chain programs (MFMA-heavy,

@@ -10,7 +10,7 @@ REPS=${2:-200}
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 CSRC=$ROOT/gemnet_pytorch_amd/csrc
 mkdir -p "$OUT" "$HERE/bin"
-SRCS="$HERE/pk_corun.hip $CSRC/aggregate.hip $CSRC/chain2.hip $CSRC/chain3.hip"
+SRCS="$HERE/pk_corun.hip $CSRC/aggregate.hip $CSRC/chain2.hip $CSRC/chain4.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -I $ROOT/include"
 # the failing form is the ROUND-2 adjoint kernel (-DGN_AGG_V1) with packed FP32 (-DGN_AGG_PK); pk2 = the round-5 kernel with
 # packed FP32 (is the restructured kernel a victim too?); the product build has neither (no-packed-fp32-ops file-wide)
