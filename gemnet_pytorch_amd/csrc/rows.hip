@@ -91,12 +91,11 @@ __global__ __launch_bounds__(256) void segsum_wave(const VT* __restrict__ y, con
 // segment alone (9 dependent perm -> row round trips: 9.6 us for 9 MB).  Here a whole workgroup owns a row: wave w
 // takes entries k0 + w*EPL + slot, stride 4*EPL; the 4*EPL partial sums are combined in a fixed order.
 template <typename VT>
-__global__ __launch_bounds__(256) void segsum_block(const VT* __restrict__ y, const int32_t* __restrict__ perm,
-                                                    const int32_t* __restrict__ seg_off, VT* __restrict__ x, int CW) {
-  __shared__ VT part[4][64];
+__device__ __forceinline__ void segsum_block_row(const VT* __restrict__ y, const int32_t* __restrict__ perm,
+                                                 const int32_t* __restrict__ seg_off, VT* __restrict__ x, int CW,
+                                                 const int64_t r, VT (&part)[4][64]) {
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
-  const int64_t r = blockIdx.x;
   const int k0 = seg_off[r], k1 = seg_off[r + 1];
   for (int cb = 0; cb < CW; cb += 64) {
     const int cw = min(64, CW - cb);
@@ -125,6 +124,28 @@ __global__ __launch_bounds__(256) void segsum_block(const VT* __restrict__ y, co
     }
     __syncthreads();
   }
+}
+
+template <typename VT>
+__global__ __launch_bounds__(256) void segsum_block(const VT* __restrict__ y, const int32_t* __restrict__ perm,
+                                                    const int32_t* __restrict__ seg_off, VT* __restrict__ x, int CW) {
+  __shared__ VT part[4][64];
+  segsum_block_row(y, perm, seg_off, x, CW, (int64_t)blockIdx.x, part);
+}
+
+// Two CSR groupings of the SAME rows in one launch (the gradients of the two gathered atom terms of an edge Dense: both are
+// segmented sums of dz over the edges, by source and by target atom; as two launches they ran back to back in front of the
+// atom-row adjoint of every interaction block and each pulled dz from HBM).  Workgroup b < N1 owns row b of the first
+// grouping, workgroup N1 + b row b of the second: per row the code — and so the order of addition — of segsum_block.
+template <typename VT>
+__global__ __launch_bounds__(256) void segsum_pair_block(const VT* __restrict__ y, const int32_t* __restrict__ perm1,
+                                                         const int32_t* __restrict__ seg1, VT* __restrict__ x1, int N1,
+                                                         const int32_t* __restrict__ perm2, const int32_t* __restrict__ seg2,
+                                                         VT* __restrict__ x2, int CW) {
+  __shared__ VT part[4][64];
+  const bool second = (int)blockIdx.x >= N1;     // uniform
+  segsum_block_row(y, second ? perm2 : perm1, second ? seg2 : seg1, second ? x2 : x1, CW,
+                   (int64_t)blockIdx.x - (second ? N1 : 0), part);
 }
 
 // x[r, c] = sum_k sign_k * sum_{i in seg_k(r)} y_k[perm_k[i], c]: up to four CSR lists over the same rows in ONE launch.
@@ -216,6 +237,28 @@ extern "C" int gn_segsum_rows_f32(const float* y, const int32_t* perm, const int
                        seg_off, reinterpret_cast<float4*>(x), N, C / 4);
   } else {
     hipLaunchKernelGGL(segsum_wave<float>, grid, block, 0, st, y, perm, seg_off, x, N, C);
+  }
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_segsum_pair_f32(const float* y, const int32_t* perm1, const int32_t* seg_off1, float* x1, int64_t N1,
+                                  const int32_t* perm2, const int32_t* seg_off2, float* x2, int64_t N2, int C, void* stream) {
+  if (C <= 0) return 0;
+  if (N1 <= 0 || N2 <= 0 || N1 > 4096 || N2 > 4096) {   // not two workgroup-per-row sums: the single launches
+    if (const int e = gn_segsum_rows_f32(y, perm1, seg_off1, x1, N1, C, stream)) return e;
+    return gn_segsum_rows_f32(y, perm2, seg_off2, x2, N2, C, stream);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)(N1 + N2)), block(256);
+  if (C % 4 == 0 && aligned16(y) && aligned16(x1) && aligned16(x2))
+    hipLaunchKernelGGL(segsum_pair_block<float4>, grid, block, 0, st, reinterpret_cast<const float4*>(y), perm1, seg_off1,
+                       reinterpret_cast<float4*>(x1), (int)N1, perm2, seg_off2, reinterpret_cast<float4*>(x2), C / 4);
+  else if (C % 4 != 0 || (!aligned16(x1) && !aligned16(x2)))
+    hipLaunchKernelGGL(segsum_pair_block<float>, grid, block, 0, st, y, perm1, seg_off1, x1, (int)N1, perm2, seg_off2, x2, C);
+  else {   // one output aligned, one not: each single launch picks its own form
+    if (const int e = gn_segsum_rows_f32(y, perm1, seg_off1, x1, N1, C, stream)) return e;
+    return gn_segsum_rows_f32(y, perm2, seg_off2, x2, N2, C, stream);
   }
   GN_LAUNCH_CHECK();
   return 0;

@@ -166,6 +166,21 @@ def segsum(y, perm, seg_off, n_rows):
     return x
 
 
+def segsum_pair(y, perm1, seg_off1, n_rows1, perm2, seg_off2, n_rows2):
+    """-> (segsum(y, perm1, seg_off1, n_rows1), segsum(y, perm2, seg_off2, n_rows2)), bit for bit, in one launch when both
+    groupings have at most 4 096 rows (gn_segsum_pair_f32): y is read from memory once.  Host tensors go to `segsum`, which
+    refuses them (or, under the tests' CPU restatement of the launchers, sums them)."""
+    if not y.is_cuda:
+        return segsum(y, perm1, seg_off1, n_rows1), segsum(y, perm2, seg_off2, n_rows2)
+    require_device(y, seg_off1, seg_off2)
+    y = _f32c(y)
+    x1 = torch.empty((n_rows1,) + tuple(y.shape[1:]), device=y.device, dtype=torch.float32)
+    x2 = torch.empty((n_rows2,) + tuple(y.shape[1:]), device=y.device, dtype=torch.float32)
+    check(_lib.load().gn_segsum_pair_f32(ptr(y), ptr(perm1), ptr(seg_off1), ptr(x1), n_rows1, ptr(perm2), ptr(seg_off2),
+                                         ptr(x2), n_rows2, _rowsize(y), stream()), "gn_segsum_pair_f32")
+    return x1, x2
+
+
 def segsum_multi(terms, n_rows):
     """x[n] = sum_k sign_k * segsum(y_k, perm_k, seg_k)[n] for up to 4 terms (y, perm, seg_off, sign) sharing the row
     space, rows of <= 4 floats, in one launch (gn_segsum_multi_f32)."""

@@ -596,9 +596,11 @@ class _FusedDense(torch.autograd.Function):
             dz, gmul = K.dact_mul(g, z, act, mul, c, want_gmul=want_gmul)
             if need[0]:
                 gx = K.gemm(dz, transposed(W), res2=prev, out=out)
-            if has_g1 and need[5]:
+            if has_g1 and need[5] and has_g2 and need[6]:     # both sums of the same rows: one launch, dz read once
+                gg1, gg2 = K.segsum_pair(dz, *i1.csr, i1.n_rows, *i2.csr, i2.n_rows)
+            elif has_g1 and need[5]:
                 gg1 = K.segsum(dz, *i1.csr, i1.n_rows)
-            if has_g2 and need[6]:
+            elif has_g2 and need[6]:
                 gg2 = K.segsum(dz, *i2.csr, i2.n_rows)
             if want_w:
                 gW = K.gemm(dz, x, True, True)          # dz^T @ x  (N, K)
@@ -1405,9 +1407,11 @@ class _Stack(torch.autograd.Function):
             K.chain(K.fuse_program(prog))
             if not last:
                 gx = None
-            if has_g1 and need[4]:
+            if has_g1 and need[4] and has_g2 and need[5]:     # both sums of the same rows: one launch, dz0 read once
+                gg1, gg2 = K.segsum_pair(dz0, *first["i1"].csr, first["i1"].n_rows, *first["i2"].csr, first["i2"].n_rows)
+            elif has_g1 and need[4]:
                 gg1 = K.segsum(dz0, *first["i1"].csr, first["i1"].n_rows)
-            if has_g2 and need[5]:
+            elif has_g2 and need[5]:
                 gg2 = K.segsum(dz0, *first["i2"].csr, first["i2"].n_rows)
         else:
             gx = torch.empty((M, width), device=dev, dtype=dt)

@@ -405,6 +405,13 @@ int gn_gather_mul_f32(const float* x, const int32_t* idx, const float* m, float*
 /* x[n,:] = sum_{k in [seg_off[n], seg_off[n+1])} y[perm ? perm[k] : k, :]   (deterministic, no atomics) */
 int gn_segsum_rows_f32(const float* y, const int32_t* perm, const int32_t* seg_off, float* x,
                        int64_t N, int C, void* stream);
+/* Two segmented sums of the SAME source rows y (M,C) under two CSR groupings, in one launch when both have at most 4 096
+ * rows (a workgroup per output row; otherwise the two gn_segsum_rows_f32 launches):
+ *   x1[n,:] = sum_{k in [seg_off1[n], seg_off1[n+1])} y[perm1 ? perm1[k] : k, :],   x2 likewise from perm2 / seg_off2.
+ * The gradients of the two gathered atom terms of the edge-embedding Dense (embedding_block.py:70-75 under autograd).  Each
+ * output is bit for bit that of gn_segsum_rows_f32 (same order of addition).  Additive: no existing entry point changes. */
+int gn_segsum_pair_f32(const float* y, const int32_t* perm1, const int32_t* seg_off1, float* x1, int64_t N1,
+                       const int32_t* perm2, const int32_t* seg_off2, float* x2, int64_t N2, int C, void* stream);
 /* x[n,:] = sum_{k < n_terms} sign[k] * sum_{i in [seg_off[k][n], seg_off[k][n+1])} y[k][perm[k] ? perm[k][i] : i, :]
  * — up to 4 CSR lists over the same N rows in one launch (y / perm / seg_off / sign: HOST arrays of n_terms device
  * pointers / floats); rows of C <= 4 floats.  The assembly of dE/dR from the per-triplet and per-edge terms of the
