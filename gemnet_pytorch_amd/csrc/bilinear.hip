@@ -1615,8 +1615,11 @@ extern "C" int gn_bil_expand_f32(const float* Y, const float* dSm, const int32_t
     hipLaunchKernelGGL(bil_expand_mfma49_kernel, dim3(gn_cdiv(E, 4)), dim3(256), 0, st, Y, dSm, seg_off, dxt, E);
   } else if (S == 49) {
     constexpr int CH = 32;
-    hipLaunchKernelGGL((bil_expand_kernel<49, CH>), grid, block, (size_t)gpb * CH * 52 * sizeof(float), st, Y, dSm,
-                       seg_off, dxt, E, C);
+    // at most 8 edge groups per block (53 KB of LDS): narrow layers (C < 32) run with a smaller block instead of asking for more
+    // LDS than a launch gets (the kernel takes its groups from blockDim.x / C)
+    const int g49 = gpb < 8 ? gpb : 8;
+    hipLaunchKernelGGL((bil_expand_kernel<49, CH>), dim3(gn_cdiv(E, g49)), dim3(g49 * C), (size_t)g49 * CH * 52 * sizeof(float), st,
+                       Y, dSm, seg_off, dxt, E, C);
   } else if (S == 7) {
     constexpr int CH = 32;
     hipLaunchKernelGGL((bil_expand_kernel<7, CH>), grid, block, (size_t)gpb * CH * 8 * sizeof(float), st, Y, dSm,

@@ -9,6 +9,7 @@
 // deterministic CSR segmented sum (rows.hip) reduces onto atoms.
 #include "common.h"
 #include "basis_math.h"
+#include "quad_math.h"
 
 namespace {
 
@@ -142,51 +143,7 @@ __global__ void trip_basis_bwd_kernel(const float* __restrict__ gY, const float*
 }
 
 // ---- quadruplets c -> a - b <- d (gemnet.py:334-418) fused with the real Y_lm (basis_layers.py:269) --
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-
-// theta = atan2(max(|u x v|, 1e-9), u.v) and, for a given dL/dtheta, dL/du and dL/dv
-__device__ __forceinline__ float angle_uv(V3 u, V3 v) {
-  const V3 w = cross(u, v);
-  const float yn = sqrtf(dot(w, w));
-  return atan2f(yn < 1e-9f ? 1e-9f : yn, dot(u, v));
-}
-// (sin, cos) of that angle without atan2 / sincos: with y = max(|u x v|, 1e-9), x = u.v: sin = y / hypot(x, y),
-// cos = x / hypot(x, y)  (exactly the sine and cosine of atan2(y, x))
-__device__ __forceinline__ void angle_uv_sc(V3 u, V3 v, double& sn, double& cs) {
-  const V3 w = cross(u, v);
-  const float yn = sqrtf(dot(w, w));
-  const double y = yn < 1e-9f ? 1e-9 : (double)yn;
-  const double x = (double)dot(u, v);
-  const double ir = 1.0 / sqrt(x * x + y * y);
-  sn = y * ir;
-  cs = x * ir;
-}
-__device__ __forceinline__ void angle_uv_bwd(V3 u, V3 v, float gth, V3& gu, V3& gv) {
-  const V3 w = cross(u, v);
-  const float x = dot(u, v);
-  const float yn = sqrtf(dot(w, w));
-  const bool clamped = yn < 1e-9f;
-  const float y = clamped ? 1e-9f : yn;
-  const float r2 = x * x + y * y;
-  const float dx = -y / r2 * gth;
-  const float dy = clamped ? 0.f : x / r2 * gth;
-  const V3 n = (clamped ? 0.f : 1.0f / y) * w;
-  gu = dx * v + dy * cross(v, n);
-  gv = dx * u + dy * cross(n, u);
-}
-// r = x - (x.n / n.n) n  (vector_rejection, gemnet.py:313-332) and its adjoint
-__device__ __forceinline__ V3 reject(V3 x, V3 n) { return x - (dot(x, n) / dot(n, n)) * n; }
-__device__ __forceinline__ void reject_bwd(V3 x, V3 n, V3 gr, V3& gx, V3& gn) {
-  const float s = dot(x, n), q = dot(n, n), a = s / q, gn_dot = dot(gr, n);
-  gx = gr - (gn_dot / q) * n;
-  gn = (-a) * gr - gn_dot * ((1.0f / q) * x - (2.0f * s / (q * q)) * n);
-}
+// (the per-quadruplet math — V3, the two angles and their adjoint onto uac, uab, ubd — is quad_math.h, shared with pbc_quad.hip)
 
 // Y[q, :] = Y_lm(Phi_cab, Theta_cabd).  One thread per quadruplet; a thread's S^2 = 49 outputs are 196 B apart from
 // its neighbour's, so rows go through LDS (row stride 49 words: conflict-free) and leave as one contiguous,
@@ -203,10 +160,8 @@ __global__ __launch_bounds__(256) void quad_basis_fwd_kernel(const float* __rest
     if (q < Q) {
       const V3 Ra = v3(R + 3 * (int64_t)qa[q]), Rb = v3(R + 3 * (int64_t)qb[q]);
       const V3 uac = v3(R + 3 * (int64_t)qc[q]) - Ra, uab = Rb - Ra, ubd = v3(R + 3 * (int64_t)qd[q]) - Rb;
-      const V3 uba = (-1.0f) * uab;
       double sn, cs, s1, c1;   // polar angle Phi_cab, azimuth Theta_cabd
-      angle_uv_sc(uab, uac, sn, cs);
-      angle_uv_sc(reject(uac, uab), reject(ubd, uba), s1, c1);
+      quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
       ylm_row_sc(sn, cs, s1, c1, S, rows + threadIdx.x * SS);
     }
     __syncthreads();
@@ -237,21 +192,12 @@ __global__ __launch_bounds__(256) void quad_basis_bwd_kernel(const float* __rest
     if (q < Q) {
       const V3 Ra = v3(R + 3 * (int64_t)qa[q]), Rb = v3(R + 3 * (int64_t)qb[q]);
       const V3 uac = v3(R + 3 * (int64_t)qc[q]) - Ra, uab = Rb - Ra, ubd = v3(R + 3 * (int64_t)qd[q]) - Rb;
-      const V3 uba = (-1.0f) * uab;
-      const V3 p1 = reject(uac, uab), p2 = reject(ubd, uba);
       double sn, cs, s1, c1;
-      angle_uv_sc(uab, uac, sn, cs);
-      angle_uv_sc(p1, p2, s1, c1);
+      quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
       double g_first, g_second;   // d/d(polar angle = Phi_cab), d/d(azimuth = Theta_cabd)
       ylm_dot_grad_sc(sn, cs, s1, c1, S, rows + threadIdx.x * SS, g_first, g_second);
-      const float g_phi = (float)g_first, g_th = (float)g_second;
-      V3 g_ab, g_ac, gp1, gp2, t1, t2, g_bd, g_ba;
-      angle_uv_bwd(uab, uac, g_phi, g_ab, g_ac);
-      angle_uv_bwd(p1, p2, g_th, gp1, gp2);
-      reject_bwd(uac, uab, gp1, t1, t2);   // d p1 / d(uac, uab)
-      g_ac = g_ac + t1; g_ab = g_ab + t2;
-      reject_bwd(ubd, uba, gp2, g_bd, g_ba);
-      g_ab = g_ab - g_ba;                   // uba = -uab
+      V3 g_ab, g_ac, g_bd;
+      quad_angles_adj(uac, uab, ubd, (float)g_first, (float)g_second, g_ac, g_ab, g_bd);
       // uac = Rc - Ra, uab = Rb - Ra, ubd = Rd - Rb
       const V3 gc = g_ac, gd = g_bd, gb = g_ab - g_bd;
       Gc[ldc * q] = gc.x; Gc[ldc * q + 1] = gc.y; Gc[ldc * q + 2] = gc.z;
@@ -273,10 +219,8 @@ __global__ __launch_bounds__(256) void quad_angles_fwd_kernel(const float* __res
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < Q; q += (int64_t)gridDim.x * 256) {
     const V3 Ra = v3(R + 3 * (int64_t)qa[q]), Rb = v3(R + 3 * (int64_t)qb[q]);
     const V3 uac = v3(R + 3 * (int64_t)qc[q]) - Ra, uab = Rb - Ra, ubd = v3(R + 3 * (int64_t)qd[q]) - Rb;
-    const V3 uba = (-1.0f) * uab;
     double sn, cs, s1, c1;
-    angle_uv_sc(uab, uac, sn, cs);
-    angle_uv_sc(reject(uac, uab), reject(ubd, uba), s1, c1);
+    quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
     ang[q] = make_float4((float)sn, (float)cs, (float)s1, (float)c1);
   }
 }
@@ -290,17 +234,9 @@ __global__ __launch_bounds__(256) void quad_angles_bwd_kernel(const float4* __re
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < Q; q += (int64_t)gridDim.x * 256) {
     const V3 Ra = v3(R + 3 * (int64_t)qa[q]), Rb = v3(R + 3 * (int64_t)qb[q]);
     const V3 uac = v3(R + 3 * (int64_t)qc[q]) - Ra, uab = Rb - Ra, ubd = v3(R + 3 * (int64_t)qd[q]) - Rb;
-    const V3 uba = (-1.0f) * uab;
-    const V3 p1 = reject(uac, uab), p2 = reject(ubd, uba);
     const float4 g = g_ang[q];
-    const float g_phi = g.x, g_th = g.y;
-    V3 g_ab, g_ac, gp1, gp2, t1, t2, g_bd, g_ba;
-    angle_uv_bwd(uab, uac, g_phi, g_ab, g_ac);
-    angle_uv_bwd(p1, p2, g_th, gp1, gp2);
-    reject_bwd(uac, uab, gp1, t1, t2);
-    g_ac = g_ac + t1; g_ab = g_ab + t2;
-    reject_bwd(ubd, uba, gp2, g_bd, g_ba);
-    g_ab = g_ab - g_ba;
+    V3 g_ab, g_ac, g_bd;
+    quad_angles_adj(uac, uab, ubd, g.x, g.y, g_ac, g_ab, g_bd);
     const V3 gc = g_ac, gd = g_bd, gb = g_ab - g_bd;
     Gc[ldc * q] = gc.x; Gc[ldc * q + 1] = gc.y; Gc[ldc * q + 2] = gc.z;
     if (ldb == 8 && ldd == 8 && Gd == Gb + 4) {

@@ -355,6 +355,15 @@ class GraphPlan:
             q_ca, q_db = inputs["id4_reduce_ca"], inputs["id4_expand_db"]
             self.q_c, self.q_a = RowIndex(id_c[q_ca], A), RowIndex(id_a[q_ca], A)
             self.q_d, self.q_b = RowIndex(id_c[q_db], A), RowIndex(id_a[q_db], A)
+            # periodic batches (pbc.PeriodicQuadGraphBuilder): the image of every interaction edge's source atom, int32
+            # (n_int,3), and the interaction edges grouped by structure for the stress (they are sorted by their target atom,
+            # so by structure: no sort, `warm` only takes the segment offsets)
+            ioffs = inputs.get("int_cell_offsets")
+            self.int_cell_offsets = None if ioffs is None else ioffs.to(torch.int32).contiguous()
+            self.int_mol = self.q_db32 = None
+            if ioffs is not None:
+                self.q_db32 = q_db.to(torch.int32).contiguous()       # the expand edge d -> b of every quadruplet (pbc_quad.hip)
+                self.int_mol = RowIndex(inputs["batch_seg"].index_select(0, i_a.long()), self.n_mol, is_sorted=True)
         self.device = dev
 
     @staticmethod
@@ -378,6 +387,8 @@ class GraphPlan:
             # likewise the c -> a <- b structures of the intermediate triplets and `reduce_cab` (a sort of Q keys): only the
             # composite closure's calculate_angles reads them, on the main stream — built on first use there
             out += [self.quad_geom[k] for k in ("a_of_exp", "b_of_exp", "d_of_exp")]
+            if self.int_mol is not None:
+                out.append(self.int_mol)
         return out
 
     def late_indices(self):

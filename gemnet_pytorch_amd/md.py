@@ -48,7 +48,7 @@ class DeviceMolecule:
         self.cell = None if cell is None else np.asarray(cell, dtype=np.float64).reshape(3, 3)
         self.pbc = np.ones(3, dtype=bool) if pbc is None else np.asarray(pbc, dtype=bool).reshape(3)
         if self.cell is not None and not triplets_only:
-            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
         self.R = R
         self.Z = Z
         self.N = np.array([len(Z)], dtype=np.int32)
@@ -88,7 +88,7 @@ def predict_periodic(model, inputs, stress=False, to_host=False):
     if not R.is_cuda:
         raise RuntimeError("periodic structures run on a HIP device only (no CPU fallback); DeviceMolecule.to('cuda')")
     if not model.triplets_only:
-        raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+        raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
     if stress and getattr(model, "direct_forces", False):
         raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
     pbc = np.asarray(inputs["pbc"].cpu().numpy(), dtype=bool).reshape(-1, 3)

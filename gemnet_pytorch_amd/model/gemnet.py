@@ -95,6 +95,10 @@ class GemNet(torch.nn.Module):
         # opt-in: a direct-force model (`direct_forces=True`) serves periodic batches on the constant-weight inference path
         # (_forward_periodic_direct: no autograd, forces (A,1,3), no stress).  False: such a call raises
         self.periodic_direct_forces = False
+        # opt-in: a GemNet-Q (`triplets_only=False`, forces by autograd) serves periodic batches in eval mode — the index arrays
+        # of pbc.PeriodicQuadGraphBuilder, the quadruplet geometry on the edge and interaction-edge vectors (csrc/pbc_quad.hip):
+        # (E, F[, S]).  False: such a call raises.  Training and direct forces with a cell stay GemNet-T only
+        self.periodic_quadruplets = False
         # arithmetic of the LDS-resident Dense stacks: None = the package default ("h3": fp32 operands as two fp16 planes,
         # three products), "split6" = three bf16 planes / six products (fp32 exponent range), "f32" = the f32-input MFMA — all
         # three at fp32 accuracy (force MAE 1e-6 .. 4e-6 eV/A against float64).  Single-plane bf16 / three-product modes exist
@@ -203,8 +207,9 @@ class GemNet(torch.nn.Module):
         return angle_cab, angle_abd, angle_cabd
 
     # ---------------------------------------------------------------------------------- forward
-    def _energy(self, R, plan, V=None, force_terms=False):
+    def _energy(self, R, plan, V=None, force_terms=False, Vint=None):
         """V: the (E,3) edge vectors of a periodic batch (pbc.edge_vectors; the leaf the force and stress are taken from).
+        Vint: the (n_int,3) interaction-edge vectors of a periodic GemNet-Q batch (pbc.int_edge_vectors; the second leaf).
         `force_terms` (direct forces): return the output blocks' per-edge force terms as a list instead of their sum."""
         T = self.triplets_only
         b3 = self.cbf_basis3
@@ -306,9 +311,16 @@ class GemNet(torch.nn.Module):
             b4, qg = self.cbf_basis, plan.quad_geom
             # interaction-edge radial basis (cutoff = int_cutoff), a-b<-d angles and the quadruplet
             # harmonics, each one launch, straight from the positions
-            _, _, _, rad4 = ops.edge_basis(R, None, plan.int_b, plan.int_a, b4.z_ln, b4.n_ln, b4.cutoff, b4.p,
-                                           want_rbf=False)
-            y_abd = ops.trip_basis(R, qg["a_of_exp"], qg["b_of_exp"], qg["d_of_exp"], self.num_spherical)
+            if V is not None:
+                # periodic batch: the same three launches on the vectors (csrc/pbc_quad.hip) — u = Vint, v = -V[d -> b] for
+                # the a - b <- d angle; -V[c -> a], -Vint[a - b], -V[d -> b] for the quadruplet
+                from .. import pbc
+                rad4 = pbc.radial_basis(Vint, b4.z_ln, b4.n_ln, b4.cutoff, b4.p)
+                y_abd = pbc.trip_basis2(Vint, V, plan, self.num_spherical)
+            else:
+                _, _, _, rad4 = ops.edge_basis(R, None, plan.int_b, plan.int_a, b4.z_ln, b4.n_ln, b4.cutoff, b4.p,
+                                               want_rbf=False)
+                y_abd = ops.trip_basis(R, qg["a_of_exp"], qg["b_of_exp"], qg["d_of_exp"], self.num_spherical)
             S, NR = self.num_spherical, b4.num_radial
             cbf4 = None
             if self.mlp_cbf4.bias is None and not self.mlp_cbf4.act:
@@ -319,8 +331,11 @@ class GemNet(torch.nn.Module):
                 cbf4 = (ops.gather_rows(rad4, plan.intm_ab) * y_abd[:, :, None]).reshape(-1, S * NR)
             # (angle form for the published quadruplet widths: the bilinear kernels rebuild Y_lm from 16 B per quadruplet)
             ang = self.int_blocks[0].quad_interaction.mlp_sbf.weight.shape[:2] == (32, 32)
-            sbf4 = (rad3, ops.share_gradient(ops.quad_basis(R, plan.q_c, plan.q_a, plan.q_b, plan.q_d, S, plan=plan,
-                                                            angle_form=ang)))
+            if V is not None:
+                sbf4 = (rad3, ops.share_gradient(pbc.quad_basis(V, Vint, plan, S, angle_form=ang)))
+            else:
+                sbf4 = (rad3, ops.share_gradient(ops.quad_basis(R, plan.q_c, plan.q_a, plan.q_b, plan.q_d, S, plan=plan,
+                                                                angle_form=ang)))
         elif not T:
             qi = self.int_blocks[0].quad_interaction.mlp_sbf.weight
             if (ops.train2_enabled() and not self.direct_forces and self.num_spherical == 7
@@ -677,7 +692,20 @@ class GemNet(torch.nn.Module):
     def _check_periodic(self, inputs, stress=False):
         """What a cell is not supported with raises (no silent molecular result)."""
         if not self.triplets_only:
-            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
+            if not getattr(self, "periodic_quadruplets", False):
+                raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q (eval-mode GemNet-Q "
+                                          "is opt-in: model.periodic_quadruplets = True, pbc.PeriodicQuadGraphBuilder)")
+            if self.direct_forces:
+                raise NotImplementedError("periodic cells: a direct-force GemNet-Q is not served with a cell")
+            graph = self.force_graph
+            if graph is None:
+                graph = self.training and torch.is_grad_enabled()
+            if graph:
+                raise NotImplementedError("periodic cells: GemNet-Q runs on the first-order (eval) path only; training with a "
+                                          "cell is GemNet-T only")
+            if "int_cell_offsets" not in inputs:
+                raise ValueError("a periodic GemNet-Q batch needs 'int_cell_offsets' and the quadruplet arrays of "
+                                 "pbc.PeriodicQuadGraphBuilder")
         if self.direct_forces:
             if not getattr(self, "periodic_direct_forces", False):
                 raise NotImplementedError("periodic cells: forces by autograd only, not direct_forces")
@@ -686,14 +714,16 @@ class GemNet(torch.nn.Module):
             if stress:
                 raise NotImplementedError("periodic cells: a direct-force model has no stress (its forces are not the "
                                           "gradient of its energy)")
+        # (the messages of a quadruplet model name it: every refusal of a periodic GemNet-Q batch says "GemNet-Q")
+        who = "periodic cells" if self.triplets_only else "periodic cells (GemNet-Q)"
         if self.num_targets != 1:
-            raise NotImplementedError("periodic cells: one target only")
+            raise NotImplementedError(f"{who}: one target only")
         if AutomaticFit.fitting_mode:
-            raise NotImplementedError("periodic cells: no scale-factor fitting with a cell")
+            raise NotImplementedError(f"{who}: no scale-factor fitting with a cell")
         # (padded batches — padded.PaddedGraphRunner(cell=...) — are ordinary periodic batches: the dummy molecule has a cell
         #  row of its own and its pad edges carry offset 0; `_guard_rows` / `max_in_degree` mean what they mean for molecules)
         if inputs["R"].requires_grad:
-            raise NotImplementedError("periodic cells: positions that take part in an autograd graph are not supported")
+            raise NotImplementedError(f"{who}: positions that take part in an autograd graph are not supported")
 
     def _forward_periodic(self, R, plan, cell):
         """E, F, S of a periodic batch.  Everything depends on R through the edge vectors V (the shift is constant), so the
@@ -701,13 +731,25 @@ class GemNet(torch.nn.Module):
         S_b = -1/|det cell_b| sum_{e of b} V_e (x) G_e."""
         from .. import pbc
         V = pbc.edge_vectors(R, plan, cell).requires_grad_(True)
+        # GemNet-Q (`periodic_quadruplets`): a second leaf, the interaction-edge vectors Vint — the quadruplet geometry needs
+        # exactly V and Vint — and the same ONE gradient call: F and S add the interaction edges' terms
+        Vint = None if self.triplets_only else pbc.int_edge_vectors(R, plan, cell).requires_grad_(True)
         with ops.weight_cache(self._wcache), ops.fused_first_order(True), ops.param_grads(False), \
                 ops.train2(False, None), ops.chain_mode(self.matmul_precision), ops.position_graph(False), \
                 torch.enable_grad():
-            E_mol, _, _ = self._energy(R.detach(), plan, V=V)
-            G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0))[0]
-        F = pbc.forces(G, plan)
-        S = pbc.stress(V.detach(), G, plan, cell)
+            E_mol, _, _ = self._energy(R.detach(), plan, V=V, Vint=Vint)
+            if Vint is None:
+                G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0))[0]
+            else:
+                G, Gint = torch.autograd.grad(E_mol, (V, Vint), grad_outputs=self._cotangent(E_mol, 0), allow_unused=True)
+        if Vint is None:
+            F = pbc.forces(G, plan)
+            S = pbc.stress(V.detach(), G, plan, cell)
+        else:
+            G = torch.zeros_like(V) if G is None else G
+            Gint = torch.zeros_like(Vint) if Gint is None else Gint
+            F = pbc.forces_q(G, Gint, plan)
+            S = pbc.stress_q(V.detach(), G, Vint.detach(), Gint, plan, cell)
         return E_mol.detach(), F, S
 
     def _forward_periodic_direct(self, R, plan, cell):

@@ -28,7 +28,10 @@ from ._lib import check, ptr, require_device, stream
 from .graph import RowIndex
 
 KEYS = ["batch_seg", "id_undir", "id_swap", "id_c", "id_a", "id3_expand_ba", "id3_reduce_ca", "Kidx3", "cell_offsets"]
-MAX_IMAGES = 64       # images per axis and side the builder accepts (cutoff / perpendicular height)
+# PeriodicQuadGraphBuilder adds the reference's quadruplet keys and the images of the interaction edges
+KEYS_Q = ["id4_int_b", "id4_int_a", "id4_reduce_ca", "id4_expand_db", "id4_reduce_cab", "id4_expand_abd", "Kidx4",
+          "id4_reduce_intm_ca", "id4_expand_intm_db", "id4_reduce_intm_ab", "id4_expand_intm_ab", "int_cell_offsets"]
+MAX_IMAGES = 64      # images per axis and side the builder accepts (cutoff / perpendicular height)
 
 
 def image_extent(cell, pbc, cutoff):
@@ -49,7 +52,8 @@ class PeriodicGraphBuilder:
 
     def __init__(self, N, cutoff, int_cutoff=None, triplets_only=True, pbc=None, device="cuda"):
         if not triplets_only:
-            raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only; GemNet-Q has no periodic index build")
+            raise NotImplementedError("periodic cells: this class builds the GemNet-T (triplets_only=True) arrays only; the "
+                                      "GemNet-Q index arrays of a periodic batch come from PeriodicQuadGraphBuilder")
         N = np.asarray(N, dtype=np.int64).reshape(-1)
         self.B, self.A = int(len(N)), int(N.sum())
         self.cutoff = float(cutoff)
@@ -72,6 +76,11 @@ class PeriodicGraphBuilder:
 
     def __call__(self, R, cell, dtype=torch.int64):
         """R (A,3) device float32 | float64, cell (B,3,3) -> {key: tensor(dtype)} (distances rounded in R's dtype)."""
+        out, _ = self._build(R, cell)
+        return {k: (out[k] if dtype == torch.int32 else out[k].to(dtype)) for k in KEYS}
+
+    def _build(self, R, cell):
+        """-> (the int32 arrays of KEYS, workspace of the build: R, cell as the kernels read them, H, off, in_ptr)."""
         require_device(R)
         if R.dtype not in (torch.float32, torch.float64):
             raise TypeError("positions must be float32 or float64")
@@ -109,7 +118,74 @@ class PeriodicGraphBuilder:
             out[k] = new(T)
         check(lib.gn_pbc_index_trip(ptr(out["id_a"]), E, ptr(in_ptr), ptr(in_edge), ptr(off3), ptr(out["id3_reduce_ca"]),
                                     ptr(out["id3_expand_ba"]), ptr(out["Kidx3"]), stream()), "gn_pbc_index_trip")
-        return {k: (out[k] if dtype == torch.int32 else out[k].to(dtype)) for k in KEYS}
+        return out, dict(R=R, cell=cell, H=H, off=off, in_ptr=in_ptr)
+
+
+class PeriodicQuadGraphBuilder(PeriodicGraphBuilder):
+    """Device index build of periodic structures for GemNet-Q: the dict of `PeriodicGraphBuilder` (the same arrays, bit for
+    bit) + the reference's quadruplet keys (data_container.py:428-489) with every node identified by (atom, image) +
+    `int_cell_offsets` (n_int,3): interaction edge k = (id4_int_b -> id4_int_a) has b in the image int_cell_offsets[k] of a.
+    Order and image rule: include/gemnet_hip.h (gn_pbc_qindex_*); without images the arrays are `DeviceGraphBuilder`'s.
+
+        idx = PeriodicQuadGraphBuilder(N, cutoff, int_cutoff, pbc=pbc)(R, cell)
+
+    Four size read-backs per call (edges, triplets, interaction edges, intermediate triplets + quadruplets)."""
+
+    def __init__(self, N, cutoff, int_cutoff, pbc=None, device="cuda"):
+        super().__init__(N, cutoff, pbc=pbc, device=device)
+        self.int_cutoff = float(int_cutoff)
+
+    def check_cell(self, cell_host):
+        super().check_cell(cell_host)
+        ext = image_extent(cell_host, self.pbc_host, max(self.cutoff, self.int_cutoff))
+        if ext.max(initial=0) > MAX_IMAGES:
+            raise ValueError(f"int_cutoff / cell height needs {int(ext.max())} images per side (limit {MAX_IMAGES})")
+
+    def __call__(self, R, cell, dtype=torch.int64):
+        out, ws = self._build(R, cell)
+        R, cell, H, off, in_ptr = ws["R"], ws["cell"], ws["H"], ws["off"], ws["in_ptr"]
+        dev, i32, i64 = R.device, torch.int32, torch.int64
+        f64 = int(R.dtype == torch.float64)
+        lib = _lib.load()
+        A, E = self.A, 2 * H
+        new = lambda *s, t=i32: torch.empty(s, dtype=t, device=dev)
+        if H == 0:
+            in_ptr = torch.zeros(A + 1, dtype=i64, device=dev)      # (gn_pbc_index_fill leaves it unwritten without edges)
+        cnt = new(max(A, 1), t=i64)
+        off_int = torch.zeros(A + 1, dtype=i64, device=dev)
+        check(lib.gn_pbc_qindex_count(ptr(R), f64, ptr(cell), ptr(self.pbc), ptr(self.mol_off), ptr(self.atom_mol), self.B, A,
+                                      self.int_cutoff, ptr(cnt), ptr(off_int), stream()), "gn_pbc_qindex_count")
+        n_int = int(off_int[A].item())
+        if n_int >= 2 ** 31:
+            raise ValueError("number of periodic interaction edges exceeds int32")
+        out["id4_int_a"], out["id4_int_b"], out["int_cell_offsets"] = new(n_int), new(n_int), new(n_int, 3)
+        in_src, pos_src = new(max(E, 1)), new(max(E, 1))
+        cnt_ca, cnt_db = new(max(n_int, 1), t=i64), new(max(n_int, 1), t=i64)
+        off_ca, off_db = torch.zeros(n_int + 1, dtype=i64, device=dev), torch.zeros(n_int + 1, dtype=i64, device=dev)
+        cnt4, off4 = new(max(E, 1), t=i64), torch.zeros(E + 1, dtype=i64, device=dev)
+        check(lib.gn_pbc_qindex_int(ptr(R), f64, ptr(cell), ptr(self.pbc), ptr(self.mol_off), ptr(self.atom_mol), A,
+                                    self.int_cutoff, ptr(off_int), n_int, ptr(off), H, ptr(out["id_a"]), ptr(out["id_c"]),
+                                    ptr(out["cell_offsets"]), ptr(in_ptr), ptr(out["id4_int_a"]), ptr(out["id4_int_b"]),
+                                    ptr(out["int_cell_offsets"]), ptr(in_src), ptr(pos_src), ptr(cnt_ca), ptr(off_ca),
+                                    ptr(cnt_db), ptr(off_db), ptr(cnt4), ptr(off4), stream()), "gn_pbc_qindex_int")
+        n_ca, n_db, Q = (int(v) for v in torch.stack([off_ca[n_int], off_db[n_int], off4[E]]).tolist())
+        if max(n_ca, n_db) >= 2 ** 31:
+            raise ValueError("number of periodic intermediate triplets exceeds int32")
+        if Q >= 2 ** 31:
+            raise ValueError("number of periodic quadruplets exceeds int32")
+        out.update(id4_reduce_intm_ca=new(n_ca), id4_reduce_intm_ab=new(n_ca), id4_expand_intm_db=new(n_db),
+                   id4_expand_intm_ab=new(n_db))
+        for k in ("id4_reduce_ca", "id4_expand_db", "id4_reduce_cab", "id4_expand_abd", "Kidx4"):
+            out[k] = new(Q)
+        check(lib.gn_pbc_qindex_quad(ptr(self.mol_off), ptr(self.atom_mol), A, ptr(off), H, ptr(out["id_a"]), ptr(out["id_c"]),
+                                     ptr(out["cell_offsets"]), ptr(in_ptr), ptr(in_src), ptr(pos_src), ptr(off_int), n_int,
+                                     ptr(out["id4_int_a"]), ptr(out["id4_int_b"]), ptr(out["int_cell_offsets"]), ptr(off_ca),
+                                     ptr(off_db), n_ca, n_db, ptr(off4), Q, ptr(out["id4_reduce_intm_ca"]),
+                                     ptr(out["id4_reduce_intm_ab"]), ptr(out["id4_expand_intm_db"]),
+                                     ptr(out["id4_expand_intm_ab"]), ptr(out["id4_reduce_ca"]), ptr(out["id4_expand_db"]),
+                                     ptr(out["id4_reduce_cab"]), ptr(out["id4_expand_abd"]), ptr(out["Kidx4"]), stream()),
+              "gn_pbc_qindex_quad")
+        return {k: (out[k] if dtype == torch.int32 else out[k].to(dtype)) for k in KEYS + KEYS_Q}
 
 
 def build_indices_periodic(R, N, cell, cutoff, pbc=None, dtype=torch.int64):
@@ -205,9 +281,150 @@ def trip_basis(V, trip, S):
     return _TripBasisVec.apply(V, trip, int(S))
 
 
+# ------------------------------------------------------------------------------------------------ GemNet-Q on vectors
+def int_edge_vectors(R, plan, cell):
+    """Vint (n_int,3) = R[id4_int_a] - (R[id4_int_b] + int_cell_offsets @ cell[b]): `edge_vectors` of the interaction edges."""
+    require_device(R, cell)
+    R = R.detach().float().contiguous()
+    cell = cell.detach().float().contiguous()
+    V = torch.empty((plan.n_int, 3), device=R.device, dtype=torch.float32)
+    check(_lib.load().gn_pbc_edge_vec_f32(ptr(R), ptr(plan.int_b.idx32), ptr(plan.int_a.idx32), ptr(plan.batch_seg.idx32),
+                                          ptr(cell), ptr(plan.int_cell_offsets), ptr(V), plan.n_int, stream()),
+          "gn_pbc_edge_vec_f32")
+    return V
+
+
+class _RadBasisVec(torch.autograd.Function):
+    """Vint -> rad (n_int,S,NR), the spherical-Bessel radial basis of the interaction edges (no Bessel rbf, no distance
+    output: gn_edge_basis_vec_fwd_f32 / _bwd_f32 with those operands absent, as ops.edge_basis(want_rbf=False))."""
+
+    @staticmethod
+    def forward(ctx, V, z, nrm, cutoff, p):
+        E = V.shape[0]
+        S, NR = z.shape
+        D = torch.empty(E, device=V.device, dtype=torch.float32)
+        rad = torch.empty((E, S, NR), device=V.device, dtype=torch.float32)
+        check(_lib.load().gn_edge_basis_vec_fwd_f32(ptr(V), None, ptr(z), ptr(nrm), ptr(D), None, ptr(rad), E, NR, S, cutoff, p,
+                                                    stream()), "gn_edge_basis_vec_fwd_f32")
+        ctx.save_for_backward(V, z, nrm)
+        ctx.cfg = (cutoff, p)
+        return rad
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rad):
+        V, z, nrm = ctx.saved_tensors
+        cutoff, p = ctx.cfg
+        S, NR = z.shape
+        E = V.shape[0]
+        W = torch.empty((E, 3), device=V.device, dtype=torch.float32)
+        check(_lib.load().gn_edge_basis_vec_bwd_f32(None, None, ptr(g_rad.float().contiguous()), ptr(V), None, ptr(z), ptr(nrm),
+                                                    ptr(W), E, NR, S, cutoff, p, stream()), "gn_edge_basis_vec_bwd_f32")
+        return W, None, None, None, None
+
+
+def radial_basis(V, z, nrm, cutoff, p):
+    return _RadBasisVec.apply(V, z, nrm, float(cutoff), int(p))
+
+
+class _TripBasisVec2(torch.autograd.Function):
+    """Vint, V -> Y_l0 of the a - b <- d angle of every intermediate triplet (u = Vint[intm_ab], v = -V[intm_db]); adjoint:
+    dE/dVint summed over the contiguous triplets of an interaction edge, dE/dV over the intm_db CSR."""
+
+    @staticmethod
+    def forward(ctx, Vint, V, plan, S):
+        T = plan.n_intm
+        Y = torch.empty((T, S), device=V.device, dtype=torch.float32)
+        check(_lib.load().gn_trip_basis_vec2_fwd_f32(ptr(Vint), ptr(plan.intm_ab.idx32), ptr(V), ptr(plan.intm_db.idx32), ptr(Y),
+                                                     T, S, stream()), "gn_trip_basis_vec2_fwd_f32")
+        ctx.save_for_backward(Vint, V)
+        ctx.plan = plan
+        return Y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gY):
+        Vint, V = ctx.saved_tensors
+        plan = ctx.plan
+        T, S = gY.shape
+        gY = gY.float().contiguous()
+        GU = torch.empty((T, 3), device=V.device, dtype=torch.float32)
+        GW = torch.empty((T, 3), device=V.device, dtype=torch.float32)
+        check(_lib.load().gn_trip_basis_vec2_bwd_f32(ptr(gY), ptr(Vint), ptr(plan.intm_ab.idx32), ptr(V),
+                                                     ptr(plan.intm_db.idx32), ptr(GU), ptr(GW), T, S, stream()),
+              "gn_trip_basis_vec2_bwd_f32")
+        return (K.segsum(GU, *plan.intm_ab.csr, plan.n_int), K.segsum(GW, *plan.intm_db.csr, plan.n_edges), None, None)
+
+
+def trip_basis2(Vint, V, plan, S):
+    return _TripBasisVec2.apply(Vint, V, plan, int(S))
+
+
+class _QuadBasisVec(torch.autograd.Function):
+    """V, Vint -> the tensor basis of every quadruplet from uac = -V[id4_reduce_ca], uab = -Vint[k], ubd = -V[id4_expand_db]:
+    Y_lm rows (Q,S^2), or in angle form (Q,4) (sin, cos) of the two angles for the *_ang bilinear kernels.  Adjoint, reduced
+    as ops._quad_adjoint does: per reduce edge over the contiguous quadruplet segments (-> dE/dV rows), per intermediate
+    triplet through the CSR of id4_expand_abd ([dE/dVint | dE/dV[db]] rows of 32 B), then onto the V rows through the intm_db
+    CSR and onto the Vint rows over the contiguous intermediate triplets of an interaction edge.  No atomics, fixed order."""
+
+    @staticmethod
+    def forward(ctx, V, Vint, plan, S, angle_form):
+        Q = plan.quad.size
+        lib, q = _lib.load(), plan.quad
+        idx = (ptr(q.reduce.idx32), ptr(quad_expand_db(plan)), ptr(q.expand.idx32), ptr(plan.intm_ab.idx32))
+        if angle_form:
+            Y = torch.empty((Q, 4), device=V.device, dtype=torch.float32)
+            check(lib.gn_quad_angles_vec_fwd_f32(ptr(V), ptr(Vint), *idx, ptr(Y), Q, stream()), "gn_quad_angles_vec_fwd_f32")
+        else:
+            Y = torch.empty((Q, S * S), device=V.device, dtype=torch.float32)
+            check(lib.gn_quad_basis_vec_fwd_f32(ptr(V), ptr(Vint), *idx, ptr(Y), Q, S, stream()), "gn_quad_basis_vec_fwd_f32")
+        ctx.save_for_backward(V, Vint)
+        ctx.cfg = (plan, S, angle_form)
+        return Y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gY):
+        V, Vint = ctx.saved_tensors
+        plan, S, angle_form = ctx.cfg
+        Q = plan.quad.size
+        lib, q = _lib.load(), plan.quad
+        idx = (ptr(q.reduce.idx32), ptr(quad_expand_db(plan)), ptr(q.expand.idx32), ptr(plan.intm_ab.idx32))
+        gY = gY.float().contiguous()
+        Gc = torch.empty((Q, 3), device=V.device, dtype=torch.float32)
+        Gbd = torch.empty((Q, 8), device=V.device, dtype=torch.float32)       # (the kernels write the two pad lanes themselves)
+        if angle_form:
+            check(lib.gn_quad_angles_vec_bwd_f32(ptr(gY), ptr(V), ptr(Vint), *idx, ptr(Gc), ptr(Gbd), Q, stream()),
+                  "gn_quad_angles_vec_bwd_f32")
+        else:
+            check(lib.gn_quad_basis_vec_bwd_f32(ptr(gY), ptr(V), ptr(Vint), *idx, ptr(Gc), ptr(Gbd), Q, S, stream()),
+                  "gn_quad_basis_vec_bwd_f32")
+        Ec = K.segsum(Gc, None, q.seg_off, plan.n_edges)
+        Ibd = K.segsum(Gbd, *q.expand.csr, q.n_expand)
+        gV = Ec + K.segsum(Ibd[:, 4:7].contiguous(), *plan.intm_db.csr, plan.n_edges)
+        gVint = K.segsum(Ibd[:, 0:3].contiguous(), *plan.intm_ab.csr, plan.n_int)
+        return gV, gVint, None, None, None
+
+
+def quad_expand_db(plan):
+    """id4_expand_db as int32 (a periodic GemNet-Q plan keeps it: graph.GraphPlan)."""
+    return plan.q_db32
+
+
+def quad_basis(V, Vint, plan, S, angle_form=False):
+    from . import ops
+    return _QuadBasisVec.apply(V, Vint, plan, int(S), bool(angle_form and ops.USE_QUAD_ANGLES and S == 7))
+
+
 def forces(G, plan):
     """F (A,3) from G = -dE/dV: F = segsum(G, id_a) - segsum(G, id_c)."""
     return K.segsum_multi([(G, *plan.id_a.csr, 1.0), (G, *plan.id_c.csr, -1.0)], plan.n_atoms)
+
+
+def forces_q(G, Gint, plan):
+    """F (A,3) of a periodic GemNet-Q batch from G = -dE/dV and Gint = -dE/dVint: the four edge -> atom sums in one launch."""
+    return K.segsum_multi([(G, *plan.id_a.csr, 1.0), (G, *plan.id_c.csr, -1.0), (Gint, *plan.int_a.csr, 1.0),
+                           (Gint, *plan.int_b.csr, -1.0)], plan.n_atoms)
 
 
 def direct_forces(terms, V, plan, coupled):
@@ -268,6 +485,17 @@ def stress(V, G, plan, cell):
     check(_lib.load().gn_pbc_stress_f32(ptr(V), ptr(G.contiguous()), ptr(perm), ptr(seg), ptr(cell), plan.n_mol, -1.0, ptr(S),
                                         stream()), "gn_pbc_stress_f32")
     return S
+
+
+def stress_q(V, G, Vint, Gint, plan, cell):
+    """S (B,3,3) of a periodic GemNet-Q batch: -1/|det cell_b| (sum_e V_e (x) G_e + sum_k Vint_k (x) Gint_k) over the edges and
+    interaction edges of structure b (two launches of gn_pbc_stress_f32; the interaction edges are grouped by `plan.int_mol`)."""
+    _, seg = plan.int_mol.csr
+    cell_f = cell.detach().float().contiguous()
+    Si = torch.empty((plan.n_mol, 3, 3), device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_pbc_stress_f32(ptr(Vint), ptr(Gint.contiguous()), None, ptr(seg), ptr(cell_f), plan.n_mol, -1.0, ptr(Si),
+                                        stream()), "gn_pbc_stress_f32")
+    return stress(V, G, plan, cell) + Si
 
 
 class _ForceStress(torch.autograd.Function):

@@ -256,7 +256,7 @@ class DynamicForceField:
         if self.periodic:
             from .pbc import PeriodicGraphBuilder
             if not model.triplets_only:
-                raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only")
+                raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
             self.builder = PeriodicGraphBuilder(self.N_host, cutoff, pbc=pbc, device=Z.device)
             # private cell buffer: the caller's tensor may change between the step and its repetition after a re-size
             self.cell = torch.as_tensor(cell).detach().to(device=Z.device, dtype=torch.float32).reshape(-1, 3, 3).clone()

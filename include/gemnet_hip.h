@@ -821,6 +821,75 @@ int gn_direct_force_f32(const float* terms, const float* V, const int32_t* id_sw
 int gn_direct_force_bwd_f32(const float* gF, const float* V, const int32_t* id_swap, const int32_t* id_a, float* g,
                             int64_t n_atoms, int64_t n_edges, int T, void* stream);
 
+/* ---- periodic cells, GemNet-Q index build (csrc/pbc_index_q.hip; additive, ABI 16) -------------------------------------------
+ * The quadruplet arrays of data_container.py:428-489 on top of the periodic edge list above (gn_pbc_index_count / _fill: id_a,
+ * id_c, cell_offsets (2H,3), off_half (A+1), in_ptr (A+1)), every node identified by (atom, image).  A quadruplet
+ * c -> a - b <- d has a in image 0, c in n_c = cell_offsets[ca], b in n_b = int_cell_offsets[ab], d in n_b + cell_offsets[db].
+ * Interaction edges (b -> a, n): |R_a - (R_b + n cell)| <= int_cutoff, every image except (b == a, n == 0), both directions,
+ * ordered by (a, b, n lexicographic); the distance of a pair is tested once, on its canonical forward form (a < b, or a == b
+ * and n lexicographically positive; the other direction tests (b, a, -n)), rounded in the dtype of R like the edge list.
+ * Intermediate triplets of interaction edge k = (b -> a): id4_reduce_intm_ca lists the in-edges of a, id4_expand_intm_db those
+ * of b, each ordered by (source atom, cell offset lexicographic) (in_src, with pos_src (2H) the position of an edge in the
+ * list of its target); id4_reduce_intm_ab / id4_expand_intm_ab repeat k.  Quadruplets: the cross product of the two lists of
+ * k minus those with (c, n_c) == (b, n_b), (a, 0) == (d, n_b + n_db) or (c, n_c) == (d, n_b + n_db), ordered by
+ * (id4_reduce_ca, id4_expand_db, k); id4_reduce_cab / id4_expand_abd point into the intermediate lists, Kidx4 counts inside a
+ * reduce segment.  Without images all of this is gn_index_gpu_stage1/2's output, array for array.
+ *   gn_pbc_qindex_count: cnt (A) int64 interaction edges per target atom, off_int (A+1) their exclusive scan.
+ *   gn_pbc_qindex_int:   int_a, int_b (n_int), int_cell_offsets (n_int,3); in_src, pos_src (2H); cnt_ca, cnt_db (n_int) and
+ *                        off_ca, off_db (n_int+1): intermediate triplets per interaction edge and their scans; cnt4 (2H),
+ *                        off4 (2H+1): quadruplets per reduce edge and their scan (Q = off4[2H]).  in_ptr must hold zeros when H = 0.
+ *   gn_pbc_qindex_quad:  the four intermediate arrays (n_ca = off_ca[n_int], n_db = off_db[n_int]) and the five (Q) arrays.
+ * All counts int64; hipErrorInvalidValue when one of them does not fit int32.  One thread per atom / interaction edge, one
+ * wavefront per reduce edge placing its rows by a wave scan: deterministic, no atomics. */
+int gn_pbc_qindex_count(const void* R, int is_f64, const void* cell, const uint8_t* pbc, const int32_t* mol_off,
+                        const int32_t* atom_mol, int B, int A, double int_cutoff, int64_t* cnt, int64_t* off_int, void* stream);
+int gn_pbc_qindex_int(const void* R, int is_f64, const void* cell, const uint8_t* pbc, const int32_t* mol_off,
+                      const int32_t* atom_mol, int A, double int_cutoff, const int64_t* off_int, int64_t n_int,
+                      const int64_t* off_half, int64_t H, const int32_t* id_a, const int32_t* id_c, const int32_t* cell_offsets,
+                      const int64_t* in_ptr, int32_t* int_a, int32_t* int_b, int32_t* int_cell_offsets, int32_t* in_src,
+                      int32_t* pos_src, int64_t* cnt_ca, int64_t* off_ca, int64_t* cnt_db, int64_t* off_db, int64_t* cnt4,
+                      int64_t* off4, void* stream);
+int gn_pbc_qindex_quad(const int32_t* mol_off, const int32_t* atom_mol, int A, const int64_t* off_half, int64_t H,
+                       const int32_t* id_a, const int32_t* id_c, const int32_t* cell_offsets, const int64_t* in_ptr,
+                       const int32_t* in_src, const int32_t* pos_src, const int64_t* off_int, int64_t n_int, const int32_t* int_a,
+                       const int32_t* int_b, const int32_t* int_cell_offsets, const int64_t* off_ca, const int64_t* off_db,
+                       int64_t n_ca, int64_t n_db, const int64_t* off4, int64_t Q, int32_t* id4_reduce_intm_ca,
+                       int32_t* id4_reduce_intm_ab, int32_t* id4_expand_intm_db, int32_t* id4_expand_intm_ab,
+                       int32_t* id4_reduce_ca, int32_t* id4_expand_db, int32_t* id4_reduce_cab, int32_t* id4_expand_abd,
+                       int32_t* Kidx4, void* stream);
+
+/* ---- periodic cells, GemNet-Q geometry on vectors (csrc/pbc_quad.hip; additive, ABI 16) --------------------------------------
+ * V (E,3): the edge vectors; Vint (n_int,3): the interaction-edge vectors, Vint[k] = R[id4_int_a[k]] - (R[id4_int_b[k]] +
+ * int_cell_offsets[k] cell) (gn_pbc_edge_vec_f32 on the interaction-edge arrays).
+ *   gn_trip_basis_vec2_fwd_f32: Y (T,S) = Y_l0 of the angle between u = U[iu[t]] and v = -W[iw[t]] — the a - b <- d angle of
+ *     the intermediate triplets with U = Vint, iu = id4_expand_intm_ab, W = V, iw = id4_expand_intm_db (the two-array twin of
+ *     gn_trip_basis_vec_fwd_f32; clamp max(|u x v|, 1e-9) as there).
+ *   gn_trip_basis_vec2_bwd_f32: GU[t] = dE/dU[iu[t]], GW[t] = dE/dW[iw[t]] (T,3) per triplet.
+ * Quadruplet q with reduce edge q_ca[q], expand edge q_db[q] and intermediate triplet q_abd[q] (id4_expand_abd) hanging on
+ * interaction edge k = intm_ab[q_abd[q]] (id4_expand_intm_ab): uac = -V[q_ca], uab = -Vint[k], ubd = -V[q_db]; the math of
+ * gn_quad_basis_* / gn_quad_angles_* on those three vectors (csrc/quad_math.h).  The reference's clamp max(|u x v|, 1e-9) is
+ * decided RELATIVE to the vectors' lengths (sin < 1e-5): an exactly collinear c - a - b / a - b - d (an atom and its images)
+ * gives the azimuth pi / 2 and no azimuth gradient, an exactly planar quadruplet no azimuth gradient — what exact arithmetic
+ * gives on the clamp, where fp32 leaves a rounding residue above the absolute 1e-9:
+ *   gn_quad_basis_vec_fwd_f32:  Y (Q,S^2) = Y_lm(Phi_cab, Theta_cabd), S <= 7
+ *   gn_quad_angles_vec_fwd_f32: ang (Q,4) = (sin, cos) of Phi_cab and of Theta_cabd
+ *   gn_quad_basis_vec_bwd_f32 (gY (Q,S^2)) / gn_quad_angles_vec_bwd_f32 (g_ang (Q,4) = (dE/dPhi_cab, dE/dTheta_cabd, -, -)):
+ *     Gc (Q,3) = dE/dV[q_ca[q]] and Gbd (Q,8) = [dE/dVint[k] xyz, 0, dE/dV[q_db[q]] xyz, 0] per quadruplet (pad lanes written).
+ * One thread per triplet / quadruplet, no atomics; T = 0 / Q = 0 return 0 without a launch. */
+int gn_trip_basis_vec2_fwd_f32(const float* U, const int32_t* iu, const float* W, const int32_t* iw, float* Y, int64_t T, int S,
+                               void* stream);
+int gn_trip_basis_vec2_bwd_f32(const float* gY, const float* U, const int32_t* iu, const float* W, const int32_t* iw, float* GU,
+                               float* GW, int64_t T, int S, void* stream);
+int gn_quad_basis_vec_fwd_f32(const float* V, const float* Vint, const int32_t* q_ca, const int32_t* q_db, const int32_t* q_abd,
+                              const int32_t* intm_ab, float* Y, int64_t Q, int S, void* stream);
+int gn_quad_basis_vec_bwd_f32(const float* gY, const float* V, const float* Vint, const int32_t* q_ca, const int32_t* q_db,
+                              const int32_t* q_abd, const int32_t* intm_ab, float* Gc, float* Gbd, int64_t Q, int S,
+                              void* stream);
+int gn_quad_angles_vec_fwd_f32(const float* V, const float* Vint, const int32_t* q_ca, const int32_t* q_db, const int32_t* q_abd,
+                               const int32_t* intm_ab, float* ang, int64_t Q, void* stream);
+int gn_quad_angles_vec_bwd_f32(const float* g_ang, const float* V, const float* Vint, const int32_t* q_ca, const int32_t* q_db,
+                               const int32_t* q_abd, const int32_t* intm_ab, float* Gc, float* Gbd, int64_t Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

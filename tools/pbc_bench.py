@@ -19,6 +19,11 @@ eager periodic direct-force calls (for a kernel trace: launches per call = calls
 force loss, ONE first-order backward, fused optimizer) beside the autograd-force PeriodicTrainStep of `--train` in the same
 process, in alternating rounds — `direct_train_eager_ms` / `autograd_train_eager_ms`, `*_train_graph_ms` (captured step), `*_rounds`;
 with `--eager-only` nothing but eager direct-force training steps (for a kernel trace).
+`--quad --int-cutoff X` times GemNet-Q (the same architecture with `triplets_only=False`, GemNet.periodic_quadruplets; index arrays of
+pbc.PeriodicQuadGraphBuilder) on the box: `quad_eager_ms` (E, F, S), `quad_graph_ms` (fixed-list replay), `quad_build_ms` (the index
+build with its read-backs), the edge / interaction-edge / intermediate-triplet / quadruplet counts and the peak device memory.
+The quadruplet count grows like cutoff^6 int_cutoff^3: at the reference's int_cutoff = 10 a 192-atom box has ~1e8; the default
+X = 5.0 keeps it below 3e7.
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -64,7 +69,7 @@ def timed(fn, steps, warmup):
     return t0.elapsed_time(t1) / steps
 
 
-def make_model(cutoff=5.0, direct=False, coupled=False):
+def make_model(cutoff=5.0, direct=False, coupled=False, quad=False, int_cutoff=10.0):
     """The 4-block, 128-wide GemNet-T of this tool (seeded weights, fitted scale factors), on the host; `direct`: the
     direct-force model of the same architecture with the periodic switch set."""
     from gemnet_pytorch_amd.model.gemnet import GemNet
@@ -74,12 +79,36 @@ def make_model(cutoff=5.0, direct=False, coupled=False):
                num_before_skip=1, num_after_skip=1, num_concat=1, num_atom=2, triplets_only=True, cutoff=cutoff)
     if direct:
         cfg.update(direct_forces=True, forces_coupled=bool(coupled))
+    if quad:
+        cfg.update(triplets_only=False, int_cutoff=float(int_cutoff))
     scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
     params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
     model = GemNet(**cfg, scale_file=scale_file)
     model.load_state_dict(GO.expand_to_reference_state_dict(params))
     model.periodic_direct_forces = bool(direct)
+    model.periodic_quadruplets = bool(quad)
     return model
+
+
+def quad_times(Rd, Zd, Nd, celld, A, args):
+    """GemNet-Q on the periodic box: index build, eager call and fixed-list replay, the four counts and the peak memory."""
+    from gemnet_pytorch_amd.pbc import PeriodicQuadGraphBuilder
+    from gemnet_pytorch_amd.runtime import ForceGraphs
+    torch.cuda.reset_peak_memory_stats()
+    builder = PeriodicQuadGraphBuilder([A], args.cutoff, args.int_cutoff, device="cuda")
+    idx = builder(Rd, celld, dtype=torch.int32)
+    out = {"int_cutoff": args.int_cutoff, "edges": int(idx["id_a"].shape[0]), "interaction_edges": int(idx["id4_int_a"].shape[0]),
+           "intermediate_triplets": int(idx["id4_expand_intm_db"].shape[0]), "quadruplets": int(idx["id4_reduce_ca"].shape[0])}
+    print(json.dumps(out), flush=True)
+    out["quad_build_ms"] = timed(lambda: builder(Rd, celld, dtype=torch.int32), max(args.steps // 5, 2), 1)
+    model = make_model(args.cutoff, quad=True, int_cutoff=args.int_cutoff).to("cuda").eval()
+    per = dict(R=Rd, Z=Zd, N=Nd, cell=celld, **idx)
+    out["quad_eager_ms"] = timed(lambda: model(per, stress=True), args.steps, args.warmup)
+    fg = ForceGraphs(model, [per])
+    out["quad_graph_ms"] = timed(fg.replay, args.steps, args.warmup)
+    out["quad_graph_ns_per_quadruplet"] = 1e6 * out["quad_graph_ms"] / max(out["quadruplets"], 1)
+    out["peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    return out
 
 
 def random_walk(R, n, sigma=0.02, seed=5):
@@ -203,6 +232,8 @@ def main():
     ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
     ap.add_argument("--direct", action="store_true", help="time a direct-force model beside the autograd-force model")
     ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
+    ap.add_argument("--quad", action="store_true", help="time GemNet-Q (periodic_quadruplets) on the box")
+    ap.add_argument("--int-cutoff", type=float, default=5.0, help="--quad: the interaction cutoff (quadruplets ~ int_cutoff^3)")
     ap.add_argument("--eager-only", action="store_true", help="--direct: only eager direct-force calls / training steps (for a kernel trace)")
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -211,14 +242,16 @@ def main():
     from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
     from gemnet_pytorch_amd.runtime import DynamicForceField, ForceGraphs
 
-    model = make_model(args.cutoff).to("cuda").eval()
-
     R, Z, cell = water_box(args.side)
     A = len(R)
     Rd = torch.tensor(R, dtype=torch.float32, device="cuda")
     Zd = torch.tensor(Z, device="cuda").long()
     Nd = torch.tensor([A], device="cuda")
     celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
+    if args.quad:
+        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **quad_times(Rd, Zd, Nd, celld, A, args))))
+        return
+    model = make_model(args.cutoff).to("cuda").eval()
     idx = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
     per = dict(R=Rd, Z=Zd, N=Nd, cell=celld, **idx)
     mol = dict(R=Rd, Z=Zd, N=Nd, **build_indices_device(Rd, np.array([A]), args.cutoff, 10.0, True, dtype=torch.int32))
