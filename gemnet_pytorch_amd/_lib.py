@@ -49,7 +49,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = ABI.funcs[name][0]
     _lib = lib
-    return lib
+    return lib if TRACE is None else TRACE.proxy(lib)      # (also on the load itself: the first launch is traced too)
 
 
 def check(code, what):

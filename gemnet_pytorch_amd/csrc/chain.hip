@@ -249,12 +249,15 @@ __global__ __launch_bounds__(NT) void chain_kernel(const gn_chain_args P) {
         GN_STAMP(6);
         float v[RT][4];
         bool ok[RT][4];
+        // N need not be a multiple of 16: the last active wave's lanes with col >= N hold zero accumulators (wload) and own
+        // no element of any global operand — row * N + col is an element of the NEXT row (of nothing, after the last row)
+        const bool col_ok = col < N;
 #pragma unroll
         for (int t = 0; t < RT; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             v[t][r] = acc[t][r];
-            ok[t][r] = growb + 16 * t + r < M;
+            ok[t][r] = col_ok && growb + 16 * t + r < M;
           }
 #define GN_EACH(body)                                                     \
   _Pragma("unroll") for (int t = 0; t < RT; ++t)                          \

@@ -1698,6 +1698,8 @@ def bil_reduce_t_tan(ang, tang, D1, D2, sp):
     D1 = None if D1 is None else _f32c(D1)
     S, C = D2.shape[1], D2.shape[2]
     assert is_angle_form(ang, S) and tang.shape == ang.shape and (D1 is None or D1.shape == D2.shape)
+    if sp.size == 0:      # edges without a single quadruplet: nothing to expand (empty `ang` / `tang` have no address to hand over)
+        return torch.zeros((sp.n_expand, C), device=ang.device, dtype=torch.float32)
     rg = sp.row_grid if (USE_ROW_GRID and C == 32 and sp.ROW_TILE == 64) else None
     if rg is not None:
         # one pass, no per-quadruplet rows in memory (csrc/bilinear_ang.hip: bil_expand_rows_ang_tan_kernel)

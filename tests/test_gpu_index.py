@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import index_oracle as IO
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 
@@ -12,7 +13,7 @@ pytestmark = pytest.mark.gpu
 def _check(R, N, triplets_only, cutoff=5.0, int_cutoff=10.0):
     from gemnet_pytorch_amd.index_device import build_indices_device
     ref = IO.build_indices(R, N, cutoff, int_cutoff, triplets_only)
-    out = build_indices_device(torch.tensor(R, device="cuda"), N, cutoff, int_cutoff, triplets_only)
+    out = build_indices_device(put(torch.tensor(R)), N, cutoff, int_cutoff, triplets_only)
     assert sorted(out) == sorted(ref)
     for k, v in ref.items():
         got = out[k].cpu().numpy()
@@ -28,7 +29,7 @@ def test_matches_reference_goldens(golden_indices, triplets_only):
         tag = f"{name}.{tagc}"
         R, N = g[f"{tag}.R"], g[f"{tag}.N"]
         from gemnet_pytorch_amd.index_device import build_indices_device
-        out = build_indices_device(torch.tensor(R, device="cuda"), N, 5.0, 10.0, triplets_only)
+        out = build_indices_device(put(torch.tensor(R)), N, 5.0, 10.0, triplets_only)
         keys = [k[len(tag) + 1:] for k in g if k.startswith(tag + ".") and k[len(tag) + 1:] not in ("R", "N")]
         ref = IO.canonicalize({k: g[f"{tag}.{k}"] for k in keys}, triplets_only)
         for k in keys:
@@ -54,11 +55,11 @@ def test_float64_positions_and_cutoff_boundary():
 
 def test_no_edges_and_int32_outputs():
     from gemnet_pytorch_amd.index_device import build_indices_device
-    R = torch.tensor([[0.0, 0, 0], [7.5, 0, 0]], device="cuda")
+    R = put(torch.tensor([[0.0, 0, 0], [7.5, 0, 0]]))
     out = build_indices_device(R, [2], 5.0, 10.0, False)
     assert out["batch_seg"].tolist() == [0, 0]
     assert all(v.numel() == 0 for k, v in out.items() if k != "batch_seg")
-    out32 = build_indices_device(torch.rand(12, 3, device="cuda") * 4, [12], 5.0, 10.0, True, dtype=torch.int32)
+    out32 = build_indices_device(put(torch.rand(12, 3) * 4), [12], 5.0, 10.0, True, dtype=torch.int32)
     assert all(v.dtype == torch.int32 for v in out32.values())
 
 
@@ -72,7 +73,7 @@ def test_model_forward_on_device_built_graph(golden_model):
     for tag in ("t2", "q1"):
         cfg, params, inputs = load_case(g, tag)
         model = build(cfg, params).eval()
-        R = inputs["R"].to("cuda")
+        R = put(inputs["R"])
         idx = build_indices_device(R, inputs["N"].numpy(), cfg.get("cutoff", 5.0), cfg.get("int_cutoff", 10.0), cfg["triplets_only"])
         dev = dict(Z=inputs["Z"].to("cuda"), R=R, N=inputs["N"].to("cuda"), **idx)
         E, F = model(dev)
@@ -93,7 +94,7 @@ def test_native_csr_build_equals_the_stable_sort(n, n_rows):
     if n > 10:
         keys[::3] = n_rows - 1                                  # heavy duplicates: stability matters
         keys[1::7] = torch.randint(0, max(n_rows // 100, 1), (len(keys[1::7]),), generator=g)
-    dev = keys.to("cuda")
+    dev = put(keys)
     perm, seg = K.csr_build(dev.to(torch.int32), n_rows)
     ref_perm = torch.argsort(dev, stable=True)
     bounds = torch.arange(n_rows + 1, device="cuda")
@@ -124,11 +125,11 @@ def test_expanded_csr_equals_the_stable_sort_of_the_item_keys():
         item_key = torch.repeat_interleave(row_of_edge.long(), cnt.long())
         want_perm = torch.argsort(item_key, stable=True).to(torch.int32)
         want_seg = torch.searchsorted(item_key[want_perm.long()].contiguous(), torch.arange(n_rows + 1)).to(torch.int32)
-        rk = row_of_edge.to("cuda")
+        rk = put(row_of_edge)
         if sorted_keys:
             perm_e, seg_e = None, K.seg_offsets(rk, n_rows)
         else:
             perm_e, seg_e = K.csr_build(rk, n_rows)
-        perm, seg = K.expanded_csr(perm_e, seg_e, so.to("cuda"), T)
+        perm, seg = K.expanded_csr(perm_e, seg_e, put(so), T)
         torch.cuda.synchronize()
         assert torch.equal(perm.cpu(), want_perm) and torch.equal(seg.cpu(), want_seg), (E, n_rows, sorted_keys)

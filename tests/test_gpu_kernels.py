@@ -9,6 +9,7 @@ import cpu_kernels as CK
 from gemnet_pytorch_amd import kernels as K
 from gemnet_pytorch_amd.graph import RowIndex, SegmentPlan
 from oracle import basis_oracle as B
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -30,7 +31,7 @@ def close(out, ref, rtol=2e-5, atol=None):
 
 
 def f32(t):
-    return t.to(torch.float32).to(DEV)
+    return put(t.to(torch.float32))
 
 
 @pytest.mark.parametrize("M,N,Kd", [(64, 128, 32), (300, 128, 128), (1000, 64, 128), (257, 32, 64),
@@ -432,6 +433,11 @@ def test_chain_kernel_vs_interpreter(M, width, mode, monkeypatch):
     MFMA kernel, on the split-operand bf16 kernel (packed weights) and on both layouts of the two-plane fp16 arithmetic
     ("h3" = csrc/chain2.hip, the default; "h3/row" = the row-resident csrc/chain4.hip, 1 .. 7 compute waves per workgroup,
     which also takes the programs chain2's row-scaled form refuses), against the float64 interpreter."""
+    _chain_vs_interpreter(M, width, mode, monkeypatch)
+
+
+def _chain_vs_interpreter(M, width, mode, monkeypatch):
+    """(shared with test_gpu_redzone.test_chain_kernel_at_row_tile_edges)"""
     if "/" in mode:
         mode, layout = mode.split("/")
         monkeypatch.setattr(K, "CHAIN_LAYOUT", layout)

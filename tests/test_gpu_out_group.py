@@ -14,6 +14,7 @@ from conftest import ROOT, SCALE_FILE
 from gemnet_pytorch_amd import _lib
 from gemnet_pytorch_amd import kernels as K
 from gemnet_pytorch_amd import ops
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 gpu = pytest.mark.gpu
 DEV = "cuda"
@@ -41,17 +42,17 @@ class AggCase:
         g = torch.Generator().manual_seed(5)
         rn = lambda *s: torch.randn(*s, generator=g)          # noqa: E731
         ia = torch.cat([torch.full((70,), 1), torch.randint(2, self.A, (self.E - 70,), generator=g)])
-        self.ia = ia[torch.randperm(self.E, generator=g)].int().to(DEV)
+        self.ia = put(ia[torch.randperm(self.E, generator=g)].int())
         self.perm, self.seg = K.csr_build(self.ia, self.A)
         deg = torch.bincount(self.ia.long().cpu(), minlength=self.A)
         assert deg[0] == 0 and deg[1] > 64
-        self.rbf = rn(self.E, NR).to(DEV)
-        self.m = [rn(self.E, C).to(DEV) for _ in range(self.G)]
-        self.W = [(rn(C, NR) / 4).to(DEV) for _ in range(self.G)]
-        self.scales = (0.5 + torch.rand(self.G, generator=g)).to(DEV)
+        self.rbf = put(rn(self.E, NR))
+        self.m = [put(rn(self.E, C)) for _ in range(self.G)]
+        self.W = [put(rn(C, NR) / 4) for _ in range(self.G)]
+        self.scales = put(0.5 + torch.rand(self.G, generator=g))
         self.sc = [float(v) for v in self.scales.cpu()]            # the same fp32 values as host scalars
-        self.g_out = rn(self.G, self.A, C).to(DEV)
-        self.prev_m = rn(self.E, C).to(DEV)                       # running gradient of the group with the accumulate bit
+        self.g_out = put(rn(self.G, self.A, C))
+        self.prev_m = put(rn(self.E, C))                       # running gradient of the group with the accumulate bit
         self.out1 = [K.rbf_aggregate_fwd(self.m[i], self.rbf, self.W[i], self.perm, self.seg, self.A, self.sc[i])
                      for i in range(self.G)]
         self.acc_group = 1
@@ -103,7 +104,7 @@ def test_grouped_aggregation_adjoint_matches_the_single_launches(agg, G):
 # -------------------------------------------------------------------------------------------------------- chain launch
 def _weights(G, n, seed):
     g = torch.Generator().manual_seed(seed)
-    return [[(torch.randn(C, C, generator=g) / C ** 0.5).to(DEV) for _ in range(G)] for _ in range(n)]
+    return [[put(torch.randn(C, C, generator=g) / C ** 0.5) for _ in range(G)] for _ in range(n)]
 
 
 def _forward_program(M, x, Ws, packed, zs, y):
@@ -148,8 +149,8 @@ def test_grouped_chain_is_bit_identical_to_separate_launches(mode, tile, G):
     g = torch.Generator().manual_seed(7)
     for rows in (16, 40, 48):      # 40: a partial tile at either height
         pitch = rows + 8           # eight rows between the groups that no launch may touch
-        x = torch.randn(G, pitch, C, generator=g).to(DEV)
-        fac = [(0.1 + torch.rand(G, pitch, C, generator=g)).to(DEV) for _ in range(5)]       # stand-ins for ssilu'(z)
+        x = put(torch.randn(G, pitch, C, generator=g))
+        fac = [put(0.1 + torch.rand(G, pitch, C, generator=g)) for _ in range(5)]       # stand-ins for ssilu'(z)
         for adjoint in (False, True):
             new = lambda: torch.full((G, pitch, C), SENTINEL, device=DEV)    # noqa: E731
             if adjoint:
@@ -171,7 +172,7 @@ def test_grouped_chain_is_bit_identical_to_separate_launches(mode, tile, G):
 @gpu
 def test_grouped_chain_rejects_row_gathers_and_other_arithmetics():
     Ws = _weights(2, 1, 4)
-    x = torch.randn(2, 16, C).to(DEV)
+    x = put(torch.randn(2, 16, C))
     y = torch.empty(2, 16, C, device=DEV)
     rows = torch.arange(16, dtype=torch.int32, device=DEV)
     prog = K.ChainProgram(16)
@@ -189,7 +190,7 @@ def test_energy_head_forward_and_adjoint_against_float64():
     G, A = 3, 37
     g = torch.Generator().manual_seed(2)
     x, w, gE = torch.randn(G, A, C, generator=g), torch.randn(G, C, generator=g) / C ** 0.5, torch.randn(A, 1, generator=g)
-    E = K.energy_head_fwd(x.to(DEV), w.to(DEV))
+    E = K.energy_head_fwd(put(x), put(w))
     prod = x.double() * w.double()[:, None, :]
     ref, mag = prod.sum((0, 2)), prod.abs().sum((0, 2))
     # per group 128 rounded products folded by a tree of depth 7 (one add inside the lane, six across), then G - 1 adds in
@@ -199,7 +200,7 @@ def test_energy_head_forward_and_adjoint_against_float64():
     err = (E[:, 0].double().cpu() - ref).abs()
     print(f"energy head: max err / bound {float((err / (eps * mag)).max()):.3f}")
     assert E.shape == (A, 1) and (err <= eps * mag).all()
-    gx = K.energy_head_bwd(gE.to(DEV), w.to(DEV))
+    gx = K.energy_head_bwd(put(gE), put(w))
     ref = gE.double()[None, :, :] * w.double()[:, None, :]
     assert gx.shape == (G, A, C) and ((gx.double().cpu() - ref).abs() <= 2.0 ** -24 * ref.abs()).all()     # one rounding
 

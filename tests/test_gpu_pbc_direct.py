@@ -9,6 +9,7 @@ import pbc_common as P
 import pbc_direct_common as D
 from conftest import SCALE_FILE
 from oracle import gemnet_oracle as GO
+from redzone import put, redzone_on_request  # noqa: F401  (the kernel-level tests below ask for `redzone`: they run under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = D.DEV
@@ -19,7 +20,7 @@ def _kernel_inputs(name, K_, T, seed=0):
     from gemnet_pytorch_amd import kernels as K
     idx, V, A = D.kernel_case(name)
     terms = np.random.RandomState(seed).standard_normal((K_, len(V), T)).astype(np.float32)
-    dev = lambda x, dt: torch.tensor(np.ascontiguousarray(x), dtype=dt, device=DEV)
+    dev = lambda x, dt: put(torch.tensor(np.ascontiguousarray(x), dtype=dt))
     id_a = dev(idx["id_a"], torch.int32)
     perm, seg = K.csr_build(id_a, A)
     return idx, V, A, terms, dev(terms, torch.float32), dev(V, torch.float32), dev(idx["id_swap"], torch.int32), perm, seg
@@ -37,7 +38,7 @@ CASES = [(n, c, k, t) for n in ("sc1", "sc08", "zoo") for c in (False, True) for
 
 
 @pytest.mark.parametrize("name,coupled,K_,T", CASES)
-def test_kernel_matches_fp64_reference(name, coupled, K_, T):
+def test_kernel_matches_fp64_reference(name, coupled, K_, T, redzone):
     idx, Vh, A, th, terms, V, swap, perm, seg = _kernel_inputs(name, K_, T)
     sw_h = idx["id_swap"] if coupled else None
     F = _launch(terms, V, swap if coupled else None, perm, seg, A)
@@ -57,7 +58,7 @@ def test_kernel_matches_fp64_reference(name, coupled, K_, T):
 
 
 @pytest.mark.parametrize("name,coupled,K_,T", CASES)
-def test_kernel_rows_unchanged_by_pad_edges_of_dummy_atoms(name, coupled, K_, T):
+def test_kernel_rows_unchanged_by_pad_edges_of_dummy_atoms(name, coupled, K_, T, redzone):
     """Pad edges that end in additional dummy atoms (the layout of padded.py), the CSR extended: every original row keeps its
     bits."""
     from gemnet_pytorch_amd import kernels as K
@@ -66,10 +67,10 @@ def test_kernel_rows_unchanged_by_pad_edges_of_dummy_atoms(name, coupled, K_, T)
     E, ep, Ad = len(Vh), 10, 3
     rs = np.random.RandomState(1)
     k = np.arange(ep)
-    id_a2 = torch.tensor(np.concatenate([idx["id_a"], A + (k // 2) % Ad]), dtype=torch.int32, device=DEV)
-    swap2 = torch.tensor(np.concatenate([idx["id_swap"], E + (k ^ 1)]), dtype=torch.int32, device=DEV)
-    V2 = torch.cat([V, torch.tensor(rs.uniform(0.5, 1.5, (ep, 3)), dtype=torch.float32, device=DEV)])
-    terms2 = torch.cat([terms, torch.tensor(rs.standard_normal((K_, ep, T)), dtype=torch.float32, device=DEV)], dim=1).contiguous()
+    id_a2 = put(torch.tensor(np.concatenate([idx["id_a"], A + (k // 2) % Ad]), dtype=torch.int32))
+    swap2 = put(torch.tensor(np.concatenate([idx["id_swap"], E + (k ^ 1)]), dtype=torch.int32))
+    V2 = put(torch.cat([V, torch.tensor(rs.uniform(0.5, 1.5, (ep, 3)), dtype=torch.float32, device=DEV)]))
+    terms2 = put(torch.cat([terms, torch.tensor(rs.standard_normal((K_, ep, T)), dtype=torch.float32, device=DEV)], dim=1))
     perm2, seg2 = K.csr_build(id_a2, A + Ad)
     F2 = _launch(terms2, V2, swap2 if coupled else None, perm2, seg2, A + Ad)
     assert torch.equal(F2[:A], F) and bool(torch.isfinite(F2).all()) and bool((F2[A:] != 0).any())

@@ -13,6 +13,7 @@ import pbc_q_common as Q
 from conftest import GOLDEN, SCALE_FILE
 from oracle import basis_oracle as B
 from oracle import gemnet_oracle as GO
+from redzone import put, redzone_on_request  # noqa: F401  (the kernel-level tests below ask for `redzone`: they run under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -86,7 +87,7 @@ def _check_rows(name, got, ref):
 
 @pytest.mark.parametrize("n_quad", [1, 63, 64, 65, None])
 @pytest.mark.parametrize("angle_form", [False, True])
-def test_quad_basis_on_vectors_fwd_and_reduced_adjoint(geometry, n_quad, angle_form):
+def test_quad_basis_on_vectors_fwd_and_reduced_adjoint(geometry, n_quad, angle_form, redzone):
     from gemnet_pytorch_amd import pbc
     inputs, V, Vint = geometry
     # the small counts start at the first well-conditioned quadruplet, so that a launch of ONE row has an adjoint to compare
@@ -96,7 +97,7 @@ def test_quad_basis_on_vectors_fwd_and_reduced_adjoint(geometry, n_quad, angle_f
     plan = _sub_plan(inputs, quads)
     nq = plan.quad.size
     assert nq == (n_quad or 5848)
-    Vd, Vid = V.detach().clone().requires_grad_(True), Vint.detach().clone().requires_grad_(True)
+    Vd, Vid = put(V.detach()).requires_grad_(True), put(Vint.detach()).requires_grad_(True)
     Y = pbc.quad_basis(Vd, Vid, plan, 7, angle_form=angle_form)
     V64, Vi64, phi, th, sin_abd = _quad_geometry64(inputs, V, Vint, quads)
     g = torch.Generator().manual_seed(5)
@@ -121,15 +122,15 @@ def test_quad_basis_on_vectors_fwd_and_reduced_adjoint(geometry, n_quad, angle_f
         gY = torch.randn(nq, 49, generator=g, dtype=torch.float64) * ok
         loss = (gY * ref).sum()
     rV, rVi = torch.autograd.grad(loss, (V64, Vi64))
-    gV, gVi = torch.autograd.grad(Y, (Vd, Vid), gY.float().to(DEV))
+    gV, gVi = torch.autograd.grad(Y, (Vd, Vid), put(gY.float()))
     _check_rows("dE/dV", gV, rV)
     _check_rows("dE/dVint", gVi, rVi)
-    gV2, gVi2 = torch.autograd.grad(pbc.quad_basis(Vd, Vid, plan, 7, angle_form=angle_form), (Vd, Vid), gY.float().to(DEV))
+    gV2, gVi2 = torch.autograd.grad(pbc.quad_basis(Vd, Vid, plan, 7, angle_form=angle_form), (Vd, Vid), put(gY.float()))
     assert torch.equal(gV, gV2) and torch.equal(gVi, gVi2)          # fixed order of addition
 
 
 @pytest.mark.parametrize("angle_form", [False, True])
-def test_exact_degeneracies_sit_on_the_clamp(geometry, angle_form):
+def test_exact_degeneracies_sit_on_the_clamp(geometry, angle_form, redzone):
     """The relative clamp decision of quad_math.h (kRel) on the rows the test above masks out.  EXACTLY planar quadruplets
     (c -> a and d -> b related by a lattice translation; polar angles fine): fp64 autograd sits on the reference's 1e-9 clamp —
     the azimuth's gradient is ~1e-9 — so the adjoint is the polar part alone, and the kernels must give the same within the usual
@@ -155,7 +156,7 @@ def test_exact_degeneracies_sit_on_the_clamp(geometry, angle_form):
     # planar
     plan = _sub_plan(inputs, planar.to(DEV))
     nq = plan.quad.size
-    Vd, Vid = V.detach().clone().requires_grad_(True), Vint.detach().clone().requires_grad_(True)
+    Vd, Vid = put(V.detach()).requires_grad_(True), put(Vint.detach()).requires_grad_(True)
     Y = pbc.quad_basis(Vd, Vid, plan, 7, angle_form=angle_form)
     V64, Vi64, phi, th, _ = _quad_geometry64(inputs, V, Vint, planar)
     if angle_form:
@@ -166,13 +167,13 @@ def test_exact_degeneracies_sit_on_the_clamp(geometry, angle_form):
         gY = torch.randn(nq, 49, generator=g, dtype=torch.float64)
         loss = (gY * B.real_sph_harm_full(7, phi, th)).sum()
     rV, rVi = torch.autograd.grad(loss, (V64, Vi64))
-    gV, gVi = torch.autograd.grad(Y, (Vd, Vid), gY.float().to(DEV))
+    gV, gVi = torch.autograd.grad(Y, (Vd, Vid), put(gY.float()))
     _check_rows("planar dE/dV", gV, rV)
     _check_rows("planar dE/dVint", gVi, rVi)
     # collinear
     plan = _sub_plan(inputs, collinear.to(DEV))
     nq = plan.quad.size
-    Vd, Vid = V.detach().clone().requires_grad_(True), Vint.detach().clone().requires_grad_(True)
+    Vd, Vid = put(V.detach()).requires_grad_(True), put(Vint.detach()).requires_grad_(True)
     ang = pbc.quad_basis(Vd, Vid, plan, 7, angle_form=True)
     assert (ang[:, 2] == 1.0).all() and (ang[:, 3] == 0.0).all()
     g_th = torch.zeros(nq, 4, device=DEV)
@@ -182,7 +183,7 @@ def test_exact_degeneracies_sit_on_the_clamp(geometry, angle_form):
 
 
 @pytest.mark.parametrize("n_intm", [1, 63, 64, 65, None])
-def test_intermediate_triplet_angles_on_vectors(geometry, n_intm):
+def test_intermediate_triplet_angles_on_vectors(geometry, n_intm, redzone):
     from gemnet_pytorch_amd import pbc
     inputs, V, Vint = geometry
     iab, idb = inputs["id4_expand_intm_ab"].cpu(), inputs["id4_expand_intm_db"].cpu()
@@ -195,14 +196,14 @@ def test_intermediate_triplet_angles_on_vectors(geometry, n_intm):
     T = plan.n_intm
     assert T == (n_intm or len(idb)) and T == plan.intm_ab.size
     iab, idb = iab[rows], idb[rows]
-    Vd, Vid = V.detach().clone().requires_grad_(True), Vint.detach().clone().requires_grad_(True)
+    Vd, Vid = put(V.detach()).requires_grad_(True), put(Vint.detach()).requires_grad_(True)
     Y = pbc.trip_basis2(Vid, Vd, plan, 7)
     V64, Vi64 = V.double().cpu().requires_grad_(True), Vint.double().cpu().requires_grad_(True)
     ref = B.real_sph_harm_l0(7, CK._angle_uv(Vi64[iab], -V64[idb]))
     assert Y.shape == ref.shape == (T, 7) and float((Y.double().cpu() - ref.detach()).abs().max()) <= 2e-5
     gY = torch.randn(ref.shape, generator=torch.Generator().manual_seed(6), dtype=torch.float64)
     rV, rVi = torch.autograd.grad((gY * ref).sum(), (V64, Vi64))
-    gVi, gV = torch.autograd.grad(Y, (Vid, Vd), gY.float().to(DEV))
+    gVi, gV = torch.autograd.grad(Y, (Vid, Vd), put(gY.float()))
     # bars of test_trip_basis_fused_fwd_bwd_including_collinear (2e-3 relative + 2e-3 of the median magnitude of the rows that
     # receive a contribution), per row sum; rows without a triplet are exact zeros
     for name, got, want in (("dE/dV", gV, rV), ("dE/dVint", gVi, rVi)):
@@ -213,18 +214,18 @@ def test_intermediate_triplet_angles_on_vectors(geometry, n_intm):
         assert (err <= 2e-3 * want.abs() + 2e-3 * med).all()
 
 
-def test_radial_basis_of_the_interaction_edges(geometry):
+def test_radial_basis_of_the_interaction_edges(geometry, redzone):
     from gemnet_pytorch_amd import pbc
     inputs, V, Vint = geometry
     z, nrm = torch.tensor(B.jn_zeros(7, 6)), torch.tensor(B.sph_bessel_normalizer(7, 6))
-    Vid = Vint.detach().clone().requires_grad_(True)
-    rad = pbc.radial_basis(Vid, z.float().to(DEV), nrm.to(DEV), Q.INT_CUTOFF, 5)
+    Vid = put(Vint.detach()).requires_grad_(True)
+    rad = pbc.radial_basis(Vid, put(z.float()), put(nrm), Q.INT_CUTOFF, 5)
     Vi64 = Vint.double().cpu().requires_grad_(True)
     ref = B.sph_bessel_radial(Vi64.norm(dim=1), 7, 6, Q.INT_CUTOFF, 5)
     assert torch.allclose(rad.double().cpu(), ref.detach(), rtol=1e-4, atol=2e-5)
     g = torch.randn(ref.shape, generator=torch.Generator().manual_seed(7), dtype=torch.float64)
     (rW,) = torch.autograd.grad((g * ref).sum(), Vi64)
-    (W,) = torch.autograd.grad(rad, Vid, g.float().to(DEV))
+    (W,) = torch.autograd.grad(rad, Vid, put(g.float()))
     assert torch.allclose(W.double().cpu(), rW, rtol=2e-4, atol=2e-4 * float(rW.abs().max()))
 
 
@@ -443,7 +444,7 @@ def test_out_of_scope_cases_raise(models):
 
 # ------------------------------------------------------------------------------------------------------------ narrow layers
 @pytest.mark.parametrize("C,E,J,mk", [(8, 60, 300, 80), (16, 61, 130, 40), (8, 1, 5, 3)])
-def test_tensor_basis_x_adjoint_at_narrow_widths(C, E, J, mk):
+def test_tensor_basis_x_adjoint_at_narrow_widths(C, E, J, mk, redzone):
     """gn_bil_expand_f32 at S = 49 and C < 32 (the quadruplet x-adjoint of a narrow model, Y_lm rows): the launch takes at most 8
     edge groups per block — 32 groups of C = 8 asked for more LDS than a launch gets.  Bars of test_gpu_kernels.test_bilinear_kernels."""
     from gemnet_pytorch_amd import kernels as K
@@ -455,6 +456,6 @@ def test_tensor_basis_x_adjoint_at_narrow_widths(C, E, J, mk):
     cpu, dev = SegmentPlan(red, exp, E, J), SegmentPlan(red.to(DEV), exp.to(DEV), E, J)
     Y = torch.randn(cpu.size, 49, generator=g, dtype=torch.float64)
     D = torch.randn(E, 49, C, generator=g, dtype=torch.float64)
-    got = K.bil_reduce_t(Y.float().to(DEV), D.float().to(DEV), dev)
+    got = K.bil_reduce_t(put(Y.float()), put(D.float()), dev)
     ref = CK.bil_reduce_t(Y, D, cpu)
     assert got.shape == ref.shape and float((got.double().cpu() - ref).abs().max()) <= 1e-4 + 2e-5 * float(ref.abs().max())

@@ -6,6 +6,7 @@ import torch
 
 import pbc_common as P
 import pbc_q_common as Q
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -15,7 +16,7 @@ def _device(structs, dtype=torch.float64, out=torch.int64):
     from gemnet_pytorch_amd.pbc import PeriodicQuadGraphBuilder
     R, _, N, cell, pbc = P.arrays(structs)
     b = PeriodicQuadGraphBuilder(N, Q.CUTOFF, Q.INT_CUTOFF, pbc=pbc, device=DEV)
-    idx = b(torch.tensor(R, dtype=dtype, device=DEV), torch.tensor(cell, dtype=dtype, device=DEV), dtype=out)
+    idx = b(put(torch.tensor(R, dtype=dtype)), put(torch.tensor(cell, dtype=dtype)), dtype=out)
     torch.cuda.synchronize()
     return idx, (R, N, cell, pbc)
 
@@ -41,7 +42,7 @@ def test_triplet_keys_are_the_triplet_builders_bit_for_bit():
     from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
     structs = [P.structure(k, seed=i) for i, k in enumerate(["thin", "skewed", "slab"])]
     idx, (R, N, cell, pbc) = _device(structs, out=torch.int32)
-    t = PeriodicGraphBuilder(N, Q.CUTOFF, pbc=pbc, device=DEV)(torch.tensor(R, device=DEV), torch.tensor(cell, device=DEV),
+    t = PeriodicGraphBuilder(N, Q.CUTOFF, pbc=pbc, device=DEV)(put(torch.tensor(R)), put(torch.tensor(cell)),
                                                                 dtype=torch.int32)
     for k, v in t.items():
         assert v.dtype == idx[k].dtype == torch.int32 and torch.equal(v, idx[k]), k
@@ -58,7 +59,7 @@ def test_without_images_equals_the_molecular_device_builder(dtype):
                                          P._gas_structure(70, rs, fff, density=0.1))]
     structs = [(s[0], s[1], s[2], np.array(fff)) for s in structs]
     idx, (R, N, cell, pbc) = _device(structs, dtype=dtype)
-    mol = DeviceGraphBuilder(N, Q.CUTOFF, Q.INT_CUTOFF, triplets_only=False, device=DEV)(torch.tensor(R, dtype=dtype, device=DEV))
+    mol = DeviceGraphBuilder(N, Q.CUTOFF, Q.INT_CUTOFF, triplets_only=False, device=DEV)(put(torch.tensor(R, dtype=dtype)))
     assert len(mol["id4_reduce_ca"]) > 5000
     for k, v in mol.items():
         assert torch.equal(idx[k], v), k

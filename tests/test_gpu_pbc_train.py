@@ -21,6 +21,7 @@ from gemnet_pytorch_amd.model.gemnet import GemNet
 from gemnet_pytorch_amd.training.ddp import TrainStep
 from gemnet_pytorch_amd.training.periodic import PeriodicTrainStep
 from oracle import gemnet_oracle as GO
+from redzone import put, redzone_on_request  # noqa: F401  (the kernel-level tests below ask for `redzone`: they run under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -31,11 +32,11 @@ def close(a, b, rtol, atol):
     torch.testing.assert_close(a.detach().cpu().double(), b.detach().cpu().double(), rtol=rtol, atol=atol)
 
 
-f32 = lambda t: t.float().to(DEV)       # noqa: E731
+f32 = lambda t: put(t.float())       # noqa: E731
 
 
 # ---------------------------------------------------------------------------------------------------------------- kernels
-def test_edge_vector_geometry_kernels():
+def test_edge_vector_geometry_kernels(redzone):
     """csrc/pbc_train.hip: distance and angle value / first adjoint / tangent on edge vectors against fp64 autograd of the
     reference formulas (tests/pbc_train_common.py), E = 67, T = 131 (no full wavefront), one exactly collinear triplet (the
     max(|u x v|, 1e-9) clamp) and a T = 0 call.  Bars: those of test_gpu_kernels.test_twice_differentiable_geometry_kernels."""
@@ -47,7 +48,7 @@ def test_edge_vector_geometry_kernels():
     pairs = torch.stack([torch.randperm(E, generator=g)[:2] for _ in range(T)]).int()
     pairs[0] = torch.tensor([0, 1])                         # the collinear triplet
     red, exp = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
-    d = lambda t: t.to(DEV)                                  # noqa: E731
+    d = put
     gD = torch.randn(E, generator=g, dtype=torch.float64).float().double()
     close(K.dist_vec_fwd(f32(V)), PT.dist_vec_fwd(V), rtol=1e-6, atol=1e-6)
     close(K.dist_vec_bwd(f32(gD), f32(V)), PT.dist_vec_bwd(gD, V), rtol=1e-5, atol=1e-5)
@@ -82,7 +83,7 @@ def test_edge_vector_geometry_kernels():
 
 
 @pytest.mark.parametrize("with_stress", [True, False])
-def test_force_stress_adjoint_kernel(with_stress):
+def test_force_stress_adjoint_kernel(with_stress, redzone):
     """gn_pbc_force_stress_adj_f32 against fp64 autograd of an ATen forces + stress composite, 3 structures; gS given / NULL."""
     g = torch.Generator().manual_seed(5)
     N = [3, 5, 4]
@@ -101,7 +102,7 @@ def test_force_stress_adjoint_kernel(with_stress):
     S = -torch.zeros(3, 3, 3, dtype=torch.float64).index_add(0, b, V[:, :, None] * G[:, None, :]) \
         / torch.linalg.det(cell).abs()[:, None, None]
     (ref,) = torch.autograd.grad((F * gF).sum() + ((S * gS).sum() if with_stress else 0.0), G)
-    d = lambda t: t.to(DEV)                                  # noqa: E731
+    d = put
     out = K.pbc_force_stress_adj(f32(gF), f32(gS) if with_stress else None, f32(V), d(id_c), d(id_a), d(batch_seg), f32(cell))
     close(out, ref, rtol=1e-5, atol=1e-5)
     close(out, PT.pbc_force_stress_adj(gF, gS if with_stress else None, V, id_c, id_a, batch_seg, cell), rtol=1e-5, atol=1e-5)

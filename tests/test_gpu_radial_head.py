@@ -15,6 +15,7 @@ from conftest import ROOT, SCALE_FILE
 from gemnet_pytorch_amd import _lib
 from gemnet_pytorch_amd import kernels as K
 from oracle import basis_oracle as B
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 gpu = pytest.mark.gpu
 DEV = "cuda"
@@ -60,8 +61,8 @@ class Case:
         self.W = [rn(NI, NR), rn(NI, NR), rn(NI, NR), rn(S, NR, NI)]
         self.g = dict(rbf=rn(n_edges, NR), rbf3=rn(n_edges, NI), rbf_h=rn(n_edges, NI), rbf_out=rn(n_edges, NI),
                       rbf_W1=rn(n_edges, S, NI))
-        self.dev = dict(R=self.R.float().to(DEV), ic=self.ic.to(DEV), ia=self.ia.to(DEV), freq=self.freq.float().to(DEV),
-                        z=self.z.float().to(DEV), nrm=self.nrm.to(DEV), wcat=K.radial_head_weights(*self.W).to(DEV))
+        self.dev = dict(R=put(self.R.float()), ic=put(self.ic), ia=put(self.ia), freq=put(self.freq.float()),
+                        z=put(self.z.float()), nrm=put(self.nrm), wcat=put(K.radial_head_weights(*self.W)))
 
     def fwd(self, E):
         d = self.dev
@@ -69,7 +70,7 @@ class Case:
 
     def bwd(self, E, names):
         d = self.dev
-        gs = [self.g[n][:E].to(DEV) if n in names else None for n in ("rbf", "rbf3", "rbf_h", "rbf_out", "rbf_W1")]
+        gs = [put(self.g[n][:E]) if n in names else None for n in ("rbf", "rbf3", "rbf_h", "rbf_out", "rbf_W1")]
         return K.radial_head_bwd(*gs, d["R"], d["ic"][:E], d["ia"][:E], d["freq"], d["z"], d["nrm"], d["wcat"], CUTOFF, P_ENV)
 
     def bwd_ref(self, E, names):

@@ -5,6 +5,7 @@ import torch
 
 from gemnet_pytorch_amd import kernels as K
 from gemnet_pytorch_amd.graph import RowIndex
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -30,9 +31,9 @@ def test_pair_equals_two_single_launches(kinds, n1, n2, M, C):
     g = torch.Generator().manual_seed(M * 131 + C)
     y = torch.randn(M, C, generator=g)
     k1, k2 = _keys(kinds[0], M, n1, g), _keys(kinds[1], M, n2, g)
-    yd = y.to(DEV)
-    p1, s1 = RowIndex(k1.to(DEV), n1).csr
-    p2, s2 = RowIndex(k2.to(DEV), n2).csr
+    yd = put(y)
+    p1, s1 = RowIndex(put(k1), n1).csr
+    p2, s2 = RowIndex(put(k2), n2).csr
     want1, want2 = K.segsum(yd, p1, s1, n1), K.segsum(yd, p2, s2, n2)
     got1, got2 = K.segsum_pair(yd, p1, s1, n1, p2, s2, n2)
     assert got1.shape == (n1, C) and got2.shape == (n2, C)

@@ -18,6 +18,7 @@ from conftest import SCALE_FILE
 from gemnet_pytorch_amd import _lib
 from gemnet_pytorch_amd.training import wgrad_queue as WQ
 from gemnet_pytorch_amd.training.wgrad_queue import WeightGradQueue
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -170,7 +171,7 @@ class Device:
 
     def __init__(self, c):
         self.c = c
-        self.ops = {n: t.to(DEV) for n, t in c.ops.items()}
+        self.ops = {n: put(t) for n, t in c.ops.items()}
         self.param = {}
         for n in c.leaves:
             p = torch.zeros(c.shape[n], device=DEV, requires_grad=True)
@@ -508,7 +509,7 @@ class Buffers:
     def __init__(self, p0, wd, gscale, with_ema=True):
         n = p0.numel()
         self.n = n
-        self.p, self.wd, self.gscale = p0.to(DEV), wd.to(DEV), gscale.to(DEV)
+        self.p, self.wd, self.gscale = put(p0), put(wd), put(gscale)
         self.m, self.v, self.vmax = (torch.zeros(n, device=DEV) for _ in range(3))
         self.ema = self.p.clone() if with_ema else None
         self.lib = _lib.load()
@@ -539,7 +540,7 @@ def test_fused_adamw_ema_matches_float64_adamw(n, schedule):
     b = Buffers(p0, wd, gscale)
     states = []
     for t, (g, (_, max_norm)) in enumerate(zip(grads, SCHEDULES[schedule]), start=1):
-        assert b.step(g.to(DEV), t, max_norm) == 0
+        assert b.step(put(g), t, max_norm) == 0
         states.append(b.state())
     worst = excess(states, orc, bounds)
     print(f"n = {n} [{schedule}]: largest |error| / bound: " + ", ".join(f"{k} {r:.3f}" for k, r in worst.items())
@@ -564,7 +565,7 @@ def test_skip_path_counts_skipped_steps_and_leaves_everything_alone():
     for bad_value in (float("inf"), float("nan")):
         b = Buffers(p0, wd, gscale)
         word = torch.zeros(1, dtype=torch.int32, device=DEV)
-        g_bad = grads[0].to(DEV).clone()
+        g_bad = put(grads[0])
         g_bad[n - 1] = bad_value                        # the last element: the grid-stride tail of the last block
         before = {k: v.clone() for k, v in b.state().items() if k != "norm"}
         assert b.step(g_bad, 1, 10.0, flag=word, flag_bit=GRAD) == 0
@@ -575,12 +576,12 @@ def test_skip_path_counts_skipped_steps_and_leaves_everything_alone():
         after = b.state()
         assert all(torch.equal(before[k], after[k]) for k in before) and int(word) == GRAD | 512
         # a finite step afterwards: the normal update (step 1: the skipped calls did not count), the word stays
-        assert b.step(grads[0].to(DEV), 1, 10.0, flag=word, flag_bit=GRAD) == 0
+        assert b.step(put(grads[0]), 1, 10.0, flag=word, flag_bit=GRAD) == 0
         assert max(excess([b.state()], orc[:1], bounds[:1]).values()) <= 1.0
         assert int(word) == GRAD | 512
     # without a flag word a non-finite norm is not intercepted (documented: the reference writes NaN too): only the return code
     b = Buffers(p0[:63], wd[:63], gscale[:63])
-    g_bad = grads[0][:63].to(DEV).clone()
+    g_bad = put(grads[0][:63])
     g_bad[62] = float("inf")
     assert b.step(g_bad, 1, 10.0) == 0
     torch.cuda.synchronize()
@@ -590,8 +591,8 @@ def test_step_zero_is_an_error_and_an_empty_buffer_a_no_op():
     (p0, wd, gscale, grads, _, _), _, _ = oracle_for(63, "main")
     b = Buffers(p0, wd, gscale)
     before = b.state()
-    assert b.step(grads[0].to(DEV), 0, 10.0) != 0
-    assert b.step(grads[0].to(DEV), 1, 10.0, n=0) == 0
+    assert b.step(put(grads[0]), 0, 10.0) != 0
+    assert b.step(put(grads[0]), 1, 10.0, n=0) == 0
     after = b.state()
     assert all(torch.equal(before[k], after[k]) for k in ("p", "m", "v", "vmax", "ema"))
 

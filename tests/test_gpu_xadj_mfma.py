@@ -25,6 +25,7 @@ import cpu_kernels as CK
 from gemnet_pytorch_amd import kernels as K
 from gemnet_pytorch_amd.graph import SegmentPlan
 from gemnet_pytorch_amd.padded import PaddedGraphRunner
+from redzone import put, redzone  # noqa: F401  (autouse: every test of this module runs under the red-zone harness)
 from test_gpu_bil_up import t_case  # noqa: F401  (the module-scoped model fixture)
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ BARE_ROW_OF = 0                                         # the atom (17 edges) on
 
 
 def f32(t):
-    return t.to(torch.float32).to(DEV)
+    return put(t.to(torch.float32))
 
 
 class Batch:
