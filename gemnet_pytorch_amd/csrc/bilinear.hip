@@ -1460,28 +1460,17 @@ __global__ __launch_bounds__(256) void bil_dy_multi_mfma49_kernel(const gn_dy_mu
 // `sph`): dY[t,s] = sum_b sum_c x_b[g(t),c] dSm_b[e,s,c], written once instead of written by the first block and
 // read-modify-written by each further one.  One wave per reduce edge, 16 triplets per MFMA row tile; the x rows of
 // block b + 1 are in flight under the 16 MFMAs of block b.
-__global__ __launch_bounds__(256) void bil_dy_multi_mfma7_kernel(const gn_dy_multi_args a,
-                                                                 const int32_t* __restrict__ expand_idx,
-                                                                 const int32_t* __restrict__ seg_off,
-                                                                 float* __restrict__ dY, int64_t E) {
+// (the body of one reduce edge with triplets [t0, t1): shared by the kernel below and, for groups beyond 32 rows, by the
+// per-atom kernel.  bd(b, j) = dSm_b[e][s = min(l15, 6)][16 j + 4 lg ..], from registers there and from LDS here: the same
+// values into the same instructions in the same order.  PF: the x rows of block b + 1 are requested before the MFMAs of block b
+// (16 more registers; without it the 1 024-thread kernel keeps 64 VGPRs: two workgroups per CU).)
+template <bool PF, class BD>
+__device__ __forceinline__ void bil_dy_multi_edge7(const gn_dy_multi_args& a, const int32_t* __restrict__ expand_idx,
+                                                   float* __restrict__ dY, int t0, int t1, int lane, const BD& bd) {
   constexpr int S = 7, C = 64;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l15 = lane & 15, lg = lane >> 4;
-  const int64_t e = (int64_t)blockIdx.x * 4 + wave;
-  if (e >= E) return;
-  const int t0 = seg_off[e], t1 = seg_off[e + 1];
-  if (t0 >= t1) return;
   auto comp = [](const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); };
   const int nb = a.nb;
-  const int scl = min(l15, S - 1);   // columns s >= 7 are MFMA padding: duplicates, never stored
-  float4 bd[4][4];                   // [block][j]: dSm_b[e][s = l15][16 j + 4 lg ..]
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-    if (b < nb) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bd[b][j] = *reinterpret_cast<const float4*>(a.dS[b] + (e * S + scl) * C + 16 * j + 4 * lg);
-    }
   auto loadx = [&](int b, int64_t g, float4 (&ax)[4]) {
     if (b >= nb) return;
     const float* __restrict__ xr = a.x[b] + g * C + 4 * lg;
@@ -1496,14 +1485,20 @@ __global__ __launch_bounds__(256) void bil_dy_multi_mfma7_kernel(const gn_dy_mul
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       if (b < nb) {
-        loadx(b + 1, g, an);
+        if (PF) loadx(b + 1, g, an);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
+          const float4 d = bd(b, j);
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            y = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(ax[j], q), comp(bd[b][j], q), y, 0, 0, 0);
+            y = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(ax[j], q), comp(d, q), y, 0, 0, 0);
+        }
+        if (PF) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ax[j] = an[j];
+          for (int j = 0; j < 4; ++j) ax[j] = an[j];
+        } else {
+          loadx(b + 1, g, ax);
+        }
       }
     }
 #pragma unroll
@@ -1512,6 +1507,192 @@ __global__ __launch_bounds__(256) void bil_dy_multi_mfma7_kernel(const gn_dy_mul
       if (l15 < S && t < t1) dY[(int64_t)t * S + l15] = y[r];
     }
   }
+}
+
+__global__ __launch_bounds__(256) void bil_dy_multi_mfma7_kernel(const gn_dy_multi_args a,
+                                                                 const int32_t* __restrict__ expand_idx,
+                                                                 const int32_t* __restrict__ seg_off,
+                                                                 float* __restrict__ dY, int64_t E) {
+  constexpr int S = 7, C = 64;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int64_t e = (int64_t)blockIdx.x * 4 + wave;
+  if (e >= E) return;
+  const int t0 = seg_off[e], t1 = seg_off[e + 1];
+  if (t0 >= t1) return;
+  const int nb = a.nb;
+  const int scl = min(l15, S - 1);   // columns s >= 7 are MFMA padding: duplicates, never stored
+  float4 bd[4][4];                   // [block][j]: dSm_b[e][s = l15][16 j + 4 lg ..]
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+    if (b < nb) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        bd[b][j] = *reinterpret_cast<const float4*>(a.dS[b] + (e * S + scl) * C + 16 * j + 4 * lg);
+    }
+  bil_dy_multi_edge7<true>(a, expand_idx, dY, t0, t1, lane, [&](int b, int j) -> const float4& { return bd[b][j]; });
+}
+
+// The same Y gradient per ATOM (S = 7, C = 64; groups of n <= 32 rows).  Both edges of a triplet c -> a <- b end in the atom a,
+// so the atom's part of dY is one dense product on v_mfma_f32_16x16x4_f32 (exact f32 products, f32 accumulate):
+//   dYmat_a (7n x n) = sum_blocks dSm_a,blk (7n x 64) . X_a,blk^T (64 x n),   dYmat_a[7 c + s, b] = dY[t(c, b), s],
+// b = local rank of the expand row, c = local rank of the reduce edge: an atom's x rows are read once per block instead of
+// once per triplet.  One workgroup per atom, as in bil_x_adjoint_atoms_kernel.  Per block the atom's dSm rows (row k = 7 c + s)
+// and x rows are parked in LDS, rows of 64 floats whose sixteen float4 slots sit XORed with row & 15: the ds_read_b128 of a
+// lane (row 16 tile + l15, slot 4 j + lg) is conflict-free in each of its four lane groups ({rows 0-3, 12-15 of one lg, rows
+// 4-11 of lg ^ 1}: the XOR sends them to sixteen different slots; a pitch of 68 floats would put row 11 of one lg and row 12 of
+// the other on one bank), and so is the ds_write_b128 of the fill.  The next block's operands are requested into registers
+// before the current block's MFMA phase.  M = tile rows, N = expand ranks, K = 64 channels per block in the order of the
+// per-edge kernel (block by block; instruction (j, q) takes channels 16 j + q + 4 {0, 1, 2, 3}): one accumulator chain per
+// output tile across all blocks, one order of summation whatever the launch.  Padding in M and N only reaches outputs that are
+// never stored.  After the last block the accumulators go through LDS as dYmat[k][b] and every thread takes entries of the
+// plan's flat list (graph.SegmentPlan.group_entries) and writes the seven values of its triplet; entries repeating a (b, c)
+// pair each write their own row.  Groups beyond 32 rows run the per-edge body above in the same launch, eight reduce edges at a
+// time with their dSm rows parked in LDS: the path depends on the group's own size only.
+constexpr int DA_ROWS = 32, DA_FB_WAVES = 8, DA_PITCH = 33;
+constexpr size_t DA_LDS = (size_t)DA_ROWS * (7 * 64 + 64) * sizeof(float);   // 65 536 B, whatever the group
+static_assert(DA_LDS <= 80 * 1024 && (size_t)DA_FB_WAVES * 4 * 7 * 64 * sizeof(float) <= DA_LDS &&
+              (size_t)DA_ROWS * 7 * DA_PITCH <= (size_t)DA_ROWS * 7 * 64, "two workgroups per CU; the other two uses of the tile");
+
+__global__ __launch_bounds__(1024) void bil_dy_atoms_kernel(
+    const gn_dy_multi_args a, const int32_t* __restrict__ grp_rows, const int32_t* __restrict__ grp_off,
+    const int32_t* __restrict__ ent_off, const int32_t* __restrict__ ent_t, const int32_t* __restrict__ ent_bc,
+    const int32_t* __restrict__ expand_idx, const int32_t* __restrict__ seg_off, float* __restrict__ dY) {
+  constexpr int S = 7, C = 64, SC = S * C, NV = SC / 4;
+  extern __shared__ float dtile[];  // [7 x 32 tile rows][64] | [32 x rows][64]; later dYmat [7 x 32][DA_PITCH]
+  const int g = blockIdx.x;
+  const int r0 = grp_off[g], n = grp_off[g + 1] - r0;
+  if (n <= 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nb = a.nb;
+  auto pick = [](const float* const (&p)[4], int b) { return b == 0 ? p[0] : (b == 1 ? p[1] : (b == 2 ? p[2] : p[3])); };
+  if (n > DA_ROWS) {
+    const int scl = min(l15, S - 1);
+    float* park = dtile + (w < DA_FB_WAVES ? w : 0) * 4 * SC;   // [block][s][64] of this wave's edge
+    for (int l0 = 0; l0 < n; l0 += DA_FB_WAVES) {
+      const int l = l0 + w;
+      int64_t e = 0;
+      int t0 = 0, t1 = 0;
+      if (w < DA_FB_WAVES && l < n) {
+        e = grp_rows[r0 + l];
+        t0 = seg_off[e], t1 = seg_off[e + 1];
+      }
+      if (t0 < t1) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (b < nb)
+            for (int i = lane; i < NV; i += 64)
+              reinterpret_cast<float4*>(park)[b * NV + i] = reinterpret_cast<const float4*>(a.dS[b] + e * SC)[i];
+      }
+      __syncthreads();
+      if (t0 < t1)
+        bil_dy_multi_edge7<false>(a, expand_idx, dY, t0, t1, lane, [&](int b, int j) {
+          return *reinterpret_cast<const float4*>(park + (b * S + scl) * C + 16 * j + 4 * lg);
+        });
+      __syncthreads();   // the edges of this round have been read
+    }
+    return;
+  }
+  const int e0 = ent_off[g], e1 = ent_off[g + 1];
+  if (e0 >= e1) return;   // no triplet ends in this atom: nothing to write
+  // the first 1 024 entries: requested here, used after the last block
+  const int i0 = e0 + tid;
+  const int bc0 = i0 < e1 ? ent_bc[i0] : 0;
+  const int t_0 = i0 < e1 ? ent_t[i0] : 0;
+  float4* tile4 = reinterpret_cast<float4*>(dtile);
+  float4* xt4 = tile4 + DA_ROWS * NV;
+  // The fills: n * NV float4 of the tile (<= 3 584) and n * 16 of the x rows (<= 512), at most four per thread — slot 3 is a
+  // tile piece for threads < 512 (n * NV - 3 072 <= 512) and an x piece for the others.  src[u]: float4 index inside the
+  // block's array, -1 = none.
+  int src[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    src[u] = -1;
+    if (u == 3 && tid >= 512) {
+      const int xi = tid - 512;
+      if (xi < n * 16) src[u] = grp_rows[r0 + (xi >> 4)] * 16 + (xi & 15);
+    } else {
+      const int i = tid + 1024 * u;
+      if (i < n * NV) {
+        const int l = i / NV;
+        src[u] = grp_rows[r0 + l] * NV + (i - l * NV);
+      }
+    }
+  }
+  auto request = [&](int b, float4 (&d)[4]) {
+    const float4* __restrict__ ds = reinterpret_cast<const float4*>(pick(a.dS, b));
+    const float4* __restrict__ xs = reinterpret_cast<const float4*>(pick(a.x, b));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      d[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (src[u] >= 0) d[u] = (u == 3 && tid >= 512 ? xs : ds)[src[u]];
+    }
+  };
+  auto park_tile = [&](const float4 (&d)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (src[u] < 0) continue;
+      if (u == 3 && tid >= 512) {
+        const int xi = tid - 512, b = xi >> 4;
+        xt4[b * 16 + ((xi & 15) ^ (b & 15))] = d[u];
+      } else {
+        const int i = tid + 1024 * u, k = i >> 4;
+        tile4[k * 16 + ((i & 15) ^ (k & 15))] = d[u];
+      }
+    }
+  };
+  float4 d[4];
+  request(0, d);
+  // Output tiles: more than eight M tiles (n >= 19: two N tiles) — wave w owns M tile w and both N tiles; else one (mt, nt) each.
+  const int nM = (S * n + 15) >> 4, nN = n > 16 ? 2 : 1;
+  const bool both = nM > 8;
+  const int mt = (both || nN == 1) ? w : (w >> 1), nt0 = (both || nN == 1) ? 0 : (w & 1);
+  const bool mm = mt < nM;
+  auto comp = [](const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); };
+  v4f_b acc0 = (v4f_b){0.f, 0.f, 0.f, 0.f}, acc1 = (v4f_b){0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < nb; ++b) {
+    if (b) __syncthreads();   // the previous block's operands have been read
+    park_tile(d);
+    if (b + 1 < nb) request(b + 1, d);
+    __syncthreads();
+    if (mm) {
+      const float4* ap = tile4 + (16 * mt + l15) * 16;
+      const float4* bp = xt4 + (16 * nt0 + l15) * 16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sl = (4 * j + lg) ^ l15;
+        const float4 fa = ap[sl], fb = bp[sl];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(fa, q), comp(fb, q), acc0, 0, 0, 0);
+        if (both) {
+          const float4 fc = bp[256 + sl];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(fa, q), comp(fc, q), acc1, 0, 0, 0);
+        }
+      }
+    }
+  }
+  __syncthreads();   // the tile is dead: dYmat takes its place
+  if (mm) {   // D layout: col = l15 (expand rank within the N tile), row = 4 lg + r (tile row within the M tile)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float* ym = dtile + (16 * mt + 4 * lg + r) * DA_PITCH + l15;
+      ym[16 * nt0] = acc0[r];
+      if (both) ym[16] = acc1[r];
+    }
+  }
+  __syncthreads();
+  auto store = [&](int bc, int t) {
+    // (a valid plan has b, c < n: the clamp only keeps a broken one inside the tile)
+    const int b = min(bc & 0xffff, DA_ROWS - 1), c = min((int)((unsigned)bc >> 16), DA_ROWS - 1);
+    const float* ym = dtile + S * c * DA_PITCH + b;
+    float* __restrict__ yo = dY + (int64_t)t * S;
+#pragma unroll
+    for (int s = 0; s < S; ++s) yo[s] = ym[s * DA_PITCH];
+  };
+  if (i0 < e1) store(bc0, t_0);
+  for (int i = i0 + 1024; i < e1; i += 1024) store(ent_bc[i], ent_t[i]);   // (more than 1 024 entries: only with repeated pairs)
 }
 
 inline bool ok_channels(int C) { return C > 0 && C <= 256 && (256 % C) == 0; }
@@ -2092,6 +2273,26 @@ extern "C" int gn_bil_dy_multi_f32(const float* const* dSm_list, const float* co
   else
     hipLaunchKernelGGL(bil_dy_multi_mfma49_kernel, dim3(gn_cdiv(E, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), a,
                        expand_idx, seg_off, dY, E);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_bil_dy_atoms_f32(const float* const* dSm_list, const float* const* x_list, int nb,
+                                   const int32_t* grp_rows, const int32_t* grp_off, const int32_t* ent_off,
+                                   const int32_t* ent_t, const int32_t* ent_bc, const int32_t* expand_idx,
+                                   const int32_t* seg_off, float* dY, int64_t G, int max_rows, int S, int C, void* stream) {
+  if (G <= 0 || nb <= 0) return 0;
+  if (nb > 4 || S != 7 || C != 64 || max_rows < 1) return (int)hipErrorInvalidValue;
+  gn_dy_multi_args a;
+  a.nb = nb;
+  for (int b = 0; b < 4; ++b) {
+    a.dS[b] = b < nb ? dSm_list[b] : nullptr;
+    a.x[b] = b < nb ? x_list[b] : nullptr;
+    if (b < nb && (!aligned16(a.dS[b]) || !aligned16(a.x[b]))) return (int)hipErrorInvalidValue;
+  }
+  // (max_rows is the plan's bound and changes nothing here: the LDS need is that of a group of 32 rows)
+  hipLaunchKernelGGL(bil_dy_atoms_kernel, dim3((unsigned)G), dim3(1024), DA_LDS, static_cast<hipStream_t>(stream), a, grp_rows,
+                     grp_off, ent_off, ent_t, ent_bc, expand_idx, seg_off, dY);
   GN_LAUNCH_CHECK();
   return 0;
 }

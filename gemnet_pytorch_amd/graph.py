@@ -234,8 +234,8 @@ class SegmentPlan:
             self._groups = (rows.to(torch.int32).contiguous(), off, kseg, rposT, max_rows)
             self._group_entries = None
             from . import kernels as _K
-            if _K.USE_XADJ_MFMA:
-                # built with the groups, on their stream (GraphPlan.warm): the x-adjoint launch reads both
+            if _K.USE_XADJ_MFMA or _K.USE_DY_ATOMS:
+                # built with the groups, on their stream (GraphPlan.warm): the x-adjoint and Y-gradient launches read both
                 self._group_entries = _group_entry_list(rows, off, rank, key, kseg, permT, self.expand.idx64, rposT)
         return self._groups
 

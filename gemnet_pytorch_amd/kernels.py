@@ -545,6 +545,10 @@ ANG_F16_MASK = int(os.environ.get("GEMNET_ANG_F16", "7")) & 7
 # on v_mfma_f32_16x16x4_f32, index staging from the plan's flat entry list; larger groups keep the scalar body in the same
 # launch).  GEMNET_XADJ_MFMA=0: the scalar grouped launch (gn_bil_reduce_t_grouped_f32) for every group.
 USE_XADJ_MFMA = os.environ.get("GEMNET_XADJ_MFMA", "1") == "1"
+# The triplet Y gradient per atom on the matrix cores (gn_bil_dy_atoms_f32: one workgroup per atom, groups of <= 32 rows as one
+# dense product over the plan's flat entry list, the atom's x rows read once per block instead of once per triplet; larger groups
+# keep the per-edge body in the same launch).  GEMNET_DY_ATOMS=0: the per-edge launch (gn_bil_dy_multi_f32) everywhere.
+USE_DY_ATOMS = os.environ.get("GEMNET_DY_ATOMS", "1") == "1"
 
 
 def bil_reduce_t(Y, D, sp):
@@ -1739,6 +1743,15 @@ def bil_dy_multi(dSm_list, x_list, sp, ang=None):
         return g_ang
     dY = torch.empty((sp.size, S), device=x_list[0].device, dtype=torch.float32)
     arr = ctypes.c_void_p * nb
+    grp = sp.groups if USE_DY_ATOMS and (S, C) == (7, 64) and nb <= 4 else None
+    if grp is not None and 0 < grp[4] * S * C * 4 <= 160 * 1024:      # (the condition of the grouped launches in bil_reduce_t)
+        rows, off, _kseg, _rposT, max_rows = grp
+        ent_off, ent_t, ent_bc = sp.group_entries
+        check(_lib.load().gn_bil_dy_atoms_f32(arr(*[addr(t) for t in dSm_list]), arr(*[addr(t) for t in x_list]), nb,
+                                              ptr(rows), ptr(off), ptr(ent_off), ptr(ent_t), ptr(ent_bc),
+                                              ptr(sp.expand.idx32), ptr(sp.seg_off), ptr(dY), off.shape[0] - 1, max_rows, S, C,
+                                              stream()), "gn_bil_dy_atoms_f32")
+        return dY
     check(_lib.load().gn_bil_dy_multi_f32(arr(*[addr(t) for t in dSm_list]), arr(*[addr(t) for t in x_list]),
                                           nb, ptr(sp.expand.idx32), ptr(sp.seg_off), ptr(dY), E, S, C, stream()),
           "gn_bil_dy_multi_f32")

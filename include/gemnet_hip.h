@@ -550,6 +550,17 @@ int gn_bil_up_bwd_f32(const float* G, const int32_t* inv_swap, const float* z_ac
  *   dY[t,s] = sum_b sum_c x_b[g(t),c] dSm_b[r(t),s,c]        (dSm_list / x_list: host arrays of nb device pointers) */
 int gn_bil_dy_multi_f32(const float* const* dSm_list, const float* const* x_list, int nb, const int32_t* expand_idx,
                         const int32_t* seg_off, float* dY, int64_t E, int S, int C, void* stream);
+/* The same dY for the spherical basis (S = 7, C = 64 only, else hipErrorInvalidValue) on a plan with row groups (both rows of
+ * every entry in one group: the triplets' target atom), one workgroup per group: a group of n <= 32 rows is one dense product
+ *   dYmat_g (S n x n) = sum_b dSm_b,g (S n x C) . x_b,g^T (C x n),   dYmat_g[S c + s, b] = dY[t, s]
+ * on v_mfma_f32_16x16x4_f32, the group's x rows read once per block instead of once per entry; t, b, c from the flat entry
+ * list of gn_bil_x_adjoint_atoms_f32 (entries repeating a pair each get their own row).  Larger groups run the per-edge body
+ * of gn_bil_dy_multi_f32 in the same launch, bit-identical to it: the path depends on the group's own size only, never on
+ * max_rows (>= 1, otherwise unused), the grid or the other groups.  K order = that of gn_bil_dy_multi_f32.  LDS 65 536 B. */
+int gn_bil_dy_atoms_f32(const float* const* dSm_list, const float* const* x_list, int nb, const int32_t* grp_rows,
+                        const int32_t* grp_off, const int32_t* ent_off, const int32_t* ent_t, const int32_t* ent_bc,
+                        const int32_t* expand_idx, const int32_t* seg_off, float* dY, int64_t G, int max_rows, int S, int C,
+                        void* stream);
 
 /* ---- basis functions (P6-P8; closed forms of SURVEY.md Appendix A, evaluated in f64 in-kernel) */
 /* out[e,n] = d^kd/dd^kd d^kf/df_n^kf [ u(d/c) sqrt(2/c) sin(f_n d/c)/d ]   (basis_layers.py:45-49);
