@@ -751,6 +751,78 @@ def radial_head_bwd(g_rbf, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1, R, idx_c, idx_a
     return W
 
 
+RADIAL_EMB_WIDTH = 128              # atom / edge embedding width the embedding form of the radial head is built for
+
+
+def _aligned16(*tensors):
+    for t in tensors:
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError("radial head: the 128-column operands must be 16-byte aligned")
+
+
+def _radial_emb_args(E, n_atoms, zrow, T_c, T_a, W_r):
+    NR, NE = RADIAL_HEAD_SHAPE[0], RADIAL_EMB_WIDTH
+    if tuple(W_r.shape) != (NR, NE):
+        raise ValueError(f"radial head: W_r of shape {tuple(W_r.shape)}, expected {(NR, NE)} (the rbf columns, transposed)")
+    if zrow is not None:
+        if T_c.dim() != 2 or T_c.shape[1] != NE or T_a.shape != T_c.shape:
+            raise ValueError(f"radial head: atom-term tables {tuple(T_c.shape)} / {tuple(T_a.shape)}, expected two (rows, {NE})")
+        if zrow.dim() != 1 or zrow.dtype != torch.int32 or zrow.shape[0] < n_atoms:
+            raise ValueError("radial head: zrow is (atoms,) int32, one table row per atom")
+        T_c, T_a, zrow = _f32c(T_c), _f32c(T_a), zrow.contiguous()
+    W_r = _f32c(W_r)
+    _aligned16(T_c, T_a, W_r)
+    require_device(zrow, T_c, T_a, W_r)
+    return zrow, T_c, T_a, W_r
+
+
+def radial_head_emb_fwd(R, idx_c, idx_a, freq, z, nrm, wcat, zrow, T_c, T_a, W_r, cutoff, p, want_rbf=False):
+    """-> m0, d0 (E,128), rbf3, rbf_h, rbf_out (E,16), rbf_W1 (E,S,16), rbf (E,NR) or None: `radial_head_fwd` with the edge
+    embedding m0 = ssilu(rbf W_r + T_c[zrow[idx_c]] + T_a[zrow[idx_a]]) and d0 = ssilu'(.) in the same launch
+    (gn_radial_head_emb_fwd_f32).  T_c / T_a (rows, 128): the atom-term tables; W_r (NR, 128)."""
+    E = idx_c.shape[0]
+    NR, S, NI = RADIAL_HEAD_SHAPE
+    NE = RADIAL_EMB_WIDTH
+    zrow, T_c, T_a, W_r = _radial_emb_args(E, R.shape[0], zrow, T_c, T_a, W_r)
+    R, idx_c, idx_a, freq, z, nrm, wcat = _radial_head_args(R, idx_c, idx_a, freq, z, nrm, wcat)
+    new = lambda *shape: torch.empty(shape, device=R.device, dtype=torch.float32)   # noqa: E731
+    rbf3, rbf_h, rbf_out, rbf_W1, m0, d0 = new(E, NI), new(E, NI), new(E, NI), new(E, S, NI), new(E, NE), new(E, NE)
+    rbf = new(E, NR) if want_rbf else None
+    check(_lib.load().gn_radial_head_emb_fwd_f32(ptr(R), ptr(idx_c), ptr(idx_a), ptr(freq), ptr(z), ptr(nrm), ptr(wcat),
+                                                 ptr(zrow), ptr(T_c), ptr(T_a), ptr(W_r), ptr(rbf), ptr(rbf3), ptr(rbf_h),
+                                                 ptr(rbf_out), ptr(rbf_W1), ptr(m0), ptr(d0), E, NR, S, NI, NE, cutoff, p,
+                                                 stream()), "gn_radial_head_emb_fwd_f32")
+    return m0, d0, rbf3, rbf_h, rbf_out, rbf_W1, rbf
+
+
+def radial_head_emb_bwd(g_rbf, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1, ga, gb, d0, W_r, R, idx_c, idx_a, freq, z, nrm, wcat,
+                        cutoff, p):
+    """-> W (E,3) of `radial_head_bwd` with the adjoint of the edge embedding added: ga / gb (E,128) are cotangents of m0
+    (their sum is taken in the kernel), d0 the stored ssilu'(z0); any cotangent may be None."""
+    E = idx_c.shape[0]
+    NR, S, NI = RADIAL_HEAD_SHAPE
+    NE = RADIAL_EMB_WIDTH
+    gs = []
+    for g, shape in ((g_rbf, (E, NR)), (g_rbf3, (E, NI)), (g_rbf_h, (E, NI)), (g_rbf_out, (E, NI)), (g_rbf_W1, (E, S, NI)),
+                     (ga, (E, NE)), (gb, (E, NE)), (d0, (E, NE))):
+        if g is not None:
+            if tuple(g.shape) != shape:
+                raise ValueError(f"radial head: cotangent of shape {tuple(g.shape)}, expected {shape}")
+            g = _f32c(g)
+        gs.append(g)
+    if (gs[5] is not None or gs[6] is not None) and gs[7] is None:
+        raise ValueError("radial head: a cotangent of m0 needs d0")
+    _aligned16(*gs[5:])
+    _, _, _, W_r = _radial_emb_args(E, R.shape[0], None, None, None, W_r)
+    require_device(*gs)
+    R, idx_c, idx_a, freq, z, nrm, wcat = _radial_head_args(R, idx_c, idx_a, freq, z, nrm, wcat)
+    W = torch.empty((E, 3), device=R.device, dtype=torch.float32)
+    check(_lib.load().gn_radial_head_emb_bwd_f32(*[ptr(g) for g in gs], ptr(W_r), ptr(R), ptr(idx_c), ptr(idx_a), ptr(freq),
+                                                 ptr(z), ptr(nrm), ptr(wcat), ptr(W), E, NR, S, NI, NE, cutoff, p, stream()),
+          "gn_radial_head_emb_bwd_f32")
+    return W
+
+
 def trip_basis_fwd(R, tc, ta, tb, S, want_theta=False):
     """-> Y (T,S) = Y_l0(angle c<-a->b), theta (T,)|None   (gemnet.py:288-311,420-451 + basis_layers.py:130-131)."""
     require_device(R, tc, ta, tb)

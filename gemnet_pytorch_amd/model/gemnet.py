@@ -235,13 +235,21 @@ class GemNet(torch.nn.Module):
                 and all(d.bias is None and not d.act for d in proj)
                 and ops.radial_head_supported(tuple(d.weight for d in proj) + (self.mlp_cbf3.weight,), b3.z_ln,
                                               self.rbf_basis.frequencies))
+        # ... and the edge embedding with it (ops.radial_head_emb): its two atom terms are rows of tables over the 93
+        # elements, so the two atom-row GEMMs, the K = 6 GEMM and its adjoint GEMM leave the step (GEMNET_RADIAL_EMB=0,
+        # other widths, the f32 arithmetic: the launches below)
+        ee = self.edge_emb
+        emb = head and ops.radial_emb_supported(self.atom_emb.embeddings.weight, ee.dense.weight, ee.dense.act, ee.dense.bias,
+                                                ee.atom_features)
+        m = None
         if ops.is_fused():
             if fork:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     sph3 = ops.share_gradient(self._trip_basis3(R, plan, V))
                     h = self.atom_emb(plan.z_rows)
-                    terms = self.edge_emb.atom_terms(h)
+                    if not emb:
+                        terms = self.edge_emb.atom_terms(h)
                     ev_a = torch.cuda.Event()
                     ev_a.record(side)
             # one launch: distances + Bessel rbf + spherical-Bessel radial basis; one launch: angles + Y_l0
@@ -249,6 +257,9 @@ class GemNet(torch.nn.Module):
                 from .. import pbc
                 D_ca, rbf, rad3 = pbc.edge_basis(V, self.rbf_basis.frequencies, b3.z_ln, b3.n_ln, b3.cutoff, b3.p)
                 V_ca = None
+            elif emb:
+                m, rbf3, rbf_h, rbf_out, rbf_W1_3 = self._radial_head(R, plan, proj, emb=True)
+                rbf = V_ca = None
             elif head:
                 rbf, rbf3, rbf_h, rbf_out, rbf_W1_3 = self._radial_head(R, plan, proj)
                 V_ca = None
@@ -260,7 +271,7 @@ class GemNet(torch.nn.Module):
                 # everything the side stream consumes of the head is rbf_out, and every output block orders itself behind
                 # the main stream before it reads it (out_block below)
                 main.wait_event(ev_a)
-                for t in (sph3, h) + tuple(terms):
+                for t in (sph3, h) + tuple(terms or ()):
                     t.record_stream(main)
             elif fork:
                 ev_1 = torch.cuda.Event()
@@ -363,8 +374,9 @@ class GemNet(torch.nn.Module):
 
         if h is None:
             h = self.atom_emb(plan.z_rows)
-        rbf = ops.accumulate_gradient(rbf)
-        m = self.edge_emb(h, rbf, plan.id_c, plan.id_a, terms=terms)
+        if m is None:
+            rbf = ops.accumulate_gradient(rbf)
+            m = self.edge_emb(h, rbf, plan.id_c, plan.id_a, terms=terms)
 
         if not T:
             rbf4 = ops.accumulate_gradient(self.mlp_rbf4(rbf))
@@ -493,8 +505,12 @@ class GemNet(torch.nn.Module):
                                act0=bool(ob.seq_energy[0].act), w_out=ob.out_energy.weight))
         return blocks if ops.output_group_supported(blocks, [m] * len(blocks), rbf_out) else None
 
-    def _radial_head(self, R, plan, proj):
+    def _radial_head(self, R, plan, proj, emb=False):
         b3 = self.cbf_basis3
+        if emb:
+            return ops.radial_head_emb(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a, b3.z_ln, b3.n_ln,
+                                       tuple(d.weight for d in proj) + (self.mlp_cbf3.weight,), b3.cutoff, b3.p, plan.z_rows,
+                                       self.atom_emb.embeddings.weight, self.edge_emb.dense.weight, self.edge_emb.atom_features)
         return ops.radial_head(R, self.rbf_basis.frequencies, plan.id_c, plan.id_a, b3.z_ln, b3.n_ln,
                                tuple(d.weight for d in proj) + (self.mlp_cbf3.weight,), b3.cutoff, b3.p)
 

@@ -1024,6 +1024,76 @@ def radial_head(R, freq, ri_c, ri_a, z, nrm, weights, cutoff, p):
     return _RadialHead.apply(R, freq.detach(), ri_c, ri_a, z, nrm, _radial_head_wcat(weights), float(cutoff), int(p))
 
 
+# Edge embedding inside the radial head launches: with frozen weights the two atom terms of the
+# embedding Dense are rows of 93-row tables, the rbf term a six-term dot product on values the head kernel holds in LDS, and
+# its adjoint a 128-long dot per radial function in front of the derivative.  GEMNET_RADIAL_EMB=0 restores the head launch +
+# two atom-row GEMMs + small-K GEMM and its adjoint GEMM (A/B runs, tests).
+USE_RADIAL_EMB = os.environ.get("GEMNET_RADIAL_EMB", "1") == "1"
+ATOM_TABLE_BUILDS = 0     # times the atom-term tables were (re)built (tests: once per weight version)
+
+
+def radial_emb_supported(emb_weight, W, act, bias, atom_features):
+    """May `radial_head_emb` produce the edge embedding too?  (Where `radial_head_supported` holds.)  `W`: the (128, 2A + NR)
+    weight of the embedding Dense, ScaledSiLU, no bias, atom and edge width 128, a 93-row embedding."""
+    NR, NE = K.RADIAL_HEAD_SHAPE[0], K.RADIAL_EMB_WIDTH
+    return (USE_RADIAL_EMB and bias is None and bool(act) and atom_features == NE and tuple(W.shape) == (NE, 2 * NE + NR)
+            and tuple(emb_weight.shape) == (93, NE) and W.is_cuda and emb_weight.is_cuda
+            and W.dtype == torch.float32 and emb_weight.dtype == torch.float32 and K.current_mode() != "f32")
+
+
+def _make_atom_tables(emb_weight, W, A):
+    """(T_c, T_a, W_r): emb W[:, :A]^T and emb W[:, A:2A]^T by the GEMM launch that forms the atom terms h W_c^T / h W_a^T
+    from the gathered rows (same kernel for every M <= 4096, rows independent of M: a table row is that launch's row), and
+    the rbf columns of W transposed to (NR, 128)."""
+    global ATOM_TABLE_BUILDS
+    ATOM_TABLE_BUILDS += 1
+    emb, W = emb_weight.detach(), W.detach()
+    T_c = K.gemm(emb, W[:, :A].contiguous())
+    T_a = K.gemm(emb, W[:, A:2 * A].contiguous())
+    return T_c, T_a, W[:, 2 * A:].t().contiguous()
+
+
+def atom_term_tables(emb_weight, W, A):
+    """The cached (T_c, T_a, W_r) of `_make_atom_tables`, keyed on both weights' address, shape, stride and version."""
+    key = ("atab",) + tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride())) for t in (emb_weight, W))
+    return _cached(key, (emb_weight._version, W._version), lambda: _make_atom_tables(emb_weight, W, A))
+
+
+class _RadialHeadEmb(torch.autograd.Function):
+    """(R) -> m0, rbf3, rbf_h, rbf_out, rbf_W1 in one launch; one adjoint launch that also folds in the adjoint of the
+    embedding Dense (first-order only, frozen weights).  The cotangent of m0 arrives as ONE tensor: the interaction block
+    marks m0 with `accumulate_gradient`, so its consumers sum in their epilogues."""
+
+    @staticmethod
+    def forward(ctx, R, freq, ri_c, ri_a, z, nrm, wcat, zrow, T_c, T_a, W_r, cutoff, p):
+        m0, d0, rbf3, rbf_h, rbf_out, rbf_W1, _ = K.radial_head_emb_fwd(R, ri_c.idx32, ri_a.idx32, freq, z, nrm, wcat, zrow,
+                                                                        T_c, T_a, W_r, cutoff, p)
+        ctx.save_for_backward(R, freq, z, nrm, wcat, d0, W_r)
+        ctx.cfg = (ri_c, ri_a, cutoff, p)
+        ctx.set_materialize_grads(False)
+        return m0, rbf3, rbf_h, rbf_out, rbf_W1
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_m0, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1):
+        R, freq, z, nrm, wcat, d0, W_r = ctx.saved_tensors
+        ri_c, ri_a, cutoff, p = ctx.cfg
+        gR = None
+        if ctx.needs_input_grad[0]:
+            W = K.radial_head_emb_bwd(None, g_rbf3, g_rbf_h, g_rbf_out, g_rbf_W1, g_m0, None, d0, W_r, R, ri_c.idx32,
+                                      ri_a.idx32, freq, z, nrm, wcat, cutoff, p)
+            gR = K.segsum_multi([(W, *ri_a.csr, 1.0), (W, *ri_c.csr, -1.0)], ri_a.n_rows)
+        return (gR,) + (None,) * 12
+
+
+def radial_head_emb(R, freq, ri_c, ri_a, z, nrm, weights, cutoff, p, z_rows, emb_weight, W_emb, atom_features):
+    """-> m0 (E,128), rbf3, rbf_h, rbf_out (E,16), rbf_W1 (E,S,16); `weights` as in `radial_head_supported`, `z_rows` the
+    RowIndex of the atoms into the embedding table, `W_emb` the embedding Dense's weight."""
+    T_c, T_a, W_r = atom_term_tables(emb_weight, W_emb, atom_features)
+    return _RadialHeadEmb.apply(R, freq.detach(), ri_c, ri_a, z, nrm, _radial_head_wcat(weights), z_rows.idx32, T_c, T_a, W_r,
+                                float(cutoff), int(p))
+
+
 class _TripBasis(torch.autograd.Function):
     """(R) -> Y_l0 of every triplet angle in one launch (first-order adjoint)."""
 

@@ -609,6 +609,27 @@ int gn_radial_head_bwd_f32(const float* g_rbf, const float* g_rbf3, const float*
                            const float* g_rbf_W1, const float* R, const int32_t* id_c, const int32_t* id_a,
                            const float* freq, const float* z, const double* nrm, const float* wcat, float* W, int64_t E,
                            int NR, int S, int NI, float cutoff, int p, void* stream);
+/* ---- the radial head with the edge embedding inside (embedding_block.py:60-75, frozen weights) -----------------------
+ * gn_radial_head_fwd_f32 plus  z0[e,i] = sum_r rbf[e,r] Wr[r,i] + Tc[zrow[id_c[e]], i] + Ta[zrow[id_a[e]], i],
+ *   m0 = ssilu(z0), d0 = ssilu'(z0)   (E,NE), NE = 128 only (else hipErrorInvalidValue).
+ * Tc / Ta: the atom terms of the concat-Dense as tables over the embedding rows, (rows, NE) = emb W_c^T / emb W_a^T;
+ * zrow (atoms,): table row of every atom; Wr (NR, NE): the rbf columns of the Dense weight, transposed.  The sum runs in
+ * the order of gn_gemm_f32's small-K kernel with gadd1 / gadd2 (fma over r from zero, + Tc row, + Ta row): m0 is
+ * bit-identical to that launch on the same operands.  rbf may be NULL (not written); the ten projected rows are those of
+ * gn_radial_head_fwd_f32 bit for bit.  Tc, Ta, Wr, m0, d0 16-byte aligned. */
+int gn_radial_head_emb_fwd_f32(const float* R, const int32_t* id_c, const int32_t* id_a, const float* freq, const float* z,
+                               const double* nrm, const float* wcat, const int32_t* zrow, const float* Tc, const float* Ta,
+                               const float* Wr, float* rbf, float* rbf3, float* rbf_h, float* rbf_out, float* rbf_W1,
+                               float* m0, float* d0, int64_t E, int NR, int S, int NI, int NE, float cutoff, int p,
+                               void* stream);
+/* adjoint: gn_radial_head_bwd_f32 with  c_r += sum_i (ga[e,i] + gb[e,i]) d0[e,i] Wr[r,i]  (fp32, i = 0..NE-1 in order);
+ * ga / gb (E,NE): cotangents of m0, either or both may be NULL (both NULL: W is gn_radial_head_bwd_f32's bit for bit, d0
+ * and Wr are not read).  ga, gb, d0, Wr 16-byte aligned. */
+int gn_radial_head_emb_bwd_f32(const float* g_rbf, const float* g_rbf3, const float* g_rbf_h, const float* g_rbf_out,
+                               const float* g_rbf_W1, const float* ga, const float* gb, const float* d0, const float* Wr,
+                               const float* R, const int32_t* id_c, const int32_t* id_a, const float* freq, const float* z,
+                               const double* nrm, const float* wcat, float* W, int64_t E, int NR, int S, int NI, int NE,
+                               float cutoff, int p, void* stream);
 /* gemnet.py:288-311,420-451 -> basis_layers.py:130-131: Y[t,l] = Y_l0(atan2(max(|u x v|,1e-9), u.v)),
  * u = R[tc]-R[ta], v = R[tb]-R[ta]; theta (T,) optional output */
 int gn_trip_basis_fwd_f32(const float* R, const int32_t* tc, const int32_t* ta, const int32_t* tb, float* Y,
