@@ -1,0 +1,278 @@
+// The forward of the atom-row MLP stack as a kernel of its own (include/gemnet_hip.h, gn_atom_stack_fwd_f32).
+//
+// Why: the stacks that run on ATOM rows (AtomUpdateBlock: Dense + ResidualLayers + the tail projections of the concat layer,
+// M = 1 024 rows, 128 -> 128) are 64 workgroups of one 16-row tile each on 256 CUs: pure latency, and the chain
+// interpreter (chain2.hip) spends ~5.8 k cycles per GEMM op there for ~1.6 k of matrix-pipe phase — descriptor decode, weights
+// requested one op ahead, an epilogue shaped for five row blocks and any operand kind.  Here the program is fixed at compile
+// time (L ResidualLayers, T tails, final skip or not) and everything that does not change a value is specialised:
+//   * no op table: template parameters and a plain argument struct;
+//   * the tile's rows, then the weight fragments of the first AS_AHEAD ops are requested at kernel entry, those of op
+//     j + AS_AHEAD when op j's MFMA phase is over (one op is 32 VGPRs per lane);
+//   * all eight fragment reads of an op, its LDS residual and its global skip operand are issued before the first MFMA;
+//   * the epilogue runs in registers; one barrier per op, none between or behind the tails.
+// What is NOT changed is the arithmetic: the activation tile sits in LDS in the two-fp16-plane format of
+// chain_split_kernel<1, 2, false, true> (no row scale: the forward is not a linear program), the same swizzle, the same K order
+// per accumulator (hh | hl | lh, k-chunks 0..3), the same epilogue expressions in the same order — every output is bit for bit
+// what gn_chain_split_f32 writes for the same program (tests/test_gpu_atom_stack.py).
+// Weights: the planes gn_pack_weight_split_fmt(..., GN_SPLIT_F16X2) produces; no packing of its own.
+#include <type_traits>
+
+#include "common.h"
+
+#include "chain_split.h"
+
+// Bit-equality with chain_split_kernel needs the same roundings, and which multiply-add pairs the compiler contracts depends
+// on the code around them: in the interpreter the stages of an epilogue sit in different basic blocks (one uniform branch per
+// stage) and nothing is contracted across them, in the straight-line code below everything would be.  So contraction is off for
+// this file and the two fused operations the interpreter's code does have are written out (as_fma): the collapse of the
+// correction accumulators, and (s + x s) - s (x s) of the activation derivative.
+#pragma clang fp contract(off)
+
+// Knock-outs of diagnosis builds (never defined in the product library; tools/atom_stack_bench.py says how they are built):
+//   AS_EXP == 1  no weight fetch (zero fragments)      AS_EXP == 2  no activation arithmetic in the epilogue
+//   AS_EXP == 3  no MFMAs                              AS_EXP == 4  no barriers between the ops (timing only: the tile races)
+#ifndef AS_EXP
+#define AS_EXP 0
+#endif
+
+#ifndef AS_AHEAD
+// GEMM ops whose weight fragments are in flight or resident ahead of the running one.  Measured at M = 1 024 (7 GEMMs, us per
+// launch): 2 -> 7.52, 3 -> 7.65, 4 -> 7.75, 5 -> 7.91, 7 (everything at entry) -> 8.4: every CU asks the L2 for the same 64 KB per op
+// at the same time, and what is requested early only delays the first op's fragments (profiles/atom_stack_timeline.txt).
+#define AS_AHEAD 2
+#endif
+
+namespace {
+using namespace gn_split;
+
+__device__ __forceinline__ float as_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// ssilu(x) and ssilu'(x) from one sigmoid, rounded as gn_ssilu_pair is inside chain_split_kernel:
+// xs = x s;  d = fma(-s, xs, s + xs) / 0.6;  y = xs / 0.6
+__device__ __forceinline__ void as_ssilu_pair(float x, float& y, float& d) {
+  const float s = gn_sigmoid(x), xs = x * s;
+  const float t = s + xs;
+  d = as_fma(-s, xs, t) * GN_INV_06;
+  y = xs * GN_INV_06;
+}
+
+constexpr int AS_MAX_GEMMS = 7;    // Dense + 2 x 2 + 2 tails
+constexpr int AS_MAX_ROWS = 4096;  // where gn_chain_split_f32 runs 16-row tiles too
+
+struct as_fwd_args {
+  const float* x;
+  int M;
+  const uint4* W[AS_MAX_GEMMS];    // packed planes in program order: W0, (W1, W2) per layer, tails
+  float* z[5];                     // ssilu'(z) of the Dense and of both GEMMs of every layer
+  float s;                         // ResidualLayer scale
+  const float* res2;               // final skip (RES2)
+  float beta2;
+  float* y;
+  float* t[2];                     // tail outputs
+};
+
+template <int L, int T, bool RES2>
+__global__ __launch_bounds__(NT) void atom_stack_fwd_kernel(const as_fwd_args P) {
+  static_assert(L >= 0 && L <= 2 && T >= 0 && T <= 2 && (!RES2 || L > 0), "programs of the atom stack");
+  constexpr int NM = 1 + 2 * L;              // GEMM ops that write the tile
+  constexpr int NG = NM + T;
+  constexpr int PLANE = 16 * ROWB;           // bytes of one plane
+  constexpr int SLOT = 2 * PLANE;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * SLOT];
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int l15 = lane & 15;
+  const int lg = lane >> 4;
+  const int M = P.M;
+  const int row0 = (int)blockIdx.x * 16;
+
+  // weight fragments: [op][k-chunk][plane]; packed layout [col tile][k-chunk][plane][lane][8 fp16]
+  uint4 w[NG][4][2];
+  auto wload = [&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    if constexpr (j < NG) {
+      const uint4* __restrict__ const base = P.W[j] + (size_t)wave * (4 * 2 * 64) + lane;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) w[j][c][p] = AS_EXP == 1 ? make_uint4(0x3c003c00u + lane, 0u, 0u, 0u) : base[(c * 2 + p) * 64];
+    }
+  };
+  // the tile's rows are requested first: returns are in order, and the LOAD below must not wait behind the weight sets
+  const int lr = tid >> 5, lc = (tid & 31) << 2;      // 16 rows x 32 float4 = one float4 per thread
+  float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (row0 + lr < M) xv = *reinterpret_cast<const float4*>(P.x + (size_t)(row0 + lr) * SW + lc);
+  wload(std::integral_constant<int, 0>{});
+  if constexpr (AS_AHEAD > 1) wload(std::integral_constant<int, 1>{});
+  if constexpr (AS_AHEAD > 2) wload(std::integral_constant<int, 2>{});
+  if constexpr (AS_AHEAD > 3) wload(std::integral_constant<int, 3>{});
+  if constexpr (AS_AHEAD > 4) wload(std::integral_constant<int, 4>{});
+  if constexpr (AS_AHEAD > 5) wload(std::integral_constant<int, 5>{});
+  if constexpr (AS_AHEAD > 6) wload(std::integral_constant<int, 6>{});
+
+  auto plane_ptr = [&](int slot, int p) -> unsigned char* { return smem + slot * SLOT + p * PLANE; };
+  // byte offset of columns col .. col+3 (col % 4 == 0) of row `row` inside a plane (the swizzle of chain2.hip)
+  auto sw_off = [&](int row, int col) -> int { return row * ROWB + ((((col >> 3) ^ row) & 15) << 4) + ((col & 4) << 1); };
+  auto slot_write = [&](int slot, int row, int col, const float4 v) {
+    const int off = sw_off(row, col);
+    uint2 H, Lo;
+    split4h(v, H, Lo);
+    *reinterpret_cast<uint2*>(plane_ptr(slot, 0) + off) = H;
+    *reinterpret_cast<uint2*>(plane_ptr(slot, 1) + off) = Lo;
+  };
+
+  // LOAD: rows past M are zero
+  slot_write(0, lr, lc, xv);
+  lds_barrier();
+
+  // accumulator layout of this lane: row l15 of the tile, columns 16 wave + 4 lg .. + 3
+  const int n0 = wave * 16 + (lg << 2);
+  const bool ok = row0 + l15 < M;
+  const uint32_t off = (uint32_t)(row0 + l15) * (uint32_t)SW + (uint32_t)n0;   // M <= 4 096 rows
+  const int my = sw_off(l15, n0);
+
+  auto gemm = [&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    constexpr bool tail = j >= NM;
+    constexpr bool second = !tail && j > 0 && (j & 1) == 0;     // second GEMM of a ResidualLayer: residual, scale
+    constexpr bool last = j == NM - 1;
+    constexpr int a_slot = tail ? 1 : (j & 1);
+    constexpr int y_slot = a_slot ^ 1;
+    // every operand of the op is requested before its first MFMA
+    uint4 xf[4][2];
+    {
+      const unsigned char* xb = smem + a_slot * SLOT + l15 * ROWB;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const unsigned char* xp = xb + ((((c << 2) | lg) ^ l15) << 4);
+        xf[c][0] = *reinterpret_cast<const uint4*>(xp);
+        xf[c][1] = *reinterpret_cast<const uint4*>(xp + PLANE);
+      }
+    }
+    uint2 rH = make_uint2(0u, 0u), rL = make_uint2(0u, 0u);
+    if constexpr (second) {
+      rH = *reinterpret_cast<const uint2*>(plane_ptr(y_slot, 0) + my);
+      rL = *reinterpret_cast<const uint2*>(plane_ptr(y_slot, 1) + my);
+    }
+    float4 q2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (last && RES2) {
+      if (ok) q2 = *reinterpret_cast<const float4*>(P.res2 + off);
+    }
+    v4f acc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = (v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f16x8 ah = __builtin_bit_cast(f16x8, w[j][c][0]), al = __builtin_bit_cast(f16x8, w[j][c][1]);
+      const f16x8 yh = __builtin_bit_cast(f16x8, xf[c][0]), yl = __builtin_bit_cast(f16x8, xf[c][1]);
+      if constexpr (AS_EXP == 3) {      // (the operands stay live: one add per fragment)
+        acc[0][0] += __uint_as_float(w[j][c][0].x ^ xf[c][0].x); acc[1][0] += __uint_as_float(w[j][c][0].y ^ xf[c][1].y);
+        acc[2][0] += __uint_as_float(w[j][c][1].z ^ xf[c][0].z);
+        continue;
+      }
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl, acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh, acc[2], 0, 0, 0);
+    }
+    const v4f corr = acc[1] + acc[2];
+    float4 v = make_float4(as_fma(corr[0], H_DOWN, acc[0][0]), as_fma(corr[1], H_DOWN, acc[0][1]),
+                           as_fma(corr[2], H_DOWN, acc[0][2]), as_fma(corr[3], H_DOWN, acc[0][3]));
+    wload(std::integral_constant<int, j + AS_AHEAD>{});     // this op's fragments are dead
+    if constexpr (tail) {
+      if (ok) *reinterpret_cast<float4*>(P.t[j - NM] + off) = v;
+    } else {
+      // the activation and its derivative from one sigmoid; the factor is what the adjoint multiplies by
+      float4 d;
+      if constexpr (AS_EXP == 2) {
+        d = v;
+      } else {
+        as_ssilu_pair(v.x, v.x, d.x); as_ssilu_pair(v.y, v.y, d.y);
+        as_ssilu_pair(v.z, v.z, d.z); as_ssilu_pair(v.w, v.w, d.w);
+      }
+      if (ok) *reinterpret_cast<float4*>(P.z[j] + off) = d;
+      if constexpr (second) {
+        const float4 q = join4h(rH, rL);
+        const float b = P.s;
+        v.x = (v.x + q.x) * b; v.y = (v.y + q.y) * b; v.z = (v.z + q.z) * b; v.w = (v.w + q.w) * b;
+      }
+      if constexpr (last && RES2) {
+        if (ok) {
+          const float b = P.beta2;
+          v.x = (v.x + q2.x) * b; v.y = (v.y + q2.y) * b; v.z = (v.z + q2.z) * b; v.w = (v.w + q2.w) * b;
+        }
+      }
+      if constexpr (last) {
+        if (ok) *reinterpret_cast<float4*>(P.y + off) = v;
+      }
+      if constexpr (!last || T > 0) {      // somebody reads the tile again
+        slot_write(y_slot, l15, n0, ok ? v : make_float4(0.f, 0.f, 0.f, 0.f));
+        if constexpr (AS_EXP != 4) lds_barrier();
+      }
+    }
+  };
+  gemm(std::integral_constant<int, 0>{});
+  if constexpr (NG > 1) gemm(std::integral_constant<int, 1>{});
+  if constexpr (NG > 2) gemm(std::integral_constant<int, 2>{});
+  if constexpr (NG > 3) gemm(std::integral_constant<int, 3>{});
+  if constexpr (NG > 4) gemm(std::integral_constant<int, 4>{});
+  if constexpr (NG > 5) gemm(std::integral_constant<int, 5>{});
+  if constexpr (NG > 6) gemm(std::integral_constant<int, 6>{});
+}
+
+template <int L, int T, bool RES2>
+int launch_fwd(const as_fwd_args& a, hipStream_t st) {
+  hipLaunchKernelGGL((atom_stack_fwd_kernel<L, T, RES2>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int L, int T>
+int launch_fwd_res(const as_fwd_args& a, hipStream_t st) {
+  if constexpr (L > 0) {
+    if (a.res2) return launch_fwd<L, T, true>(a, st);
+  }
+  return launch_fwd<L, T, false>(a, st);
+}
+
+template <int L>
+int launch_fwd_tails(const as_fwd_args& a, int tails, hipStream_t st) {
+  switch (tails) {
+    case 0: return launch_fwd_res<L, 0>(a, st);
+    case 1: return launch_fwd_res<L, 1>(a, st);
+    default: return launch_fwd_res<L, 2>(a, st);
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+extern "C" int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tails, const void* const* W, float* const* z,
+                                     float s, const float* res2, float beta2, float* y, float* const* t, void* stream) {
+  if (M <= 0) return 0;
+  if (M > AS_MAX_ROWS || layers < 0 || layers > 2 || tails < 0 || tails > 2) return (int)hipErrorInvalidValue;
+  if (!x || !y || !W || !z || (tails && !t) || (res2 && layers == 0)) return (int)hipErrorInvalidValue;
+  if (!aligned16(x) || !aligned16(y) || !aligned16(res2)) return (int)hipErrorInvalidValue;
+  as_fwd_args a = {};
+  a.x = x; a.M = M; a.s = s; a.res2 = res2; a.beta2 = beta2; a.y = y;
+  const int nm = 1 + 2 * layers;
+  for (int j = 0; j < nm + tails; ++j) {
+    if (!W[j] || !aligned16(W[j])) return (int)hipErrorInvalidValue;
+    a.W[j] = static_cast<const uint4*>(W[j]);
+  }
+  for (int j = 0; j < nm; ++j) {
+    if (!z[j] || !aligned16(z[j])) return (int)hipErrorInvalidValue;
+    a.z[j] = z[j];
+  }
+  for (int j = 0; j < tails; ++j) {
+    if (!t[j] || !aligned16(t[j])) return (int)hipErrorInvalidValue;
+    a.t[j] = t[j];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (layers) {
+    case 0: return launch_fwd_tails<0>(a, tails, st);
+    case 1: return launch_fwd_tails<1>(a, tails, st);
+    default: return launch_fwd_tails<2>(a, tails, st);
+  }
+}

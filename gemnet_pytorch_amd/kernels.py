@@ -1443,6 +1443,99 @@ def chain_grouped_supported(mode=None):
     return (mode or current_mode()) in ("h3", "split6") and CHAIN_LAYOUT == "tall"
 
 
+# The forward of the atom-row stacks (AtomUpdateBlock: Dense + ResidualLayers + tail projections, M <= 4 096 rows of 128
+# columns, mode "h3") runs on a kernel of its own (csrc/atom_stack.hip) with bit-identical results;
+# GEMNET_ATOM_STACK=0 hands those programs to gn_chain_split_f32 like every other.
+USE_ATOM_STACK = os.environ.get("GEMNET_ATOM_STACK", "1") == "1"
+ATOM_STACK_MAX_ROWS = 4096     # up to here gn_chain_split_f32 runs 16-row tiles as well
+ATOM_STACK_WIDTH = 128
+
+
+def _atom_mat(t, M):
+    return (torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == (M, ATOM_STACK_WIDTH)
+            and t.is_contiguous() and t.data_ptr() % 16 == 0)
+
+
+def _atom_gemm_plain(o):
+    """A GEMM op of 128 x 128 with none of the operand forms the atom-row kernel leaves out."""
+    return (o["kind"] == "gemm" and tuple(o["W"].shape) == (ATOM_STACK_WIDTH, ATOM_STACK_WIDTH) and o["alpha"] == 1.0
+            and o["gadd1"] is None and o["gadd2"] is None and o["mul"] is None and o["res_rows"] is None
+            and o["y2"] < 0 and o["Z2"] is None and o["out2"] is None and o.get("add") is None and o.get("add2") is None)
+
+
+def atom_stack_match(prog, mode=None):
+    """Is `prog` the forward of an atom-row MLP stack in the form csrc/atom_stack.hip runs?
+         LOAD x -> 0;  GEMM W0 (act, ssilu' stored) 0 -> 1;  L in {0, 1, 2} times [GEMM W1 (act) 1 -> 0,  GEMM W2 (act) 0 -> 1 with
+         the LDS residual (. + slot 1) * s];  on the last of them the stack's output and (L > 0) the optional global skip
+         (. + res2) * beta2;  T in {0, 1, 2} tail GEMMs 1 -> their own output
+    at width 128 -> 128, 1 <= M <= 4 096, mode "h3" in the tall layout.  -> dict(x, W [ops], z, s, res2, beta2, y, t) or None
+    (gathered adds, parked or intermediate skips, a residual of the Dense, other widths / modes: not this kernel)."""
+    M, ops = prog.M, prog.ops
+    if not (1 <= M <= ATOM_STACK_MAX_ROWS) or (mode or current_mode()) != "h3" or CHAIN_LAYOUT != "tall":
+        return None
+    if len(ops) < 2 or len(ops) > 8:
+        return None
+    o = ops[0]
+    if not (o["kind"] == "load" and o["slot"] == 0 and o["rows"] is None and o.get("alpha", 1.0) == 1.0 and o.get("y2", -1) < 0
+            and o.get("Z2") is None and o.get("add2") is None and _atom_mat(o["src"], M)):
+        return None
+    n_main = 0
+    while 1 + n_main < len(ops) and ops[1 + n_main]["kind"] == "gemm" and ops[1 + n_main]["slot"] >= 0:
+        n_main += 1
+    main, tails = ops[1:1 + n_main], ops[1 + n_main:]
+    L = (n_main - 1) // 2
+    if n_main not in (1, 3, 5) or len(tails) > 2:
+        return None
+    s, res2, beta2 = 1.0, None, 1.0
+    for j, g in enumerate(main):
+        last = j + 1 == len(main)
+        if not (_atom_gemm_plain(g) and g["act"] and g.get("pre_deriv") and _atom_mat(g["pre_out"], M)
+                and g["a_slot"] == (j & 1) and g["slot"] == 1 - (j & 1)):
+            return None
+        if (g["out"] is not None) != last or (last and not _atom_mat(g["out"], M)):
+            return None
+        second = j > 0 and j % 2 == 0
+        if second:
+            if not (isinstance(g["res"], int) and g["res"] == 1 and (j == 2 or g["beta"] == s)):
+                return None
+            s = g["beta"]
+        elif g["res"] is not None:
+            return None
+        if g["res2"] is not None:
+            if not (second and last and _atom_mat(g["res2"], M)):
+                return None
+            res2, beta2 = g["res2"], g["beta2"]
+    for g in tails:
+        if not (_atom_gemm_plain(g) and not g["act"] and g["a_slot"] == 1 and g["slot"] < 0 and g["pre_out"] is None
+                and g["res"] is None and g["res2"] is None and _atom_mat(g["out"], M)):
+            return None
+    return dict(x=ops[0]["src"], L=L, gemms=main + tails, z=[g["pre_out"] for g in main], s=s, res2=res2, beta2=beta2,
+                y=main[-1]["out"], t=[g["out"] for g in tails])
+
+
+def _atom_stack_fwd(M, m):
+    """Launch gn_atom_stack_fwd_f32 for a matched program (atom_stack_match)."""
+    fmt = SPLIT_FORMAT["h3"]
+    require_device(m["x"], m["y"], m["res2"], *m["z"], *m["t"])
+    Ws = []
+    for g in m["gemms"]:
+        Wp = g.get("packed")
+        if Wp is None:
+            _mat(g["W"])
+            Wp = pack_weight_split(g["W"], fmt=fmt)
+        elif getattr(Wp, "_gn_fmt", 0) != fmt:
+            raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a launch in "
+                               f"mode 'h3' (format {fmt})")
+        Ws.append(Wp)
+    z, t = m["z"], m["t"]
+    arr = ctypes.c_void_p
+    check(_lib.load().gn_atom_stack_fwd_f32(ptr(m["x"]), int(M), int(m["L"]), len(t), (arr * len(Ws))(*[addr(W) for W in Ws]),
+                                            (arr * len(z))(*[addr(a) for a in z]), float(m["s"]), ptr(m["res2"]),
+                                            float(m["beta2"]), ptr(m["y"]), (arr * max(1, len(t)))(*[addr(a) for a in t]),
+                                            stream()),
+          "gn_atom_stack_fwd_f32")
+
+
 def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
     """Run a ChainProgram (one launch).
     groups > 0 (gn_chain_split_grouped_f32): `prog` describes group 0 — M rows, operands = the first slab of stacked tensors
@@ -1452,6 +1545,10 @@ def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
     if len(ops) > GN_CHAIN_MAX_OPS:
         raise ValueError("chain program too long")
     mode = mode or current_mode()
+    if USE_ATOM_STACK and not groups and prog.M <= ATOM_STACK_MAX_ROWS:
+        m = atom_stack_match(prog, mode)
+        if m is not None:
+            return _atom_stack_fwd(prog.M, m)
     nprod = CHAIN_MODES[mode]
     if nprod and not chain_split_supported(prog):
         nprod = 0

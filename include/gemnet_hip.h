@@ -179,6 +179,17 @@ int gn_chain_split_f32(const gn_chain_args* args, int nprod, void* stream);
 #define GN_CHAIN_MAX_GROUPS 8
 #define GN_CHAIN_GROUP_TILE_ROWS 32
 int gn_chain_split_grouped_f32(const gn_chain_args* args, int nprod, int groups, int group_pitch, int tile_rows, void* stream);
+/* The forward of the atom-row MLP stack (atom_update_block.py:100-172 plus the atom terms of the concat layer,
+ * embedding_block.py:70-72) as a kernel of its own (csrc/atom_stack.hip; additive, ABI 16): for M <= 4 096 rows of 128 columns
+ *   y = ssilu(x W[0]^T);  per ResidualLayer k < layers: y = (y + ssilu(ssilu(y W[1+2k]^T) W[2+2k]^T)) * s;
+ *   res2 (layers > 0 only): y = (y + res2) * beta2;  t[i] = y W[1 + 2 layers + i]^T for i < tails
+ * i.e. the program LOAD, GEMM(act, pre_deriv) x (1 + 2 layers), tail GEMMs that ops.stack hands to gn_chain_split_f32 with
+ * nprod = GN_CHAIN_F16X2, with the same arithmetic in the same order: every output is bit for bit that launch's.
+ * W: host array of 1 + 2 layers + tails packed weights (gn_pack_weight_split_fmt, GN_SPLIT_F16X2, N = K = 128) in program order;
+ * z: host array of 1 + 2 layers (M,128) outputs that receive ssilu'(pre-activation) of each GEMM; t: host array of `tails`
+ * (M,128) outputs.  layers 0..2, tails 0..2; every matrix contiguous and 16-byte aligned; else hipErrorInvalidValue. */
+int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tails, const void* const* W, float* const* z, float s,
+                          const float* res2, float beta2, float* y, float* const* t, void* stream);
 /* W (N,K) fp32 with row pitch ldw — or, trans != 0, the (K,N) matrix whose transpose is the weight — -> three bf16
  * planes in MFMA-fragment order; `out` holds gn_pack_weight_split_bytes(N,K) bytes (16-byte aligned). */
 int gn_pack_weight_split(const float* W, int N, int K, int ldw, int trans, void* out, void* stream);
