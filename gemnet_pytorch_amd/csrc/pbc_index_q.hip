@@ -111,27 +111,6 @@ __global__ void pbq_intm_kernel(const int32_t* __restrict__ int_a, const int32_t
   for (int64_t p = in_ptr[b]; p < in_ptr[b + 1] && q < n_db; ++p, ++q) { exp_intm_db[q] = in_src[p]; exp_intm_ab[q] = (int32_t)k; }
 }
 
-// inclusive scan of one int per lane over the wave
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// interaction edges (a, b, *) inside a's range [lo0, hi0) of int_b (sorted by b)
-__device__ __forceinline__ void int_range(const int32_t* __restrict__ int_b, int64_t lo0, int64_t hi0, int b, int64_t& lo,
-                                          int64_t& hi) {
-  int64_t l = lo0, h = hi0;
-  while (l < h) { const int64_t md = (l + h) >> 1; if (int_b[md] < b) l = md + 1; else h = md; }
-  lo = l;
-  h = hi0;
-  while (l < h) { const int64_t md = (l + h) >> 1; if (int_b[md] <= b) l = md + 1; else h = md; }
-  hi = l;
-}
-
 struct QuadOut {
   int32_t *red_ca, *exp_db, *red_cab, *exp_abd, *kidx;
 };

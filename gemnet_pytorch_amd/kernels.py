@@ -7,6 +7,7 @@ lives under tests/ and is never imported by the product.)
 """
 import contextlib
 import ctypes
+import functools
 import os
 import threading
 
@@ -324,6 +325,42 @@ def index_padded_q(builder, R, caps, a_cap, n_groups, deg_bound, staging, bufs, 
         builder.sum_n2, builder.cutoff, builder.int_cutoff, ptr(builder.ws), e_cap, t_cap, eint_cap, i_cap, q_cap, int(a_cap),
         int(n_groups), int(deg_bound), ptr(staging), c_arr, ptr(state), stream()),
         "gn_index_gpu_padded_q")
+
+
+@functools.lru_cache(maxsize=64)
+def pbc_qindex_ws_bytes(n_atoms, e_cap, eint_cap):
+    """Bytes of the workspace gn_pbc_qindex_padded needs for `n_atoms` atoms and capacities of `e_cap` edges and `eint_cap`
+    interaction edges (its staging array: 7 e_cap + 5 eint_cap int32).  A pure function of the three sizes, remembered: the
+    size check of `pbc_index_padded_q` inside a capture then asks nothing of the library."""
+    return int(_lib.load().gn_pbc_qindex_ws_bytes(int(n_atoms), int(e_cap), int(eint_cap), None))
+
+
+PADDED_QP_KEYS = PADDED_Q_KEYS + ("cell_offsets", "int_cell_offsets")
+
+
+def pbc_index_padded_q(builder, R, cell, caps, a_cap, n_groups, deg_bound, ws, staging, bufs, state):
+    """The quadruplet index build of `builder` (pbc.PeriodicQuadGraphBuilder) for positions R (A,3) and `cell` (>= B rows of
+    (3,3)), both float32 ON THE DEVICE, straight into the capacity-sized arrays `bufs` (the sixteen arrays PADDED_Q_KEYS +
+    cell_offsets (e_cap,3) + int_cell_offsets (eint_cap,3): int32) with the dummy molecule's pad rows behind the batch — no
+    read-back, capturable (gn_pbc_qindex_padded; caps = (e_cap, t_cap, eint_cap, i_cap, q_cap); ws: uint8 of
+    pbc_qindex_ws_bytes(A, e_cap, eint_cap), staging: int32[7 e_cap + 5 eint_cap], state: int32[8], see the header)."""
+    require_device(R, cell, ws, staging, state)
+    assert R.dtype == torch.float32 and R.is_contiguous() and tuple(R.shape) == (builder.A, 3)
+    assert cell.dtype == torch.float32 and cell.is_contiguous() and cell.shape[0] >= builder.B and tuple(cell.shape[1:]) == (3, 3)
+    e_cap, t_cap, eint_cap, i_cap, q_cap = (int(c) for c in caps)
+    assert staging.dtype == torch.int32 and staging.numel() >= 7 * e_cap + 5 * eint_cap
+    assert state.dtype == torch.int32 and state.numel() >= 8
+    assert ws.dtype == torch.uint8 and ws.numel() >= pbc_qindex_ws_bytes(builder.A, e_cap, eint_cap)
+    want = dict(zip(PADDED_Q_KEYS, (e_cap,) * 4 + (t_cap,) * 2 + (eint_cap,) * 2 + (i_cap,) * 4 + (q_cap,) * 4))
+    for k, n in want.items():
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == n and bufs[k].is_contiguous(), k
+    for k, n in (("cell_offsets", e_cap), ("int_cell_offsets", eint_cap)):
+        assert bufs[k].dtype == torch.int32 and tuple(bufs[k].shape) == (n, 3) and bufs[k].is_contiguous(), k
+    c_arr = (ctypes.c_void_p * 18)(*[addr(bufs[k]) for k in PADDED_QP_KEYS])
+    check(_lib.load().gn_pbc_qindex_padded(
+        ptr(R), ptr(cell), ptr(builder.pbc), ptr(builder.mol_off), ptr(builder.atom_mol), builder.B, builder.A, builder.cutoff,
+        builder.int_cutoff, ptr(ws), e_cap, t_cap, eint_cap, i_cap, q_cap, int(a_cap), int(n_groups), int(deg_bound), ptr(staging),
+        c_arr, ptr(state), stream()), "gn_pbc_qindex_padded")
 
 
 def cbf_project_supported(rad, y, W):

@@ -39,15 +39,17 @@ class MoleculeInputs(dict):
 class DeviceMolecule:
     """Drop-in for the reference's `Molecule(R, Z, cutoff, int_cutoff, triplets_only)` (ase_calculator.py:23-104)."""
 
-    def __init__(self, R, Z, cutoff, int_cutoff, triplets_only=False, cell=None, pbc=None):
-        """cell (3,3) rows = lattice vectors, pbc (3,) bool (default all periodic): a periodic structure (pbc.py; GemNet-T)."""
+    def __init__(self, R, Z, cutoff, int_cutoff, triplets_only=False, cell=None, pbc=None, periodic_quadruplets=False):
+        """cell (3,3) rows = lattice vectors, pbc (3,) bool (default all periodic): a periodic structure (pbc.py; GemNet-T).
+        `periodic_quadruplets=True`: a periodic structure for a GemNet-Q (`triplets_only=False`) that opts in with
+        `model.periodic_quadruplets` and `model.periodic_quadruplets_dynamic`; without it such a molecule raises."""
         R = np.asarray(R)
         Z = np.asarray(Z)
         assert R.shape == (len(Z), 3)
         self.cutoff, self.int_cutoff, self.triplets_only = cutoff, int_cutoff, triplets_only
         self.cell = None if cell is None else np.asarray(cell, dtype=np.float64).reshape(3, 3)
         self.pbc = np.ones(3, dtype=bool) if pbc is None else np.asarray(pbc, dtype=bool).reshape(3)
-        if self.cell is not None and not triplets_only:
+        if self.cell is not None and not triplets_only and not periodic_quadruplets:
             raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
         self.R = R
         self.Z = Z
@@ -82,12 +84,15 @@ class DeviceMolecule:
 def predict_periodic(model, inputs, stress=False, to_host=False):
     """A periodic `MoleculeInputs` -> (E, F) or (E, F, S).  Served like a molecule (predict_molecule) from a cached
     `runtime.DynamicForceField(cell=, pbc=)`: the image neighbour list is built INSIDE the replayed graph for the positions and
-    the cell of the call, so an MD step is one replay.  The cache key is the layout, the cutoff, the periodic axes and the
+    the cell of the call, so an MD step is one replay.  A GemNet-Q is served the same way when it opts in
+    (`model.periodic_quadruplets` and `model.periodic_quadruplets_dynamic`; gn_pbc_qindex_padded), otherwise it raises.  The cache
+    key is the layout, both cutoffs, the periodic axes and the
     device — the cell is data.  GEMNET_INDEX_IN_GRAPH=0: the host-sized path (device list per call, padded, one replay)."""
     R, Z, N, cell = inputs["R"], inputs["Z"], inputs["N"], inputs["cell"]
     if not R.is_cuda:
         raise RuntimeError("periodic structures run on a HIP device only (no CPU fallback); DeviceMolecule.to('cuda')")
-    if not model.triplets_only:
+    from .padded import periodic_quad_opted_in
+    if not model.triplets_only and not periodic_quad_opted_in(model):
         raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
     if stress and getattr(model, "direct_forces", False):
         raise ValueError("a direct-force model has no stress (its forces are not the gradient of its energy)")
@@ -95,7 +100,7 @@ def predict_periodic(model, inputs, stress=False, to_host=False):
     lk = inputs.layout_key
     if lk is None:
         lk = (Z.detach().cpu().numpy().astype(np.int64).tobytes(), tuple(int(n) for n in N.tolist()))
-    key = (lk, inputs.cutoff, pbc.tobytes(), R.device.index)
+    key = (lk, inputs.cutoff, inputs.int_cutoff, pbc.tobytes(), R.device.index)
     cache = model.__dict__.setdefault("_md_fields", {})
     ff = cache.get(key)
     was_training = model.training

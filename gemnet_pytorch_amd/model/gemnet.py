@@ -99,6 +99,10 @@ class GemNet(torch.nn.Module):
         # of pbc.PeriodicQuadGraphBuilder, the quadruplet geometry on the edge and interaction-edge vectors (csrc/pbc_quad.hip):
         # (E, F[, S]).  False: such a call raises.  Training and direct forces with a cell stay GemNet-T only
         self.periodic_quadruplets = False
+        # opt-in on top of `periodic_quadruplets`: the runners that follow a MOVING periodic system (padded.PaddedGraphRunner
+        # with cell= and quad_caps=, runtime.DynamicForceField(cell=), md.DeviceMolecule / predict_periodic) accept this model —
+        # the quadruplet index build inside the captured graph (csrc/pbc_index_qp.hip).  False: they raise as before
+        self.periodic_quadruplets_dynamic = False
         # arithmetic of the LDS-resident Dense stacks: None = the package default ("h3": fp32 operands as two fp16 planes,
         # three products), "split6" = three bf16 planes / six products (fp32 exponent range), "f32" = the f32-input MFMA — all
         # three at fp32 accuracy (force MAE 1e-6 .. 4e-6 eV/A against float64).  Single-plane bf16 / three-product modes exist

@@ -31,7 +31,10 @@ intermediate triplet).  A pad row only needs valid indices and a non-degenerate 
 
 Periodic structures (pbc.py; GemNet-T): a runner built with `cell=` pads `cell_offsets` with zeros, gives the dummy molecule the
 identity as its cell and returns the stress as well; `attach_builder(pbc.PeriodicGraphBuilder)` puts the image neighbour list
-(gn_pbc_index_padded_t: positions AND cell read at replay time) inside the graph.
+(gn_pbc_index_padded_t: positions AND cell read at replay time) inside the graph.  A GemNet-Q that opts in
+(`model.periodic_quadruplets` and `model.periodic_quadruplets_dynamic`) runs the same way with `quad_caps=`: `int_cell_offsets`
+is padded with zeros as well and `attach_builder(pbc.PeriodicQuadGraphBuilder)` builds all eighteen arrays inside the graph
+(gn_pbc_qindex_padded).
 
 Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
 `Trainer.enable_padded_graph` (the training step in the same form), `bench.py` (`extra.dynamic_shape`,
@@ -164,6 +167,9 @@ def pad_indices(idx, n_atoms, e_cap, t_cap, n_groups, dtype=torch.int64, quad_ca
         out["id4_expand_abd"] = torch.cat([idx["id4_expand_abd"].to(dtype), im.to(dtype)])
         out["id4_reduce_cab"] = torch.cat([idx["id4_reduce_cab"].to(dtype), im.to(dtype)])
         out["id4_expand_db"] = torch.cat([idx["id4_expand_db"].to(dtype), db[im - I].to(dtype) if qp else db[:0].to(dtype)])
+        if "int_cell_offsets" in idx:   # periodic quadruplet batch (pbc.PeriodicQuadGraphBuilder): pad interaction edges, image 0
+            ioffs = idx["int_cell_offsets"].reshape(-1, 3)
+            out["int_cell_offsets"] = torch.cat([ioffs.to(dtype), torch.zeros(eintp, 3, device=dev, dtype=dtype)])
     return out
 
 
@@ -182,6 +188,11 @@ def dummy_positions(n_groups, like, offset=1.0e3, quad=False, bond=1.0):
     rows = [[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]] + ([[1.0, 0.0, 1.0]] if quad else [])
     d = bond * torch.tensor(rows, device=like.device, dtype=like.dtype)
     return (base[:, None, :] + d[None, :, :]).reshape(-1, 3)
+
+
+def periodic_quad_opted_in(model):
+    """Does `model` opt in to periodic GemNet-Q on the paths that follow a moving system (both switches of model/gemnet.py)?"""
+    return bool(getattr(model, "periodic_quadruplets", False)) and bool(getattr(model, "periodic_quadruplets_dynamic", False))
 
 
 def dummy_bond(model):
@@ -219,7 +230,7 @@ class PaddedGraphRunner:
         # (E, F, S) from a periodic autograd-force model; a direct-force one (GemNet.periodic_direct_forces) has no stress
         self.with_stress = self.periodic and not getattr(model, "direct_forces", False)
         if self.periodic:
-            if self.quad:
+            if self.quad and not periodic_quad_opted_in(model):
                 raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
             if a_cap is not None:
                 raise NotImplementedError("periodic cells: fixed structure layout only (no a_cap)")
@@ -265,6 +276,8 @@ class PaddedGraphRunner:
                 raise ValueError(f"cell must have shape ({self.n_mol}, 3, 3); got {tuple(c.shape)}")
             self.inputs["cell"] = torch.cat([c, torch.eye(3, device=dev, dtype=torch.float32)[None]]).contiguous()
             self.inputs["cell_offsets"] = torch.zeros(self.e_cap, 3, dtype=torch.int32, device=dev)
+            if self.quad:
+                self.inputs["int_cell_offsets"] = torch.zeros(int(quad_caps[0]), 3, dtype=torch.int32, device=dev)
         self.pbc = None if pbc is None else torch.as_tensor(pbc).detach().cpu().reshape(-1, 3).bool()
         self.quad_caps = tuple(int(c) for c in quad_caps) if self.quad else None
         if max((self.e_cap, self.t_cap, self.A_tot) + (self.quad_caps or ())) >= 2 ** 31:
@@ -353,6 +366,9 @@ class PaddedGraphRunner:
         if self.periodic != ("cell_offsets" in idx):
             raise ValueError("a periodic runner takes index dicts with 'cell_offsets' (pbc.PeriodicGraphBuilder), a molecular "
                              "one those without")
+        if self.periodic and self.quad and "int_cell_offsets" not in idx:
+            raise ValueError("a periodic quadruplet runner takes the index dicts of pbc.PeriodicQuadGraphBuilder "
+                             "('int_cell_offsets')")
         if cell is not None and not self.periodic:
             raise ValueError("this runner was built without a cell")
         A = int(R.shape[0])
@@ -401,6 +417,10 @@ class PaddedGraphRunner:
         if self.periodic:
             buf["cell_offsets"][:E].copy_(idx["cell_offsets"].reshape(-1, 3))
             buf["cell_offsets"][E:].zero_()
+            if self.quad:
+                Eint = int(idx["id4_int_a"].shape[0])
+                buf["int_cell_offsets"][:Eint].copy_(idx["int_cell_offsets"].reshape(-1, 3))
+                buf["int_cell_offsets"][Eint:].zero_()
             if cell is not None:
                 self._set_cell(cell)
         buf["R"][:self.A].copy_(R)
@@ -497,10 +517,12 @@ class PaddedGraphRunner:
         reports through `index_error()`."""
         if self.variable_atoms:
             raise NotImplementedError("the in-graph index build needs a fixed molecule layout (no a_cap)")
-        from .pbc import PeriodicGraphBuilder
+        from .pbc import PeriodicGraphBuilder, PeriodicQuadGraphBuilder
         pb = isinstance(builder, PeriodicGraphBuilder)
         if pb != self.periodic or (pb and builder.B != self.n_mol):
             raise ValueError("builder and runner describe different systems (periodic / molecular)")
+        if pb and isinstance(builder, PeriodicQuadGraphBuilder) != self.quad:
+            raise ValueError("builder and runner describe different systems (triplets / quadruplets)")
         if pb and self.pbc is not None and not torch.equal(self.pbc.expand(self.n_mol, 3), torch.as_tensor(builder.pbc_host)):
             raise ValueError("builder and runner differ in their periodic axes")
         if (not pb and builder.triplets_only == self.quad) or builder.A != self.A or self.index_dtype != torch.int32:
@@ -513,7 +535,12 @@ class PaddedGraphRunner:
         if pb:      # gn_pbc_index_padded_t: the four edge arrays + the offsets are staged, triplets go straight to the buffers
             from . import kernels as K
             n_stage = 7 * self.e_cap
-            self._pbc_ws = torch.zeros(K.pbc_index_ws_bytes(self.A, self.e_cap), dtype=torch.uint8, device=dev)
+            if self.quad:   # gn_pbc_qindex_padded: the interaction edges and their offsets are staged as well
+                n_stage += 5 * self.quad_caps[0]
+                n_ws = K.pbc_qindex_ws_bytes(self.A, self.e_cap, self.quad_caps[0])
+            else:
+                n_ws = K.pbc_index_ws_bytes(self.A, self.e_cap)
+            self._pbc_ws = torch.zeros(n_ws, dtype=torch.uint8, device=dev)
         # (zeros: a build whose interaction-edge count alone exceeds its capacity skips the edge kernel, and the count kernels
         # behind it must not index with uninitialised staging on the very first build)
         self._staging = torch.zeros(n_stage, dtype=torch.int32, device=dev)
@@ -524,7 +551,11 @@ class PaddedGraphRunner:
 
     def _index_in_graph(self):
         from . import kernels as K
-        if self.periodic:
+        if self.periodic and self.quad:
+            K.pbc_index_padded_q(self.builder, self.inputs["R"][:self.A], self.inputs["cell"], (self.e_cap, self.t_cap) + self.quad_caps,
+                                 self.a_cap, self.G, self.pad_degree_bound(), self._pbc_ws, self._staging, self.inputs,
+                                 self._idx_state)
+        elif self.periodic:
             K.pbc_index_padded_t(self.builder, self.inputs["R"][:self.A], self.inputs["cell"], self.e_cap, self.t_cap,
                                  self.a_cap, self.G, self.pad_degree_bound(), self._pbc_ws, self._staging, self.inputs,
                                  self._idx_state)
@@ -547,7 +578,8 @@ class PaddedGraphRunner:
     def index_sizes(self):
         """(E, T[, Eint, I, Q]) of the last completed in-graph index build."""
         h = self._idx_host
-        return (int(h[1]), int(h[2])) + ((int(h[4]), int(h[5]), int(h[6])) if self.quad else ())
+        k = 5 if self.periodic else 4       # (a periodic build reports the largest in-degree in state[4])
+        return (int(h[1]), int(h[2])) + ((int(h[k]), int(h[k + 1]), int(h[k + 2])) if self.quad else ())
 
     def reset_index_state(self):
         self._idx_state.zero_()

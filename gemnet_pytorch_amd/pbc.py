@@ -17,7 +17,8 @@ whose backward is the adjoint kernel of the head: one first-order `loss.backward
 
 The builder reads two sizes back per call.  For MD — a new list every step — the same list is built without a read-back inside a
 captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
-runtime.DynamicForceField(cell=...), md.predict_periodic.
+runtime.DynamicForceField(cell=...), md.predict_periodic.  The same holds for PeriodicQuadGraphBuilder (four read-backs per call)
+and a GemNet-Q that opts in with `model.periodic_quadruplets_dynamic`: csrc/pbc_index_qp.hip, kernels.pbc_index_padded_q.
 """
 import numpy as np
 import torch

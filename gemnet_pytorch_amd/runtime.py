@@ -234,7 +234,8 @@ class DynamicForceField:
     latter since round 5: padded.py pads interaction edges, intermediate triplets and quadruplets as well — GemNet-Q is the
     model of the reference's MD example, ase_example.ipynb cell 13).
 
-    Periodic structures (`cell=` (B,3,3), `pbc=`; GemNet-T): the image neighbour list of pbc.PeriodicGraphBuilder, built inside
+    Periodic structures (`cell=` (B,3,3), `pbc=`; GemNet-T, and a GemNet-Q with `model.periodic_quadruplets` and
+    `model.periodic_quadruplets_dynamic` set — pbc.PeriodicQuadGraphBuilder / gn_pbc_qindex_padded, all five capacities): the image neighbour list of pbc.PeriodicGraphBuilder, built inside
     the replayed graph (gn_pbc_index_padded_t) for the positions AND the cell of the step:
 
         ff = DynamicForceField(model, Z, N_host, cutoff, int_cutoff, cell=cell, pbc=pbc)
@@ -254,10 +255,14 @@ class DynamicForceField:
         self.margin = float(margin)
         self.periodic = cell is not None
         if self.periodic:
-            from .pbc import PeriodicGraphBuilder
-            if not model.triplets_only:
+            from .padded import periodic_quad_opted_in
+            from .pbc import PeriodicGraphBuilder, PeriodicQuadGraphBuilder
+            if model.triplets_only:
+                self.builder = PeriodicGraphBuilder(self.N_host, cutoff, pbc=pbc, device=Z.device)
+            elif periodic_quad_opted_in(model):     # (model.periodic_quadruplets and model.periodic_quadruplets_dynamic)
+                self.builder = PeriodicQuadGraphBuilder(self.N_host, cutoff, int_cutoff, pbc=pbc, device=Z.device)
+            else:
                 raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
-            self.builder = PeriodicGraphBuilder(self.N_host, cutoff, pbc=pbc, device=Z.device)
             # private cell buffer: the caller's tensor may change between the step and its repetition after a re-size
             self.cell = torch.as_tensor(cell).detach().to(device=Z.device, dtype=torch.float32).reshape(-1, 3, 3).clone()
             self._good_cell = self.cell.clone()      # the last cell a completed step accepted (restored after a rejected one)
@@ -277,7 +282,7 @@ class DynamicForceField:
         with torch.cuda.stream(self._bstream):
             if self.periodic:                            # (check_cell raises the ValueErrors of a cell it cannot serve)
                 idx = self.builder(R, self.cell, dtype=torch.int32)
-                idx = {k: v for k, v in idx.items() if k not in ("batch_seg", "Kidx3")}
+                idx = {k: v for k, v in idx.items() if k not in ("batch_seg", "Kidx3", "Kidx4")}
             else:
                 idx = self.builder(R, dtype=torch.int32)     # as built: the padded runner keeps its index buffers in int32
         main.wait_stream(self._bstream)
@@ -340,6 +345,8 @@ class DynamicForceField:
                 # quad — groups for the padding left when the list shrinks by 4 x margin, two incoming edges per quad
                 pad_max = e_cap - int(E * (1 - min(1.0, 4 * m)))
                 groups = max(1, -(-(-(-pad_max // 4)) // max(self.deg // 2, 1)))
+                if not self.model.triplets_only:    # units of six, two incoming edges per unit on atoms a and b of a group
+                    groups = max(1, -(-(-(-pad_max // 6)) // max(self.deg // 2, 1)))
             quad_caps = None
             if not self.model.triplets_only:
                 Eint, I, Q = sizes[2:5]

@@ -900,6 +900,36 @@ int gn_pbc_qindex_quad(const int32_t* mol_off, const int32_t* atom_mol, int A, c
                        int32_t* id4_reduce_intm_ab, int32_t* id4_expand_intm_db, int32_t* id4_expand_intm_ab,
                        int32_t* id4_reduce_ca, int32_t* id4_expand_db, int32_t* id4_reduce_cab, int32_t* id4_expand_abd,
                        int32_t* Kidx4, void* stream);
+/* Capacity form of the periodic quadruplet build (csrc/pbc_index_qp.hip; additive, ABI 16): the periodic twin of
+ * gn_index_gpu_padded_q on top of what gn_pbc_index_padded_t does for edges and triplets — image neighbour list, interaction
+ * edges, intermediate triplets, quadruplets and the model as ONE capturable graph; no read-back, every launch sized by the
+ * capacities, no atomics, no sort.  R (A,3), cell (>= B,3,3) float32 and pbc (B,3) uint8 on the device, read at replay time.
+ * arrays: HOST array of 18 device pointers = the sixteen arrays of gn_index_gpu_padded_q in its order, then cell_offsets
+ * (e_cap,3) and int_cell_offsets (eint_cap,3), each of its family's capacity.  Real rows [0, n) of every family: the arrays of
+ * gn_pbc_index_* / gn_pbc_qindex_* above for float32 R, bit for bit (the GemNet-T keys are gn_pbc_index_padded_t's); the rows
+ * behind them: the pad rows of gemnet_pytorch_amd/padded.py, quadruplet layout (n_groups groups of 4 dummy atoms behind atom
+ * a_cap, pad edges in units of six, offsets 0).
+ * Launch order: cell (both cutoffs) -> pairs<count> -> scan -> pairs<fill> (staging) -> the same three with int_cutoff (ws) ->
+ * in-degrees of both lists -> scans -> in-edges ascending (triplets), in-edges by (source, offset) + positions, interaction
+ * edges by (a, b, n) (staging) -> triplet / intermediate-triplet counts -> scans -> quadruplets per reduce edge (one wavefront
+ * each) -> scan -> decide (one block: every count against its capacity, the padding rules, both in-degree bounds; writes
+ * state[]) -> triplets, intermediate triplets, quadruplets straight into `arrays` (only when state[3] == 0) -> commit (edges
+ * and interaction edges from staging + all pad rows, ditto).
+ * staging: 7 e_cap + 5 eint_cap int32; ws: gn_pbc_qindex_ws_bytes(A, e_cap, eint_cap) bytes (a host-side function of its three
+ * sizes: nothing is launched, `stream` is not used — every entry point outside the short list of queries ends in one);
+ * e_cap, t_cap even; B <= A <= a_cap.
+ *   state (device int32[8]): [0] |= err (sticky)  [1] E  [2] T  [3] err of this call  [4] largest in-degree of a real atom
+ *                            [5] Eint  [6] I  [7] Q   (counts clipped to int32; they are accumulated in int64)
+ *   err bits: 1, 2, 4, 8, 16, 32, 64 as for gn_pbc_index_padded_t (4 / 8 for units of six over groups of four; 32 judged for
+ *             max(cutoff, int_cutoff)); 256 Eint > eint_cap, 512 I > i_cap, 1024 Q > q_cap, 2048 pad rows of the three
+ *             quadruplet families without the pad rows they refer to (padded._check_quad_padding)
+ * Every count is compared with its capacity BEFORE a kernel indexes with it; after an error nothing the model reads is written
+ * (the arrays keep the previous step's valid contents) and gn_index_poison_f32 turns the step's outputs into NaN. */
+int64_t gn_pbc_qindex_ws_bytes(int A, int e_cap, int eint_cap, void* stream);
+int gn_pbc_qindex_padded(const float* R, const float* cell, const uint8_t* pbc, const int32_t* mol_off, const int32_t* atom_mol,
+                         int B, int A, double cutoff, double int_cutoff, void* ws, int e_cap, int t_cap, int eint_cap, int i_cap,
+                         int q_cap, int a_cap, int n_groups, int deg_bound, int32_t* staging, int32_t* const* arrays,
+                         int32_t* state, void* stream);
 
 /* ---- periodic cells, GemNet-Q geometry on vectors (csrc/pbc_quad.hip; additive, ABI 16) --------------------------------------
  * V (E,3): the edge vectors; Vint (n_int,3): the interaction-edge vectors, Vint[k] = R[id4_int_a[k]] - (R[id4_int_b[k]] +

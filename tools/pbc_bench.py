@@ -90,10 +90,12 @@ def make_model(cutoff=5.0, direct=False, coupled=False, quad=False, int_cutoff=1
     return model
 
 
-def quad_times(Rd, Zd, Nd, celld, A, args):
-    """GemNet-Q on the periodic box: index build, eager call and fixed-list replay, the four counts and the peak memory."""
+def quad_times(R, Rd, Zd, Nd, celld, A, args):
+    """GemNet-Q on the periodic box: index build, eager call and fixed-list replay, the four counts and the peak memory; then the
+    MD loop (positions walk, all arrays rebuilt every step): builder + eager call, and the one-replay step of
+    runtime.DynamicForceField (exact=False / True) with the index build inside the graph."""
     from gemnet_pytorch_amd.pbc import PeriodicQuadGraphBuilder
-    from gemnet_pytorch_amd.runtime import ForceGraphs
+    from gemnet_pytorch_amd.runtime import DynamicForceField, ForceGraphs
     torch.cuda.reset_peak_memory_stats()
     builder = PeriodicQuadGraphBuilder([A], args.cutoff, args.int_cutoff, device="cuda")
     idx = builder(Rd, celld, dtype=torch.int32)
@@ -108,6 +110,28 @@ def quad_times(Rd, Zd, Nd, celld, A, args):
     out["quad_graph_ms"] = timed(fg.replay, args.steps, args.warmup)
     out["quad_graph_ns_per_quadruplet"] = 1e6 * out["quad_graph_ms"] / max(out["quadruplets"], 1)
     out["peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    walk = random_walk(R, args.steps + args.warmup)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % len(walk)
+        return walk[state["i"]]
+
+    def md_eager():
+        Rs = nxt()
+        return model(dict(R=Rs, Z=Zd, N=Nd, cell=celld, **builder(Rs, celld, dtype=torch.int32)), stress=True)
+
+    out["md_eager_ms"] = timed(md_eager, args.steps, args.warmup)
+    model.periodic_quadruplets_dynamic = True
+    ff = DynamicForceField(model, Zd, [A], args.cutoff, args.int_cutoff, cell=celld)
+    ff(walk[0])
+    state["i"] = 0
+    out["md_graph_ms"] = timed(lambda: ff(nxt(), exact=False), args.steps, args.warmup)
+    torch.cuda.synchronize()
+    out["md_graph_exact_ms"] = timed(lambda: ff(nxt()), args.steps, args.warmup)
+    out["recaptures"] = int(ff.recaptures)
+    out["md_index_failed"] = bool(ff.index_failed())
+    out["md_sizes"] = list(ff.runner.index_sizes())
     return out
 
 
@@ -249,7 +273,7 @@ def main():
     Nd = torch.tensor([A], device="cuda")
     celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
     if args.quad:
-        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **quad_times(Rd, Zd, Nd, celld, A, args))))
+        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **quad_times(R, Rd, Zd, Nd, celld, A, args))))
         return
     model = make_model(args.cutoff).to("cuda").eval()
     idx = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
