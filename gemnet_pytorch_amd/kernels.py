@@ -1026,6 +1026,61 @@ def pbc_force_stress_adj(gF, gS, V, id_c, id_a, batch_seg, cell, scale=-1.0):
     return gG
 
 
+# --- ... and of the quadruplet branch on (V, Vint) (csrc/pbc_quad_train.hip): force training of GemNet-Q with a cell
+def angle_vec2_fwd(U, iu, W, iw):
+    """theta (T,) between u = U[iu] and v = -W[iw] (the a - b <- d angle: U = Vint, W = V)."""
+    require_device(U, iu, W, iw)
+    U, W = _f32c(U), _f32c(W)
+    assert iw.shape == iu.shape
+    th = torch.empty(iu.shape[0], device=U.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec2_fwd_f32(ptr(U), ptr(iu), ptr(W), ptr(iw), ptr(th), iu.shape[0], stream()),
+          "gn_angle_vec2_fwd_f32")
+    return th
+
+
+def angle_vec2_bwd(g, U, iu, W, iw):
+    """-> GU, GW (T,3) = g dtheta/dU[iu], g dtheta/dW[iw] per triplet."""
+    require_device(g, U, W)
+    g, U, W = _f32c(g), _f32c(U), _f32c(W)
+    T = iu.shape[0]
+    assert iw.shape == iu.shape and g.shape == (T,)
+    GU = torch.empty((T, 3), device=U.device, dtype=torch.float32)
+    GW = torch.empty((T, 3), device=U.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec2_bwd_f32(ptr(g), ptr(U), ptr(iu), ptr(W), ptr(iw), ptr(GU), ptr(GW), T, stream()),
+          "gn_angle_vec2_bwd_f32")
+    return GU, GW
+
+
+def angle_vec2_jvp(U, iu, W, iw, tU, tW):
+    """-> thdot (T,): the tangent of the angles along (tU, tW), shaped like (U, W); either may be None (zero)."""
+    require_device(U, W)
+    U, W = _f32c(U), _f32c(W)
+    tU = None if tU is None else _f32c(tU)
+    tW = None if tW is None else _f32c(tW)
+    assert iw.shape == iu.shape and (tU is None or tU.shape == U.shape) and (tW is None or tW.shape == W.shape)
+    thd = torch.empty(iu.shape[0], device=U.device, dtype=torch.float32)
+    check(_lib.load().gn_angle_vec2_jvp_f32(ptr(U), ptr(iu), ptr(W), ptr(iw), ptr(tU), ptr(tW), ptr(thd), iu.shape[0], stream()),
+          "gn_angle_vec2_jvp_f32")
+    return thd
+
+
+def quad_angles_vec_jvp(V, Vint, tV, tVint, q_ca, q_db, q_abd, intm_ab):
+    """tang (Q,4) = (dPhi_cab, dTheta_cabd, 0, 0) along (tV, tVint): the tangents of the two quadruplet angles of a periodic
+    batch — the double backward of gn_quad_angles_vec_bwd_f32, with its decisions at collinear and planar quadruplets
+    (gn_quad_angles_vec_jvp_f32).  tV / tVint: shaped like V / Vint, either may be None (zero)."""
+    require_device(V, Vint, q_ca, q_db, q_abd, intm_ab)
+    V, Vint = _f32c(V), _f32c(Vint)
+    tV = None if tV is None else _f32c(tV)
+    tVint = None if tVint is None else _f32c(tVint)
+    assert (tV is None or tV.shape == V.shape) and (tVint is None or tVint.shape == Vint.shape)
+    Q = q_ca.shape[0]
+    assert q_db.shape == q_abd.shape == (Q,)
+    tang = torch.empty((Q, 4), device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_quad_angles_vec_jvp_f32(ptr(V), ptr(Vint), ptr(tV), ptr(tVint), ptr(q_ca), ptr(q_db), ptr(q_abd),
+                                                 ptr(intm_ab), ptr(tang), Q, stream()), "gn_quad_angles_vec_jvp_f32")
+    return tang
+
+
 def direct_force(terms, V, id_swap, perm, seg_off, n_atoms, out=None):
     """-> F (n_atoms, T, 3): the force head of the direct-force model in one launch (gn_direct_force_f32).  terms (K,E,T): the
     force magnitudes of the K output blocks; V (E,3): edge vectors, not normalised; id_swap (E) int32 or None (uncoupled);

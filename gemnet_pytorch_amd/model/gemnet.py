@@ -17,6 +17,7 @@ second-order graph is built when it can be used — `self.training and torch.is_
 or when `self.force_graph` is set to True/False explicitly.
 """
 import contextlib
+import math
 import os
 
 import torch
@@ -210,6 +211,36 @@ class GemNet(torch.nn.Module):
         angle_cabd = GemNet.calculate_neighbor_angles(R_ac_proj, R_bd_proj)
         return angle_cab, angle_abd, angle_cabd
 
+    REL_SIN2 = 1e-10        # kRelSin^2 of csrc/quad_math.h
+
+    @staticmethod
+    def calculate_angles_vec(V, Vint, plan):
+        """`calculate_angles` of a periodic batch on the edge vectors V (E,3) and the interaction-edge vectors Vint (n_int,3), in
+        ATen and differentiable to any order: Phi_cab (Q,), Phi_abd (I,), Theta_cabd (Q,) from uac = -V[ca], uab = -Vint[k],
+        ubd = -V[db] per quadruplet and u = Vint[k], v = -V[db] per intermediate triplet (csrc/pbc_quad.hip).  The clamp
+        decisions of the two quadruplet angles are those of csrc/quad_math.h, relative to the vectors' lengths and taken on
+        detached values: c - a - b collinear => Phi_cab is a constant; a vanished rejection => Theta_cabd = pi / 2, a constant;
+        a planar quadruplet => Theta_cabd (0 or pi) is a constant."""
+        rel2 = GemNet.REL_SIN2
+        sq = lambda x: torch.sum(x * x, dim=-1)       # noqa: E731
+        angle_abd = GemNet.calculate_neighbor_angles(ops.gather_rows(Vint, plan.intm_ab), -ops.gather_rows(V, plan.intm_db))
+        uac = -ops.gather_rows(V, plan.quad.reduce)
+        uab = -ops.gather_rows(ops.gather_rows(Vint, plan.intm_ab), plan.quad.expand)
+        ubd = -ops.gather_rows(ops.gather_rows(V, plan.intm_db), plan.quad.expand)
+        with torch.no_grad():
+            p1, p2 = GemNet.vector_rejection(uac, uab), GemNet.vector_rejection(ubd, -uab)
+            parallel = lambda u, v: sq(torch.linalg.cross(u, v, dim=-1)) <= rel2 * sq(u) * sq(v)       # noqa: E731
+            flat = parallel(uab, uac)
+            vanished = (sq(p1) <= rel2 * sq(uac)) | (sq(p2) <= rel2 * sq(ubd))
+            fixed = (vanished | parallel(p1, p2))[:, None]
+            flat = flat[:, None]
+        angle_cab = GemNet.calculate_neighbor_angles(torch.where(flat, uab.detach(), uab), torch.where(flat, uac.detach(), uac))
+        # (a row whose azimuth sits on its clamp sees detached vectors: the rejections carry no gradient there)
+        tac, tab, tbd = (torch.where(fixed, x.detach(), x) for x in (uac, uab, ubd))
+        angle_cabd = GemNet.calculate_neighbor_angles(GemNet.vector_rejection(tac, tab), GemNet.vector_rejection(tbd, -tab))
+        angle_cabd = torch.where(vanished, torch.full_like(angle_cabd, math.pi / 2), angle_cabd)
+        return angle_cab, angle_abd, angle_cabd
+
     # ---------------------------------------------------------------------------------- forward
     def _energy(self, R, plan, V=None, force_terms=False, Vint=None):
         """V: the (E,3) edge vectors of a periodic batch (pbc.edge_vectors; the leaf the force and stress are taken from).
@@ -360,18 +391,36 @@ class GemNet(torch.nn.Module):
                 # twins rebuild Y_lm and its tangent in-kernel, ops_train._BilinearAng2) — no (Q, 49) array in any of the four
                 # sweeps, no ATen launch over (Q, 3) temporaries
                 from .. import ops_train
-                qg = plan.quad_geom
-                D_ab = ops_train.distances(R, plan.int_b, plan.int_a)
-                Phi_abd = ops_train.triplet_angles(R, qg["a_of_exp"], qg["b_of_exp"], qg["d_of_exp"])
-                cbf4 = self.cbf_basis(D_ab, Phi_abd, plan.intm_ab)
-                sbf4 = (rad3, ops_train.quad_angles(R, plan.q_c, plan.q_a, plan.q_b, plan.q_d, plan))
-            else:
-                if ops.train2_enabled() and not self.direct_forces:
-                    from .. import ops_train
-                    D_ab = ops_train.distances(R, plan.int_b, plan.int_a)
+                if V is not None:
+                    # periodic batch: the same three on the two vector arrays (csrc/pbc_quad_train.hip, ops_train._AngleVec2Q /
+                    # _QuadAnglesVec2), the clamp decisions of the quadruplet angles relative to the vectors' lengths
+                    D_ab = ops_train.distances_vec(Vint)
+                    Phi_abd = ops_train.triplet_angles_vec2(Vint, V, plan)
+                    ang = ops_train.quad_angles_vec(V, Vint, plan)
                 else:
-                    D_ab, _ = self.calculate_interatomic_vectors(R, plan.int_b, plan.int_a)
-                Phi_cab, Phi_abd, Theta_cabd = self.calculate_angles(R, plan)
+                    qg = plan.quad_geom
+                    D_ab = ops_train.distances(R, plan.int_b, plan.int_a)
+                    Phi_abd = ops_train.triplet_angles(R, qg["a_of_exp"], qg["b_of_exp"], qg["d_of_exp"])
+                    ang = ops_train.quad_angles(R, plan.q_c, plan.q_a, plan.q_b, plan.q_d, plan)
+                cbf4 = self.cbf_basis(D_ab, Phi_abd, plan.intm_ab)
+                sbf4 = (rad3, ang)
+            else:
+                if V is not None:
+                    # periodic batch on the composite closure (other widths, force_graph=True, GEMNET_TRAIN2=0, the quadruplet
+                    # twins switched off, matmul_precision="f32"): ATen on (V, Vint), the A/B reference of the fused form
+                    if ops.train2_enabled():
+                        from .. import ops_train
+                        D_ab = ops_train.distances_vec(Vint)
+                    else:
+                        D_ab = torch.sqrt(torch.sum(Vint ** 2, dim=1))
+                    Phi_cab, Phi_abd, Theta_cabd = self.calculate_angles_vec(V, Vint, plan)
+                else:
+                    if ops.train2_enabled() and not self.direct_forces:
+                        from .. import ops_train
+                        D_ab = ops_train.distances(R, plan.int_b, plan.int_a)
+                    else:
+                        D_ab, _ = self.calculate_interatomic_vectors(R, plan.int_b, plan.int_a)
+                    Phi_cab, Phi_abd, Theta_cabd = self.calculate_angles(R, plan)
                 cbf4 = self.cbf_basis(D_ab, Phi_abd, plan.intm_ab)           # (I, S*R)
                 # the tensor basis shares cutoff and radial tables with cbf_basis3: reuse rad3
                 sbf4 = (rad3, ops.ylm(Phi_cab, Theta_cabd, self.num_spherical))  # ((E,S,R), (Q,S^2))
@@ -534,6 +583,8 @@ class GemNet(torch.nn.Module):
         graph to the parameters (`_forward_periodic_direct_train`).
         With `periodic_training = True` a call that builds the second-order force graph (training mode with grad enabled, or
         `force_graph = True`) returns the same outputs with an autograd graph to the parameters; without it that call raises.
+        A GemNet-Q (`triplets_only=False`) needs `periodic_quadruplets = True` for a cell at all and, for that second-order graph,
+        `periodic_quadruplets_training = True` as well (training.periodic.PeriodicTrainStep sets all three); else it raises.
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
         value beyond 65 504 becomes inf — fitted scale factors keep activations O(1), a model with
         unfitted ones (the starting state of fit_scaling.py, foreign checkpoints) need not.  A non-finite result of an eager
@@ -720,9 +771,14 @@ class GemNet(torch.nn.Module):
             graph = self.force_graph
             if graph is None:
                 graph = self.training and torch.is_grad_enabled()
-            if graph:
+            # (training — the second-order force graph on (V, Vint) — is a third opt-in, `periodic_quadruplets_training`, on top
+            #  of `periodic_training`; training.periodic.PeriodicTrainStep sets all three)
+            if graph and not getattr(self, "periodic_quadruplets_training", False):
                 raise NotImplementedError("periodic cells: GemNet-Q runs on the first-order (eval) path only; training with a "
                                           "cell is GemNet-T only")
+            if graph and inputs.get("_guard_rows") is not None:
+                raise NotImplementedError("periodic cells (GemNet-Q): training runs on fixed index arrays only, not on the "
+                                          "padded or in-graph-rebuilt lists of padded.PaddedGraphRunner")
             if "int_cell_offsets" not in inputs:
                 raise ValueError("a periodic GemNet-Q batch needs 'int_cell_offsets' and the quadruplet arrays of "
                                  "pbc.PeriodicQuadGraphBuilder")
@@ -818,13 +874,25 @@ class GemNet(torch.nn.Module):
         and cell never join an autograd graph — so `loss.backward()` reaches the parameters through G alone."""
         from .. import pbc
         V = pbc.edge_vectors(R, plan, cell).requires_grad_(True)
+        # GemNet-Q (`periodic_quadruplets_training`): the second private leaf Vint, ONE gradient call for both, and F, S linear in
+        # (G, Gint) through pbc.force_stress_q (the adjoint kernel once per edge family)
+        Vint = None if self.triplets_only else pbc.int_edge_vectors(R, plan, cell).requires_grad_(True)
         with ops.weight_cache(self._wcache), ops.fused_first_order(False), ops.param_grads(True), \
                 ops.train2(t2, self._packs if (t2 and R.is_cuda) else None), ops.chain_mode(self.matmul_precision), \
                 ops.position_graph(False), torch.enable_grad():
-            E_mol, _, _ = self._energy(R.detach(), plan, V=V)
-            with ops.param_grads(False):  # only dE/dV is needed here
-                G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0), create_graph=True)[0]
-            F, S = pbc.force_stress(G, V.detach(), plan, cell)
+            E_mol, _, _ = self._energy(R.detach(), plan, V=V, Vint=Vint)
+            with ops.param_grads(False):  # only dE/dV (and dE/dVint) is needed here
+                if Vint is None:
+                    G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0), create_graph=True)[0]
+                else:
+                    G, Gint = torch.autograd.grad(E_mol, (V, Vint), grad_outputs=self._cotangent(E_mol, 0), create_graph=True,
+                                                  allow_unused=True)
+            if Vint is None:
+                F, S = pbc.force_stress(G, V.detach(), plan, cell)
+            else:
+                G = torch.zeros_like(V) if G is None else G
+                Gint = torch.zeros_like(Vint) if Gint is None else Gint
+                F, S = pbc.force_stress_q(G, V.detach(), Gint, Vint.detach(), plan, cell)
         return E_mol, F, S
 
     def _cotangent(self, E_mol, target):

@@ -1272,3 +1272,102 @@ class _AngleVec2B(torch.autograd.Function):
 
 def triplet_angles_vec(V, trip):
     return _AngleVec2.apply(V, trip)
+
+
+# ============================================ the quadruplet branch of a periodic batch on (V, Vint): csrc/pbc_quad_train.hip
+def _rows2(GU, GW, plan):
+    """Per-triplet terms of the a - b <- d angle -> (rows of Vint, rows of V), as pbc._TripBasisVec2.backward sums them."""
+    return K.segsum(GU, *plan.intm_ab.csr, plan.n_int), K.segsum(GW, *plan.intm_db.csr, plan.n_edges)
+
+
+class _AngleVec2Q(torch.autograd.Function):
+    """theta[t] = atan2(max(|u x v|, 1e-9), u . v), u = Vint[intm_ab[t]], v = -V[intm_db[t]]: the a - b <- d angle of every
+    intermediate triplet (pbc.trip_basis2's convention), twice differentiable: _AngleVec2 on two vector arrays."""
+
+    @staticmethod
+    def forward(ctx, Vint, V, plan):
+        ctx.save_for_backward(Vint, V)
+        ctx.plan = plan
+        return K.angle_vec2_fwd(Vint, plan.intm_ab.idx32, V, plan.intm_db.idx32)
+
+    @staticmethod
+    def backward(ctx, g):
+        Vint, V = ctx.saved_tensors
+        plan = ctx.plan
+        if g is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        if torch.is_grad_enabled():
+            return _AngleVec2QB.apply(g, Vint, V, plan) + (None,)
+        return _rows2(*K.angle_vec2_bwd(g.contiguous(), Vint, plan.intm_ab.idx32, V, plan.intm_db.idx32), plan) + (None,)
+
+
+class _AngleVec2QB(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, Vint, V, plan):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(Vint, V)
+        ctx.plan = plan
+        return _rows2(*K.angle_vec2_bwd(g.contiguous(), Vint, plan.intm_ab.idx32, V, plan.intm_db.idx32), plan)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tVint, tV):
+        Vint, V = ctx.saved_tensors
+        plan = ctx.plan
+        if (tVint is None and tV is None) or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        c = lambda t: None if t is None else t.contiguous()       # noqa: E731
+        return K.angle_vec2_jvp(Vint, plan.intm_ab.idx32, V, plan.intm_db.idx32, c(tVint), c(tV)), None, None, None
+
+
+def triplet_angles_vec2(Vint, V, plan):
+    return _AngleVec2Q.apply(Vint, V, plan)
+
+
+class _QuadAnglesVec2(torch.autograd.Function):
+    """ang (Q,4) = (sin, cos) of Phi_cab and Theta_cabd from uac = -V[ca], uab = -Vint[k], ubd = -V[db] of every quadruplet of a
+    periodic batch, twice differentiable: _QuadAngles2 on (V, Vint) — value and first adjoint are the kernels of the eval path
+    (csrc/pbc_quad.hip, pbc.quad_reduce), the tangent is csrc/pbc_quad_train.hip.  Gradient convention of the angle form: the
+    slot of `ang` carries g_ang (Q,4) = (dE/dPhi, dE/dTheta, 0, 0).  Clamp decisions relative to the vectors' lengths
+    (quad_math.h), the same in all three kernels."""
+
+    @staticmethod
+    def forward(ctx, V, Vint, plan):
+        from . import pbc
+        ctx.save_for_backward(V, Vint)
+        ctx.plan = plan
+        return pbc.quad_angles_vec_fwd(V, Vint, plan)
+
+    @staticmethod
+    def backward(ctx, g_ang):
+        from . import pbc
+        V, Vint = ctx.saved_tensors
+        if g_ang is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        if torch.is_grad_enabled():
+            return _QuadAnglesVec2B.apply(g_ang, V, Vint, ctx.plan) + (None,)
+        return pbc.quad_angles_vec_adjoint(g_ang, V, Vint, ctx.plan) + (None,)
+
+
+class _QuadAnglesVec2B(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g_ang, V, Vint, plan):
+        from . import pbc
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(V, Vint)
+        ctx.plan = plan
+        return pbc.quad_angles_vec_adjoint(g_ang, V, Vint, plan)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tV, tVint):
+        from . import pbc
+        V, Vint = ctx.saved_tensors
+        if (tV is None and tVint is None) or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        c = lambda t: None if t is None else t.contiguous()       # noqa: E731
+        return K.quad_angles_vec_jvp(V, Vint, c(tV), c(tVint), *pbc.quad_index(ctx.plan)), None, None, None
+
+
+def quad_angles_vec(V, Vint, plan):
+    return _QuadAnglesVec2.apply(V, Vint, plan)

@@ -19,6 +19,10 @@ The builder reads two sizes back per call.  For MD — a new list every step —
 captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
 runtime.DynamicForceField(cell=...), md.predict_periodic.  The same holds for PeriodicQuadGraphBuilder (four read-backs per call)
 and a GemNet-Q that opts in with `model.periodic_quadruplets_dynamic`: csrc/pbc_index_qp.hip, kernels.pbc_index_padded_q.
+
+Training GemNet-Q with a cell (`model.periodic_quadruplets_training`, set by training.periodic.PeriodicTrainStep) differentiates
+the energy through ops_train._DistVec2 / _AngleVec2 / _AngleVec2Q / _QuadAnglesVec2 on the two leaves V and Vint
+(csrc/pbc_quad_train.hip) and takes forces and stress from `force_stress_q` below.
 """
 import numpy as np
 import torch
@@ -400,11 +404,45 @@ class _QuadBasisVec(torch.autograd.Function):
         else:
             check(lib.gn_quad_basis_vec_bwd_f32(ptr(gY), ptr(V), ptr(Vint), *idx, ptr(Gc), ptr(Gbd), Q, S, stream()),
                   "gn_quad_basis_vec_bwd_f32")
-        Ec = K.segsum(Gc, None, q.seg_off, plan.n_edges)
-        Ibd = K.segsum(Gbd, *q.expand.csr, q.n_expand)
-        gV = Ec + K.segsum(Ibd[:, 4:7].contiguous(), *plan.intm_db.csr, plan.n_edges)
-        gVint = K.segsum(Ibd[:, 0:3].contiguous(), *plan.intm_ab.csr, plan.n_int)
-        return gV, gVint, None, None, None
+        return quad_reduce(Gc, Gbd, plan) + (None, None, None)
+
+
+def quad_reduce(Gc, Gbd, plan):
+    """The per-quadruplet adjoint rows Gc (Q,3) = dE/dV[ca], Gbd (Q,8) = [dE/dVint[k] | dE/dV[db]] -> (gV (E,3), gVint (n_int,3)):
+    the three-level reduction of `_QuadBasisVec` (shared with the training twin, ops_train._QuadAnglesVec2)."""
+    q = plan.quad
+    Ec = K.segsum(Gc, None, q.seg_off, plan.n_edges)
+    Ibd = K.segsum(Gbd, *q.expand.csr, q.n_expand)
+    gV = Ec + K.segsum(Ibd[:, 4:7].contiguous(), *plan.intm_db.csr, plan.n_edges)
+    gVint = K.segsum(Ibd[:, 0:3].contiguous(), *plan.intm_ab.csr, plan.n_int)
+    return gV, gVint
+
+
+def quad_index(plan):
+    """The four int32 index arrays of the quadruplet kernels on vectors: q_ca, q_db, q_abd, intm_ab."""
+    q = plan.quad
+    return q.reduce.idx32, quad_expand_db(plan), q.expand.idx32, plan.intm_ab.idx32
+
+
+def quad_angles_vec_fwd(V, Vint, plan):
+    """ang (Q,4) = (sin, cos) of Phi_cab and Theta_cabd from (V, Vint) (gn_quad_angles_vec_fwd_f32), no autograd history."""
+    Q = plan.quad.size
+    ang = torch.empty((Q, 4), device=V.device, dtype=torch.float32)
+    check(_lib.load().gn_quad_angles_vec_fwd_f32(ptr(V), ptr(Vint), *(ptr(i) for i in quad_index(plan)), ptr(ang), Q, stream()),
+          "gn_quad_angles_vec_fwd_f32")
+    return ang
+
+
+def quad_angles_vec_adjoint(g_ang, V, Vint, plan):
+    """First adjoint of the angle form on vectors: g_ang (Q,4) = (dE/dPhi, dE/dTheta, -, -) -> (gV, gVint)
+    (gn_quad_angles_vec_bwd_f32 + `quad_reduce`)."""
+    Q = plan.quad.size
+    g_ang = g_ang.float().contiguous()
+    Gc = torch.empty((Q, 3), device=V.device, dtype=torch.float32)
+    Gbd = torch.empty((Q, 8), device=V.device, dtype=torch.float32)       # (the kernel writes the two pad lanes itself)
+    check(_lib.load().gn_quad_angles_vec_bwd_f32(ptr(g_ang), ptr(V), ptr(Vint), *(ptr(i) for i in quad_index(plan)), ptr(Gc),
+                                                 ptr(Gbd), Q, stream()), "gn_quad_angles_vec_bwd_f32")
+    return quad_reduce(Gc, Gbd, plan)
 
 
 def quad_expand_db(plan):
@@ -528,3 +566,37 @@ class _ForceStress(torch.autograd.Function):
 def force_stress(G, V, plan, cell):
     """(F, S) from G = -dE/dV with an autograd graph through G (force training on periodic batches)."""
     return _ForceStress.apply(G, V, plan, cell)
+
+
+class _ForceStressQ(torch.autograd.Function):
+    """G = -dE/dV (E,3), Gint = -dE/dVint (n_int,3) -> F (A,3), S (B,3,3): `forces_q` + `stress_q`, differentiable in G and Gint
+    (`_ForceStress` for a periodic GemNet-Q batch).  Backward: the adjoint kernel once per edge family — over the edges, and
+    over the interaction edges with int_b, int_a in the roles of id_c, id_a (both arrays are of edge size)."""
+
+    @staticmethod
+    def forward(ctx, G, V, Gint, Vint, plan, cell):
+        ctx.set_materialize_grads(False)
+        G, Gint = G.contiguous(), Gint.contiguous()
+        ctx.save_for_backward(V, Vint, cell)
+        ctx.plan = plan
+        return forces_q(G, Gint, plan), stress_q(V, G, Vint, Gint, plan, cell)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gS):
+        V, Vint, cell = ctx.saved_tensors
+        plan = ctx.plan
+        if gF is None and gS is None:
+            return (None,) * 6
+        if gF is None:
+            gF = torch.zeros((plan.n_atoms, 3), device=V.device, dtype=V.dtype)
+        bs, cell = plan.batch_seg.idx32, cell.detach()
+        gG = K.pbc_force_stress_adj(gF, gS, V, plan.id_c.idx32, plan.id_a.idx32, bs, cell, -1.0)
+        gGint = K.pbc_force_stress_adj(gF, gS, Vint, plan.int_b.idx32, plan.int_a.idx32, bs, cell, -1.0)
+        return gG, None, gGint, None, None, None
+
+
+def force_stress_q(G, V, Gint, Vint, plan, cell):
+    """(F, S) of a periodic GemNet-Q batch from G = -dE/dV and Gint = -dE/dVint with an autograd graph through both (force
+    training; the stress cotangent may be None)."""
+    return _ForceStressQ.apply(G, V, Gint, Vint, plan, cell)

@@ -21,6 +21,12 @@ backward.  Such a model has no stress: `rho_stress > 0` raises at construction.
 
     ts = PeriodicTrainStep(direct_model, rho_force=0.999, fused_optimizer=True)
     loss = ts(inputs, dict(E=Et, F=Ft))
+
+GemNet-Q (`triplets_only=False`, forces by autograd) trains on the batches of `PeriodicQuadGraphBuilder`: constructing the step
+opts the model in (`periodic_quadruplets`, `periodic_training` and `periodic_quadruplets_training`).  The second-order force graph
+then runs on the edge vectors V and the interaction-edge vectors Vint (ops_train._AngleVec2Q / _QuadAnglesVec2,
+csrc/pbc_quad_train.hip; pbc.force_stress_q); `rho_stress > 0` and `capture()` work as for GemNet-T.  A direct-force GemNet-Q, several
+targets, scale-factor fitting and the padded / in-graph runners in training mode still raise.
 """
 import torch
 
@@ -39,6 +45,9 @@ class PeriodicTrainStep(TrainStep):
         if getattr(model, "direct_forces", False):
             model.periodic_direct_forces = True
         model.periodic_training = True
+        if not getattr(model, "triplets_only", True) and not getattr(model, "direct_forces", False):
+            model.periodic_quadruplets = True
+            model.periodic_quadruplets_training = True
         self._S = None
 
     def _outputs(self, inputs):

@@ -963,6 +963,33 @@ int gn_quad_angles_vec_fwd_f32(const float* V, const float* Vint, const int32_t*
 int gn_quad_angles_vec_bwd_f32(const float* g_ang, const float* V, const float* Vint, const int32_t* q_ca, const int32_t* q_db,
                                const int32_t* q_abd, const int32_t* intm_ab, float* Gc, float* Gbd, int64_t Q, void* stream);
 
+/* ---- force training of GemNet-Q on periodic batches (csrc/pbc_quad_train.hip; additive, ABI 16) -----------------------------
+ * The twice-differentiable geometry of the quadruplet branch on the vectors (V, Vint), for `loss.backward()` through
+ * G = -dE/dV and Gint = -dE/dVint (create_graph=True).  Neither array joins a caller's graph: no second-order terms w.r.t. them.
+ *   theta[t]  = atan2(max(|u x v|, 1e-9), u . v), u = U[iu[t]], v = -W[iw[t]]                 gn_angle_vec2_fwd_f32
+ *               (the a - b <- d angle in the convention of gn_trip_basis_vec2_fwd_f32: U = Vint, W = V)
+ *   GU, GW    = g dtheta/dU[iu[t]], g dtheta/dW[iw[t]] (T,3) per triplet; the caller sums them onto the rows of U and W
+ *               (fixed order, gn_segsum_f32)                                                    gn_angle_vec2_bwd_f32
+ *   thdot[t]  = dtheta/du . tU[iu[t]] - dtheta/dv . tW[iw[t]]; tU / tW may be NULL (= zero)     gn_angle_vec2_jvp_f32
+ *   tang[q]   = (dPhi_cab, dTheta_cabd, 0, 0) along (tV, tVint) (Q,4), tang 16-byte aligned: the tangent of the two angles of
+ *               gn_quad_angles_vec_fwd_f32 with its operands; tV / tVint may be NULL (= zero).  Formed from the body of
+ *               gn_quad_angles_vec_bwd_f32 with unit cotangents, so it takes that kernel's decisions relative to the vectors'
+ *               lengths: c - a - b collinear => dPhi = 0 exactly; a vanished rejection or a planar quadruplet => dTheta = 0
+ *               exactly                                                                         gn_quad_angles_vec_jvp_f32
+ * The same arithmetic as gn_angle_vec_* (the angle adjoint of csrc/geom_dual.h).  The distances of the interaction edges are
+ * gn_dist_vec_* on Vint; the adjoint of (G, Gint) -> (F, S) is gn_pbc_force_stress_adj_f32 once over the edges and once over
+ * the interaction edges (id4_int_b, id4_int_a in the roles of id_c, id_a).  One thread per triplet / quadruplet, no atomics;
+ * T = 0 / Q = 0 return 0 without a launch. */
+int gn_angle_vec2_fwd_f32(const float* U, const int32_t* iu, const float* W, const int32_t* iw, float* theta, int64_t T,
+                          void* stream);
+int gn_angle_vec2_bwd_f32(const float* g, const float* U, const int32_t* iu, const float* W, const int32_t* iw, float* GU,
+                          float* GW, int64_t T, void* stream);
+int gn_angle_vec2_jvp_f32(const float* U, const int32_t* iu, const float* W, const int32_t* iw, const float* tU, const float* tW,
+                          float* thdot, int64_t T, void* stream);
+int gn_quad_angles_vec_jvp_f32(const float* V, const float* Vint, const float* tV, const float* tVint, const int32_t* q_ca,
+                               const int32_t* q_db, const int32_t* q_abd, const int32_t* intm_ab, float* tang, int64_t Q,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

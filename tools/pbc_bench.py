@@ -24,6 +24,11 @@ pbc.PeriodicQuadGraphBuilder) on the box: `quad_eager_ms` (E, F, S), `quad_graph
 build with its read-backs), the edge / interaction-edge / intermediate-triplet / quadruplet counts and the peak device memory.
 The quadruplet count grows like cutoff^6 int_cutoff^3: at the reference's int_cutoff = 10 a 192-atom box has ~1e8; the default
 X = 5.0 keeps it below 3e7.
+`--train --quad` times the TRAINING step of GemNet-Q on the box (PeriodicTrainStep on a `triplets_only=False` model: the second-order
+force graph on the edge and interaction-edge vectors, energy + force + stress loss, fused optimizer), eager and captured
+(`quad_train_eager_ms` / `quad_train_graph_ms`), beside the molecular `TrainStep` of the same model on the same atoms without a
+cell (`quad_train_molecular_*_ms`), alternating in one process (`*_rounds`), + the counts of both graphs and the peak memory;
+with `--eager-only` nothing but eager periodic steps (for a kernel trace).
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -164,6 +169,53 @@ def train_times(per, mol, args):
     return out
 
 
+def quad_train_times(Rd, Zd, Nd, celld, A, args):
+    """Eager and captured training step of GemNet-Q on the periodic box beside the molecular TrainStep of the same model on the
+    same atoms without a cell, alternating in one process; optimizer included."""
+    from gemnet_pytorch_amd.index_device import build_indices_device
+    from gemnet_pytorch_amd.pbc import PeriodicQuadGraphBuilder
+    from gemnet_pytorch_amd.training.ddp import TrainStep
+    from gemnet_pytorch_amd.training.periodic import PeriodicTrainStep
+    torch.cuda.reset_peak_memory_stats()
+    idx = PeriodicQuadGraphBuilder([A], args.cutoff, args.int_cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
+    mix = build_indices_device(Rd, np.array([A]), args.cutoff, args.int_cutoff, False, dtype=torch.int32)
+    out = {"int_cutoff": args.int_cutoff}
+    for tag, d in (("periodic", idx), ("molecular", mix)):
+        out.update({f"edges_{tag}": int(d["id_a"].shape[0]), f"interaction_edges_{tag}": int(d["id4_int_a"].shape[0]),
+                    f"quadruplets_{tag}": int(d["id4_reduce_ca"].shape[0])})
+    print(json.dumps(out), flush=True)
+    g = torch.Generator().manual_seed(2)
+    targets = {"E": torch.randn(1, 1, generator=g).cuda(), "F": torch.randn(A, 3, generator=g).cuda(),
+               "S": 0.01 * torch.randn(1, 3, 3, generator=g).cuda()}
+    new = lambda: make_model(args.cutoff, quad=True, int_cutoff=args.int_cutoff).to("cuda")      # noqa: E731
+    steps = {"quad_train": PeriodicTrainStep(new(), rho_stress=0.01, fused_optimizer=True)}
+    inputs = {"quad_train": dict(R=Rd, Z=Zd, N=Nd, cell=celld, **idx)}
+    if args.eager_only:
+        for _ in range(args.warmup + args.steps):
+            steps["quad_train"](inputs["quad_train"], targets)
+        torch.cuda.synchronize()
+        out["eager_steps"] = args.warmup + args.steps
+        return out
+    steps["quad_train_molecular"] = TrainStep(new(), fused_optimizer=True)
+    inputs["quad_train_molecular"] = dict(R=Rd, Z=Zd, N=Nd, **mix)
+
+    def record(tag, res):
+        for k, (med, rounds) in res.items():
+            out[f"{k}_{tag}_ms"], out[f"{k}_{tag}_rounds"] = med, rounds
+
+    fns = {k: (lambda ts=ts, k=k: ts(inputs[k], targets)) for k, ts in steps.items()}
+    record("eager", alternated(fns, args.steps, args.warmup))
+    out["peak_memory_eager_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    for k, ts in steps.items():
+        ts.capture(inputs[k], targets)
+    record("graph", alternated(fns, args.steps, args.warmup))
+    for k, ts in steps.items():
+        out[f"{k}_loss"] = float(ts.last_loss)
+        out[f"{k}_precision"] = str(ts.model.matmul_precision)
+    out["peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    return out
+
+
 def train_direct_times(per, args):
     """Eager and captured training step of the direct-force model beside the autograd-force model's (energy + force + stress
     loss, as `--train`), alternating in one process; optimizer included."""
@@ -258,7 +310,7 @@ def main():
     ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
     ap.add_argument("--quad", action="store_true", help="time GemNet-Q (periodic_quadruplets) on the box")
     ap.add_argument("--int-cutoff", type=float, default=5.0, help="--quad: the interaction cutoff (quadruplets ~ int_cutoff^3)")
-    ap.add_argument("--eager-only", action="store_true", help="--direct: only eager direct-force calls / training steps (for a kernel trace)")
+    ap.add_argument("--eager-only", action="store_true", help="--direct / --train --quad: only eager direct-force calls / training steps (for a kernel trace)")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -273,7 +325,8 @@ def main():
     Nd = torch.tensor([A], device="cuda")
     celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
     if args.quad:
-        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **quad_times(R, Rd, Zd, Nd, celld, A, args))))
+        res = quad_train_times(Rd, Zd, Nd, celld, A, args) if args.train else quad_times(R, Rd, Zd, Nd, celld, A, args)
+        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **res)))
         return
     model = make_model(args.cutoff).to("cuda").eval()
     idx = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
