@@ -143,6 +143,70 @@ extern "C" int gn_force_loss_f32(const float* E, const float* Et, int64_t nE, co
   return 0;
 }
 
+// ---- the periodic training loss (energy + force + stress) and its cotangents in one launch ----------------------------------
+// force_loss_kernel with the stress term of training/periodic.py: + w_s sum_{b < B} |S_b - St_b|_F, gS_b = w_s (S_b - St_b) /
+// |S_b - St_b|_F (0 where the norm is 0, as ATen).  Same loops in the same order, the stress term added LAST: with S == NULL a
+// thread's partial sum, the tree and hence loss, gE, gF are those of force_loss_kernel bit for bit.
+__global__ __launch_bounds__(1024) void periodic_loss_kernel(const float* __restrict__ E, const float* __restrict__ Et, int64_t nE,
+                                                             const float* __restrict__ F, const float* __restrict__ Ft, int64_t A,
+                                                             const float* __restrict__ mask, const float* __restrict__ S,
+                                                             const float* __restrict__ St, int64_t B, float w_e, float w_f,
+                                                             const float* __restrict__ w_f_dev, float w_s,
+                                                             float* __restrict__ loss, float* __restrict__ gE,
+                                                             float* __restrict__ gF, float* __restrict__ gS) {
+  __shared__ double red[1024];
+  const int tid = threadIdx.x;
+  if (w_f_dev) w_f *= *w_f_dev;
+  double acc = 0.0;
+  for (int64_t i = tid; i < nE; i += 1024) {
+    const float d = E[i] - Et[i];
+    acc += (double)w_e * fabsf(d);
+    gE[i] = d > 0.f ? w_e : (d < 0.f ? -w_e : 0.f);
+  }
+  for (int64_t a = tid; a < A; a += 1024) {
+    const float m = mask ? mask[a] : 1.f;
+    const float dx = F[3 * a] - Ft[3 * a], dy = F[3 * a + 1] - Ft[3 * a + 1], dz = F[3 * a + 2] - Ft[3 * a + 2];
+    const float n = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float s = (m != 0.f && n > 0.f) ? w_f * m / n : 0.f;
+    if (m != 0.f) acc += (double)w_f * m * n;
+    gF[3 * a] = s * dx; gF[3 * a + 1] = s * dy; gF[3 * a + 2] = s * dz;
+  }
+  if (S) {
+    for (int64_t b = tid; b < B; b += 1024) {
+      float d[9];
+      float q = 0.f;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        d[k] = S[9 * b + k] - St[9 * b + k];
+        q += d[k] * d[k];
+      }
+      const float n = sqrtf(q);
+      const float s = n > 0.f ? w_s / n : 0.f;
+      acc += (double)w_s * n;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) gS[9 * b + k] = s * d[k];
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) *loss = (float)red[0];
+}
+
+extern "C" int gn_periodic_loss_f32(const float* E, const float* Et, int64_t nE, const float* F, const float* Ft, int64_t A,
+                                    const float* mask, const float* S, const float* St, int64_t B, float w_e, float w_f,
+                                    const float* w_f_dev, float w_s, float* loss, float* gE, float* gF, float* gS, void* stream) {
+  if (nE < 0 || A < 0 || B < 0) return (int)hipErrorInvalidValue;
+  if (S && (!St || !gS)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(periodic_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), E, Et, nE, F, Ft, A, mask, S,
+                     St, B, w_e, w_f, w_f_dev, w_s, loss, gE, gF, gS);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int gn_optim_blocks(int64_t n) {
   int64_t b = (n + OPT_NT * 8 - 1) / (OPT_NT * 8);
   return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));

@@ -409,6 +409,29 @@ def force_loss(E, Et, F, Ft, w_e, w_f, mask=None, w_f_dev=None):
     return loss, gE, gF
 
 
+def periodic_loss(E, Et, F, Ft, w_e, w_f, S=None, St=None, w_s=0.0, mask=None, w_f_dev=None):
+    """-> (loss (), gE like E, gF like F, gS like S or None): force_loss plus w_s sum_b |S_b - St_b|_F over the (B,3,3) stresses
+    and its cotangent, in one launch (gn_periodic_loss_f32).  S = None: no stress term — loss, gE, gF are force_loss's bit for bit."""
+    require_device(E, Et, F, Ft)
+    E, Et, F, Ft = _f32c(E), _f32c(Et), _f32c(F), _f32c(Ft)
+    assert E.shape == Et.shape and F.shape == Ft.shape and F.dim() == 2 and F.shape[1] == 3
+    if mask is not None:
+        mask = _f32c(mask)
+        assert mask.numel() == F.shape[0]
+    gS, B = None, 0
+    if S is not None:
+        require_device(S, St)
+        S, St = _f32c(S), _f32c(St)
+        assert S.shape == St.shape and S.dim() == 3 and tuple(S.shape[1:]) == (3, 3)
+        gS, B = torch.empty_like(S), int(S.shape[0])
+    loss = torch.empty((), device=E.device, dtype=torch.float32)
+    gE, gF = torch.empty_like(E), torch.empty_like(F)
+    check(_lib.load().gn_periodic_loss_f32(ptr(E), ptr(Et), E.numel(), ptr(F), ptr(Ft), F.shape[0], ptr(mask), ptr(S), ptr(St), B,
+                                           float(w_e), float(w_f), ptr(w_f_dev), float(w_s), ptr(loss), ptr(gE), ptr(gF), ptr(gS),
+                                           stream()), "gn_periodic_loss_f32")
+    return loss, gE, gF, gS
+
+
 def index_poison(x, state):
     """x <- NaN when the index build of this step reported an error (gn_index_poison_f32)."""
     require_device(x, state)

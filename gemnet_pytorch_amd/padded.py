@@ -37,7 +37,8 @@ is padded with zeros as well and `attach_builder(pbc.PeriodicQuadGraphBuilder)` 
 (gn_pbc_qindex_padded).
 
 Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
-`Trainer.enable_padded_graph` (the training step in the same form), `bench.py` (`extra.dynamic_shape`,
+`Trainer.enable_padded_graph` (the training step in the same form), `training.periodic.PeriodicPaddedTrainStep` (the training
+step on periodic batches: a periodic runner's buffers, `_fill`, `attach_builder` and `_index_in_graph`), `bench.py` (`extra.dynamic_shape`,
 `extra.train_step_dynamic`).
 """
 import torch

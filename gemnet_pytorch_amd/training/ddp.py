@@ -106,8 +106,35 @@ class _ForceLoss(torch.autograd.Function):
         return gE * g, gF * g, None, None, None, None, None, None
 
 
+class _PeriodicLoss(torch.autograd.Function):
+    """_ForceLoss + w_s sum_b |S_b - St_b|_F over the (B,3,3) stresses (kernels.periodic_loss: one launch); S = None: no stress
+    term.  First-order backward only, as _ForceLoss."""
+
+    @staticmethod
+    def forward(ctx, E, F, S, Et, Ft, St, w_e, w_f, w_s, mask, w_f_dev):
+        from .. import kernels as K
+        loss, gE, gF, gS = K.periodic_loss(E, Et, F, Ft, w_e, w_f, S=S, St=St, w_s=w_s, mask=mask, w_f_dev=w_f_dev)
+        ctx.with_S = gS is not None
+        ctx.save_for_backward(gE, gF, *((gS,) if gS is not None else ()))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gE, gF = ctx.saved_tensors[:2]
+        gS = ctx.saved_tensors[2] * g if ctx.with_S else None
+        return gE * g, gF * g, gS, None, None, None, None, None, None, None, None
+
+
 class TrainStep:
     """fwd + force + loss + backward + (all-reduce) + shared-grad rescale + clip + optimizer step."""
+
+    # `capture()` warms the step up on a stream of its own and then captures on torch's capture stream.  Gradient accumulators
+    # (AccumulateGrad nodes) that the warm-up created stay tied to the warm-up's stream for as long as anything keeps them alive —
+    # the reference cycles of a composite-closure pass do, until the cyclic collector runs — and a captured backward then
+    # accumulates on that stream: it joins the capture (torch warns that this "may break CUDA graph capture").  A subclass sets
+    # this to capture on the warm-up's stream itself, so that no stream from outside the capture takes part in it.
+    CAPTURE_ON_WARMUP_STREAM = False
 
     def __init__(self, model, world_size=1, rho_force=0.999, grad_clip_max=10.0, optimizer=None,
                  global_counts=None, fused_optimizer=False):
@@ -231,7 +258,8 @@ class TrainStep:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
+            # (CAPTURE_ON_WARMUP_STREAM: the capture runs on the stream of the warm-up instead of torch's capture stream)
+            with torch.cuda.graph(self._graph, stream=side if self.CAPTURE_ON_WARMUP_STREAM else None):
                 if check:
                     from .. import hbcheck
                     with hbcheck.record(keep=check == "keep") as self.hb:
@@ -274,6 +302,9 @@ class TrainStep:
         if self.fused is not None and bits & self.flag.GRAD:
             # exactly the steps the device skipped (counted next to the flag, csrc/optim.hip): Adam's bias-correction counter
             self.fused.steps = max(0, self.fused.steps - max(1, skipped))
+        # (everything is synchronised here.)  A step whose in-graph neighbour list outgrew the capacities poisons its gradient so
+        # that the optimizer skips it: that is no overflow of the fp16 planes — the subclass raises, nothing falls back
+        self._index_overflow()
         cap = getattr(self, "_cap_args", None)
         if fall_back_to_bf16_planes(self.model, "a training step (%s)" % ("gradient norm" if bits & self.flag.GRAD else
                                                                           "energies / forces"),
@@ -282,6 +313,10 @@ class TrainStep:
                 self._recapture()
             return True
         return False
+
+    def _index_overflow(self):
+        """Hook of `_range_check`, called after the synchronisation and the reset of a tripped flag: a step with an index build
+        inside its graph (training.periodic.PeriodicPaddedTrainStep) raises here when that build reported an error."""
 
     def _recapture(self):
         inputs, targets = self._cap_args
@@ -350,10 +385,12 @@ class PaddedTrainStep(TrainStep):
     batch's atom count into the graph); the atom count of the step (all ranks) is a device scalar filled before the
     replay.  On a CPU model (host emulation of the launchers: tests) the padded batch runs eagerly."""
 
-    def __init__(self, model, Z, N, e_cap, t_cap, max_in_degree=None, n_groups=None, a_cap=None, **kw):
+    def __init__(self, model, Z, N, e_cap, t_cap, max_in_degree=None, n_groups=None, a_cap=None, cell=None, pbc=None, **kw):
+        """`cell` (n_mol,3,3) / `pbc`: a periodic runner (padded.PaddedGraphRunner) — training.periodic.PeriodicPaddedTrainStep."""
         super().__init__(model, **kw)
         from ..padded import PaddedGraphRunner
-        self.pad = PaddedGraphRunner(model, Z, N, e_cap, t_cap, max_in_degree=max_in_degree, n_groups=n_groups, a_cap=a_cap)
+        self.pad = PaddedGraphRunner(model, Z, N, e_cap, t_cap, max_in_degree=max_in_degree, n_groups=n_groups, a_cap=a_cap,
+                                     cell=cell, pbc=pbc)
         dev = Z.device
         self.inputs = dict(self.pad.inputs, max_in_degree=self.pad.pad_degree_bound())
         dt = next(model.parameters()).dtype

@@ -12,7 +12,9 @@ to the parameters).  Loss:
 
 with B the global structure count (all ranks); `targets["S"]` (B_local,3,3), dE/d(strain)/|det cell| in ASE's sign convention,
 is needed only when rho_stress > 0.  Eager steps, `capture()`, the fused optimizer, the range flag and `world_size > 1` are
-those of `TrainStep`.  A new neighbour list every training step (padded or in-graph-rebuilt lists) is not provided.
+those of `TrainStep`.  A new neighbour list every training step — frames of a trajectory: new positions, a new cell and a new
+image list each time — trains from ONE captured graph with `PeriodicPaddedTrainStep` (below): lists handed in and padded, or built
+inside the replay.
 
 A direct-force model (`GemNet(direct_forces=True)`, GemNet-dT) trains on the same batches: constructing the step opts the model
 in (`periodic_direct_forces` and `periodic_training`), the model returns (E, F (A,1,3)) from its first-order training layers (chain programs with
@@ -30,7 +32,7 @@ targets, scale-factor fitting and the padded / in-graph runners in training mode
 """
 import torch
 
-from .ddp import TrainStep
+from .ddp import USE_FUSED_LOSS, PaddedTrainStep, TrainStep, _PeriodicLoss
 
 
 class PeriodicTrainStep(TrainStep):
@@ -80,3 +82,175 @@ class PeriodicTrainStep(TrainStep):
         if self.rho_stress > 0 and targets.get("S") is None:
             raise ValueError("PeriodicTrainStep(rho_stress > 0) needs the stress targets: targets['S'] of shape (B, 3, 3)")
         return super()._forward_backward(inputs, targets)
+
+
+class PeriodicPaddedTrainStep(PaddedTrainStep):
+    """`PeriodicTrainStep` for batches whose positions, cells, species and image neighbour lists change EVERY step (frames of a
+    trajectory; the structure layout N is fixed), replayed from ONE captured hipGraph: `PaddedTrainStep` on a periodic
+    `padded.PaddedGraphRunner` (the dummy molecule has a cell of its own, pad edges carry offset 0).  GemNet-T (E, F, S: the
+    stress term with rho_stress > 0) and GemNet-dT (E, F); GemNet-Q and an atom capacity (`a_cap`) raise.
+
+        ts = PeriodicPaddedTrainStep(model, Z, N, e_cap, t_cap, cell=cell0, pbc=pbc, max_in_degree=deg, rho_stress=0.01,
+                                     fused_optimizer=True)
+        loss = ts.step(R, idx, cell, E_t, F_t, S_t)                       # idx: pbc.PeriodicGraphBuilder(N, cutoff)(R, cell)
+        ts.attach_builder(pbc.PeriodicGraphBuilder(N, cutoff, pbc=pbc, device=dev))
+        loss = ts.step_positions(R, cell, E_t, F_t, S_t)                  # the list is built inside the replay: no read-back
+
+    The loss is `PeriodicTrainStep.loss` over the real structures (B = n_mol x world_size; the dummy molecule's energy, forces
+    and stress row never enter it), with GEMNET_FUSED_LOSS=1 on the device one launch (kernels.periodic_loss).  The graph holds
+    the optional index build, the index plan, the forward, the force graph, the loss and loss.backward(); the collective and
+    the optimizer stay outside, as in `TrainStep`.
+
+    A step of `step_positions` whose list outgrows the capacities (or breaks a padding rule: the error bits of
+    gn_pbc_index_padded_t) ran on the previous step's arrays: its flat gradient and its loss are turned into NaN inside the
+    graph, so the fused optimizer's non-finite check skips the update on the device (the eager optimizer reads the norm on the
+    host and takes the same decision) — the parameters, the moments and Adam's step counter are those before the step.  The
+    NEXT call raises ValueError with the capacities, the error bits and the sizes; the model stays in its arithmetic (no
+    fall-back to the bf16 planes, no recapture).  The report is sticky: build a larger step.
+    `world_size > 1` inherits `PaddedTrainStep`'s device-side exchange of the atom count; it has not been exercised."""
+
+    # The capture runs on the warm-up's stream (TrainStep.CAPTURE_ON_WARMUP_STREAM).  On torch's capture stream the step of a
+    # model on the composite closure (widths the chain kernel does not take) ended with "capturing stream has unjoined work" when
+    # other captures had run in the process before: the warm-up's stream was drawn into the capture by gradient accumulators the
+    # warm-up had left alive, and stayed unjoined.
+    CAPTURE_ON_WARMUP_STREAM = True
+
+    def __init__(self, model, Z, N, e_cap, t_cap, cell=None, pbc=None, max_in_degree=None, n_groups=None, rho_stress=0.0, **kw):
+        if cell is None:
+            raise ValueError("PeriodicPaddedTrainStep needs the structures' cells (cell=); use PaddedTrainStep for molecules")
+        if not getattr(model, "triplets_only", True):
+            raise NotImplementedError("PeriodicPaddedTrainStep: GemNet-T and GemNet-dT (triplets_only=True) only, not GemNet-Q "
+                                      "(periodic GemNet-Q trains on fixed index arrays: PeriodicTrainStep)")
+        direct = bool(getattr(model, "direct_forces", False))
+        if direct and float(rho_stress) > 0:
+            raise ValueError("PeriodicPaddedTrainStep(rho_stress > 0): a direct-force model has no stress (its forces are not the "
+                             "gradient of its energy); train it with rho_stress = 0")
+        super().__init__(model, Z, N, e_cap, t_cap, max_in_degree=max_in_degree, n_groups=n_groups, cell=cell, pbc=pbc, **kw)
+        self.rho_stress = float(rho_stress)
+        if direct:
+            model.periodic_direct_forces = True
+        model.periodic_training = True
+        if self.rho_stress > 0:
+            self.targets["S"] = torch.zeros(self.pad.n_mol, 3, 3, device=Z.device, dtype=self.targets["E"].dtype)
+        self._S = None
+
+    def attach_builder(self, builder):
+        """From the next capture on the graph starts with the image neighbour list itself (PaddedGraphRunner.attach_builder:
+        gn_pbc_index_padded_t reads positions AND cell at replay time).  The buffers must hold a first batch: one `step`, or
+        `ts.pad._fill(R, idx, cell=cell)`."""
+        self.pad.attach_builder(builder)
+        self._graph = None
+        self._captured = False
+        self.inputs.pop("_plan", None)
+
+    def _outputs(self, inputs):
+        if not self._captured:
+            inputs.pop("_plan", None)       # the plan is rebuilt INSIDE the capture from the static buffers (PaddedTrainStep)
+        inputs["_guard_rows"] = (self.pad.n_mol, self.pad.a_cap)
+        want_S = self.rho_stress > 0
+        if self.flag is not None:
+            inputs["_range_flag"] = self.flag
+        try:
+            out = self.model(inputs, stress=want_S)
+        finally:
+            inputs.pop("_range_flag", None)
+        self._S = out[2][:self.pad.n_mol] if want_S else None
+        E, F = out[0], out[1]
+        if F.dim() == 3:          # a direct-force model: (A,1,3)
+            F = F[:, 0]
+        return E[:self.pad.n_mol], F[:self.pad.a_cap]
+
+    def loss(self, E, F, targets):
+        B = float(self.pad.n_mol * max(self.world_size, 1))
+        S, self._S = self._S, None
+        w_s = self.rho_stress / B
+        if USE_FUSED_LOSS and E.is_cuda and E.dtype == torch.float32:
+            return _PeriodicLoss.apply(E, F, S, targets["E"], targets["F"], targets["S"] if S is not None else None,
+                                       (1 - self.rho) / (B * E.shape[1]), self.rho, w_s, self.mask, self.inv_atoms)
+        loss = super().loss(E, F, targets)
+        if S is not None:
+            d = (S - targets["S"].reshape(S.shape)).reshape(S.shape[0], 9)
+            loss = loss + torch.linalg.vector_norm(d, dim=1).sum() * w_s
+        return loss
+
+    def _in_graph(self):
+        return self.pad.builder is not None and self.inputs["R"].is_cuda
+
+    def _forward_backward(self, inputs, targets):
+        if not self._in_graph():
+            return super()._forward_backward(inputs, targets)
+        from .. import kernels as K
+        self.pad._index_in_graph()
+        loss = super()._forward_backward(inputs, targets)
+        # a list that did not fit: the step ran on the previous arrays.  force_loss / periodic_loss map a NaN difference to a
+        # ZERO cotangent, so poisoned outputs would give a zero gradient and AdamW would still move the weights (momentum,
+        # decay): the gradient itself and the loss are poisoned, the optimizer's non-finite check then skips the step
+        K.index_poison(self.buf.flat, self.pad._idx_state)
+        K.index_poison(loss, self.pad._idx_state)
+        self.pad._idx_host.copy_(self.pad._idx_state, non_blocking=True)
+        return loss
+
+    def _index_overflow(self):
+        err = self.pad.index_error() if self.pad.builder is not None else 0
+        if err:
+            raise ValueError(f"an earlier training step did not fit the capacities (e_cap {self.pad.e_cap}, t_cap {self.pad.t_cap}, "
+                             f"in-degree bound {self.pad.pad_degree_bound()}): index error bits {err}, sizes "
+                             f"{self.pad.index_sizes()} — the optimizer skipped it (the parameters did not move); build a larger "
+                             "PeriodicPaddedTrainStep")
+
+    def _check_index(self):
+        """Start of every step: the report of the completed steps (pinned memory, no synchronisation unless it is set)."""
+        if self.pad.builder is None or not self.pad.index_error():
+            return
+        torch.cuda.synchronize()
+        self._range_check()         # a tripped flag (the optimizer skipped the step): corrects Adam's counter, resets, raises
+        self._index_overflow()      # no optimizer step was asked for: nothing tripped, the report still stands
+
+    def _need_stress_target(self, S_target):
+        if self.rho_stress > 0 and S_target is None:
+            raise ValueError("PeriodicPaddedTrainStep(rho_stress > 0) needs the stress targets: S_t of shape (n_mol, 3, 3)")
+
+    def _load(self, cell, E_target, F_target, S_target):
+        A = self.pad.A
+        self.pad._set_cell(cell)
+        self.targets["E"].copy_(E_target.reshape(self.targets["E"].shape))
+        self.targets["F"][:A].copy_(F_target)
+        self.mask[:A].fill_(1.0)
+        if self.rho_stress > 0:
+            self.targets["S"].copy_(S_target.reshape(self.targets["S"].shape))
+        if self.world_size > 1:
+            import torch.distributed as dist
+            cnt = torch.full((), float(A), device=self.mask.device, dtype=torch.float64)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)          # device-side: no host sync, before the replay
+            self.inv_atoms.copy_(1.0 / cnt)
+        else:
+            self.inv_atoms.fill_(1.0 / A)
+
+    def _run(self, step_optimizer):
+        if self.inputs["R"].is_cuda and not self._captured:
+            self.capture(self.inputs, self.targets, check=getattr(self, "check", False))
+            self._captured = True
+        return self(self.inputs, self.targets, step_optimizer=step_optimizer)
+
+    def step(self, R, idx, cell, E_target, F_target, S_target=None, Z=None, step_optimizer=True):
+        """One training step on the lists handed in (pbc.PeriodicGraphBuilder's dict for R and cell)."""
+        self._need_stress_target(S_target)
+        self._check_index()
+        self.pad._fill(R, idx, Z, None, cell)
+        self._load(cell, E_target, F_target, S_target)
+        return self._run(step_optimizer)
+
+    def step_positions(self, R, cell, E_target, F_target, S_target=None, Z=None, step_optimizer=True):
+        """One training step with the image neighbour list built inside the replay from R and cell: no host read-back."""
+        if self.pad.builder is None:
+            raise RuntimeError("step_positions needs attach_builder")
+        if R.dtype != self.inputs["R"].dtype or tuple(R.shape) != (self.pad.A, 3):
+            raise TypeError(f"step_positions: positions must be {self.inputs['R'].dtype} of shape ({self.pad.A}, 3); got "
+                            f"{R.dtype} {tuple(R.shape)}")
+        self._need_stress_target(S_target)
+        self._check_index()
+        if Z is not None:
+            self.inputs["Z"][:self.pad.A].copy_(Z)
+        self._load(cell, E_target, F_target, S_target)
+        self.inputs["R"][:self.pad.A].copy_(R)
+        return self._run(step_optimizer)

@@ -743,6 +743,13 @@ int gn_cbf_project_bwd_f32(const float* g, const float* rad, const int32_t* seg_
  * E, Et, gE: nE values; F, Ft, gF: (A,3).  One workgroup, fixed order of addition. */
 int gn_force_loss_f32(const float* E, const float* Et, int64_t nE, const float* F, const float* Ft, int64_t A, const float* mask,
                       float w_e, float w_f, const float* w_f_dev, float* loss, float* gE, float* gF, void* stream);
+/* The loss of a periodic training step (training/periodic.py) with its cotangents (additive, ABI 16): the above plus the stress
+ * term,  + w_s sum_{b < B} |S_b - St_b|_F,  gS_b = w_s (S_b - St_b) / |S_b - St_b|_F (0 where the norm is 0, as ATen).
+ * S, St, gS: (B,3,3).  S == NULL: no stress term, gS untouched, and loss / gE / gF are those of gn_force_loss_f32 bit for bit
+ * (the same loops in the same order; the stress term is added last).  One workgroup, fixed order of addition. */
+int gn_periodic_loss_f32(const float* E, const float* Et, int64_t nE, const float* F, const float* Ft, int64_t A, const float* mask,
+                         const float* S, const float* St, int64_t B, float w_e, float w_f, const float* w_f_dev, float w_s,
+                         float* loss, float* gE, float* gF, float* gS, void* stream);
 
 /* ---- periodic cells, GemNet-T first-order path (csrc/pbc.hip; additive, ABI 15) -------------------------------------------
  * Edge vector with the image of the source atom:  V_e = R[id_a[e]] - (R[id_c[e]] + cell_offsets[e] cell[b(e)]),

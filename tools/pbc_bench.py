@@ -29,6 +29,11 @@ force graph on the edge and interaction-edge vectors, energy + force + stress lo
 (`quad_train_eager_ms` / `quad_train_graph_ms`), beside the molecular `TrainStep` of the same model on the same atoms without a
 cell (`quad_train_molecular_*_ms`), alternating in one process (`*_rounds`), + the counts of both graphs and the peak memory;
 with `--eager-only` nothing but eager periodic steps (for a kernel trace).
+`--train --stream [--direct]` times training on a NEW frame every step (positions walk, the cell is strained, the image list
+changes): `stream_eager_ms` (PeriodicGraphBuilder + eager PeriodicTrainStep), `stream_padded_ms` (builder +
+PeriodicPaddedTrainStep.step: one graph, lists handed in), `stream_graph_ms` (step_positions: the list built inside the replay)
+and `fixed_captured_ms` (the fixed-list captured step on frame 0: the floor), alternating in one process (`*_rounds`), optimizer
+included, + the capacities, the report of the in-graph build and the peak memory.
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -249,6 +254,90 @@ def train_direct_times(per, args):
     return out
 
 
+def stream_frames(R, cell, n, sigma=0.02, strain=2e-4, seed=5):
+    """n frames of a trajectory (numpy, float32-rounded): the positions take a Gaussian walk, the cell gets a small random strain
+    every step — positions, cell and the image neighbour list all change from frame to frame."""
+    rs = np.random.RandomState(seed)
+    R, cell = np.asarray(R, np.float64), np.asarray(cell, np.float64)
+    out = []
+    for _ in range(n):
+        out.append((R.astype(np.float32), cell.astype(np.float32)))
+        R = R + rs.normal(0, sigma, R.shape)
+        cell = cell @ (np.eye(3) + rs.normal(0, strain, (3, 3)))
+    return out
+
+
+def stream_train_times(R, Zd, Nd, cell, A, args, sized_on=8):
+    """`--train --stream`: a NEW frame (positions, cell, list) every training step, optimizer included, four ways in alternating
+    rounds: PeriodicGraphBuilder + eager PeriodicTrainStep (`stream_eager_ms`: all the parent offered for this workload), builder +
+    PeriodicPaddedTrainStep.step (`stream_padded_ms`: one graph, lists handed in), step_positions (`stream_graph_ms`: the list
+    built inside the replay) and, as the floor, the fixed-list captured PeriodicTrainStep on frame 0 (`fixed_captured_ms`).  The
+    capacities come from the first `sized_on` frames (PaddedGraphRunner.suggest_capacities / in_degree_of)."""
+    from gemnet_pytorch_amd.padded import PaddedGraphRunner
+    from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
+    from gemnet_pytorch_amd.training.periodic import PeriodicPaddedTrainStep, PeriodicTrainStep
+    torch.cuda.reset_peak_memory_stats()
+    frames = [(torch.tensor(r, device="cuda"), torch.tensor(c[None], device="cuda"))
+              for r, c in stream_frames(R, cell, args.steps + args.warmup + 1)]
+    builder = PeriodicGraphBuilder([A], args.cutoff, device="cuda")
+    lists = [builder(r, c, dtype=torch.int32) for r, c in frames[:sized_on]]
+    sizes = [PaddedGraphRunner.sizes_of(ix) for ix in lists]
+    e_cap, t_cap = PaddedGraphRunner.suggest_capacities(sizes)
+    deg = int(max(PaddedGraphRunner.in_degree_of(ix) for ix in lists) * 1.08) + 1
+    # dummy groups for the padding left when the list shrinks to 3/4 of the smallest seen: two incoming edges per pad quad
+    pad_max = e_cap - int(min(s[0] for s in sizes) * 0.75)
+    groups = max(1, -(-(-(-pad_max // 4)) // max(deg // 2, 1)))
+    rho_s = 0.0 if args.direct else 0.01
+    g = torch.Generator().manual_seed(2)
+    Et, Ft = torch.randn(1, 1, generator=g).cuda(), torch.randn(A, 3, generator=g).cuda()
+    St = None if args.direct else 0.01 * torch.randn(1, 3, 3, generator=g).cuda()
+    targets = {"E": Et, "F": Ft} if args.direct else {"E": Et, "F": Ft, "S": St}
+    new = lambda: make_model(args.cutoff, direct=args.direct, coupled=args.coupled).to("cuda")      # noqa: E731
+    out = {"direct": bool(args.direct), "rho_stress": rho_s, "frames": len(frames), "sizes_first_frames": [list(s) for s in sizes],
+           "e_cap": e_cap, "t_cap": t_cap, "max_in_degree": deg, "dummy_groups": groups}
+    print(json.dumps(out), flush=True)
+    eager = PeriodicTrainStep(new(), rho_stress=rho_s, fused_optimizer=True)
+    fixed = PeriodicTrainStep(new(), rho_stress=rho_s, fused_optimizer=True)
+    kw = dict(cell=frames[0][1], max_in_degree=deg, n_groups=groups, rho_stress=rho_s, fused_optimizer=True)
+    padded = PeriodicPaddedTrainStep(new(), Zd, Nd, e_cap, t_cap, **kw)
+    graph = PeriodicPaddedTrainStep(new(), Zd, Nd, e_cap, t_cap, **kw)
+    graph.pad._fill(frames[0][0], lists[0], cell=frames[0][1])
+    graph.attach_builder(builder)
+    fixed_inputs = dict(R=frames[0][0], Z=Zd, N=Nd, cell=frames[0][1], **lists[0])
+    fixed.capture(fixed_inputs, targets)
+    pos = {k: 0 for k in ("stream_eager", "stream_padded", "stream_graph")}
+
+    def nxt(k):
+        pos[k] = (pos[k] + 1) % len(frames)
+        return frames[pos[k]]
+
+    def f_eager():
+        r, c = nxt("stream_eager")
+        return eager(dict(R=r, Z=Zd, N=Nd, cell=c, **builder(r, c, dtype=torch.int32)), targets)
+
+    def f_padded():
+        r, c = nxt("stream_padded")
+        return padded.step(r, builder(r, c, dtype=torch.int32), c, Et, Ft, St)
+
+    def f_graph():
+        r, c = nxt("stream_graph")
+        return graph.step_positions(r, c, Et, Ft, St)
+
+    fns = {"stream_eager": f_eager, "stream_padded": f_padded, "stream_graph": f_graph,
+           "fixed_captured": lambda: fixed(fixed_inputs, targets)}
+    for k, (med, rounds) in alternated(fns, args.steps, args.warmup).items():
+        out[f"{k}_ms"], out[f"{k}_rounds"] = med, rounds
+    torch.cuda.synchronize()
+    out["index_error"] = int(graph.pad.index_error())
+    out["index_sizes_last"] = list(graph.pad.index_sizes())
+    out["losses"] = {"stream_eager": float(eager.last_loss), "stream_padded": float(padded.last_loss),
+                     "stream_graph": float(graph.last_loss), "fixed_captured": float(fixed.last_loss)}
+    out["range_trips"] = {"stream_eager": eager.flag.trips, "stream_padded": padded.flag.trips, "stream_graph": graph.flag.trips,
+                          "fixed_captured": fixed.flag.trips}
+    out["peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    return out
+
+
 def alternated(fns, steps, warmup, rounds=3):
     """{name: fn} timed in turns, `rounds` times each -> {name: (median ms, [ms of every round])}."""
     times = {k: [] for k in fns}
@@ -306,6 +395,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cutoff", type=float, default=5.0)
     ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
+    ap.add_argument("--stream", action="store_true", help="--train: a new frame (positions, cell, list) every step — eager, padded, "
+                    "in-graph list, and the fixed-list captured step as the floor; with --direct for the direct-force model")
     ap.add_argument("--direct", action="store_true", help="time a direct-force model beside the autograd-force model")
     ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
     ap.add_argument("--quad", action="store_true", help="time GemNet-Q (periodic_quadruplets) on the box")
@@ -326,6 +417,12 @@ def main():
     celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
     if args.quad:
         res = quad_train_times(Rd, Zd, Nd, celld, A, args) if args.train else quad_times(R, Rd, Zd, Nd, celld, A, args)
+        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **res)))
+        return
+    if args.stream:
+        if not args.train:
+            ap.error("--stream times the training step: use it with --train")
+        res = stream_train_times(R, Zd, Nd, cell, A, args)
         print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **res)))
         return
     model = make_model(args.cutoff).to("cuda").eval()
