@@ -75,10 +75,12 @@ __global__ __launch_bounds__(256) void pbx_pairs_kernel(const float* __restrict_
                                                         int64_t* __restrict__ cnt, const int64_t* __restrict__ off, int e_cap,
                                                         int32_t* __restrict__ s_a, int32_t* __restrict__ s_c,
                                                         int32_t* __restrict__ s_undir, int32_t* __restrict__ s_swap,
-                                                        int32_t* __restrict__ s_offs) {
+                                                        int32_t* __restrict__ s_offs, int m_fill) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= A) return;                                         // (wave-uniform: i is the wave's atom)
-  if (cellerr[0]) {
+  // m_fill: the structure of the filler atoms of an atom capacity (gn_pbc_index_padded_tv; -1: none) — they have no pair,
+  // wherever they sit and whatever the cutoff (wave-uniform: the structure is the wave's atom's)
+  if (cellerr[0] || atom_mol[i] == m_fill) {
     if (!kFill && lane == 0) cnt[i] = 0;
     return;
   }
@@ -175,11 +177,13 @@ template <bool kList>
 __global__ __launch_bounds__(256) void pbx_in_kernel(const int32_t* __restrict__ mol_off, const int32_t* __restrict__ atom_mol,
                                                      int A, const int64_t* __restrict__ off, const int32_t* __restrict__ s_c,
                                                      int e_cap, const int32_t* __restrict__ cellerr, int64_t* __restrict__ deg,
-                                                     const int64_t* __restrict__ in_ptr, int32_t* __restrict__ in_edge) {
+                                                     const int64_t* __restrict__ in_ptr, int32_t* __restrict__ in_edge,
+                                                     int m_fill) {
   const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (a >= A) return;
   const int64_t H = off[A];
-  if (cellerr[0] || 2 * H > (int64_t)e_cap) {                // the staging arrays were not written
+  // (the staging arrays were not written | a filler atom of structure m_fill: degree 0, as in pbx_pairs_kernel)
+  if (cellerr[0] || 2 * H > (int64_t)e_cap || atom_mol[a] == m_fill) {
     if (!kList && lane == 0) deg[a] = 0;
     return;
   }
@@ -217,7 +221,10 @@ __global__ void pbx_cnt3_kernel(const int32_t* __restrict__ s_a, const int64_t* 
 __global__ __launch_bounds__(256) void pbx_decide_kernel(const int64_t* __restrict__ off, const int64_t* __restrict__ off3,
                                                          const int64_t* __restrict__ deg, int A, int e_cap, int t_cap, int G,
                                                          int deg_bound, const int32_t* __restrict__ cellerr,
-                                                         int32_t* __restrict__ state) {
+                                                         int32_t* __restrict__ state, int layout_gate) {
+  // layout_gate: the layout kernel of the same step (pbc_index.hip, gn_pbc_layout) refused the sizes — state[3] holds its bit 128 and stays
+  // as it is, so that trip / commit write nothing (block-uniform: every thread reads the same word)
+  if (layout_gate && (state[3] & 128)) return;
   __shared__ int64_t mx_s[256];
   int64_t mx = 0;
   for (int a = threadIdx.x; a < A; a += 256) mx = deg[a] > mx ? deg[a] : mx;

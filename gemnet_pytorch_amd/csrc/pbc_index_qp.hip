@@ -409,25 +409,25 @@ extern "C" int gn_pbc_qindex_padded(const float* R, const float* cell, const uin
   hipLaunchKernelGGL(pbqp_cellerr_kernel, one, dim3(64), 0, st, w.cellerr, w.cellerr_i);
   // the edge list (staging) and the interaction pairs (workspace): count -> scan -> fill
   hipLaunchKernelGGL((pbx_pairs_kernel<false>), gw, b256, 0, st, R, cell, pbc, mol_off, atom_mol, A, (float)cutoff, w.geo, w.cellerr,
-                     w.cnt, w.off, e_cap, s_a, s_c, s_undir, s_swap, s_offs);
+                     w.cnt, w.off, e_cap, s_a, s_c, s_undir, s_swap, s_offs, -1);
   hipLaunchKernelGGL(pbc_scan_kernel, one, dim3(1024), 0, st, w.cnt, w.off, (int64_t)A);
   hipLaunchKernelGGL((pbx_pairs_kernel<true>), gw, b256, 0, st, R, cell, pbc, mol_off, atom_mol, A, (float)cutoff, w.geo, w.cellerr,
-                     w.cnt, w.off, e_cap, s_a, s_c, s_undir, s_swap, s_offs);
+                     w.cnt, w.off, e_cap, s_a, s_c, s_undir, s_swap, s_offs, -1);
   hipLaunchKernelGGL((pbx_pairs_kernel<false>), gw, b256, 0, st, R, cell, pbc, mol_off, atom_mol, A, (float)int_cutoff, w.geo_i,
-                     w.cellerr_i, w.cnti, w.offi, eint_cap, w.p_a, w.p_c, w.p_undir, w.p_swap, w.p_offs);
+                     w.cellerr_i, w.cnti, w.offi, eint_cap, w.p_a, w.p_c, w.p_undir, w.p_swap, w.p_offs, -1);
   hipLaunchKernelGGL(pbc_scan_kernel, one, dim3(1024), 0, st, w.cnti, w.offi, (int64_t)A);
   hipLaunchKernelGGL((pbx_pairs_kernel<true>), gw, b256, 0, st, R, cell, pbc, mol_off, atom_mol, A, (float)int_cutoff, w.geo_i,
-                     w.cellerr_i, w.cnti, w.offi, eint_cap, w.p_a, w.p_c, w.p_undir, w.p_swap, w.p_offs);
+                     w.cellerr_i, w.cnti, w.offi, eint_cap, w.p_a, w.p_c, w.p_undir, w.p_swap, w.p_offs, -1);
   GN_LAUNCH_CHECK();
   // in-degrees of both lists, the three in-edge orders
   hipLaunchKernelGGL((pbx_in_kernel<false>), gw, b256, 0, st, mol_off, atom_mol, A, w.off, s_c, e_cap, w.cellerr, w.deg, w.in_ptr,
-                     w.in_edge);
+                     w.in_edge, -1);
   hipLaunchKernelGGL((pbx_in_kernel<false>), gw, b256, 0, st, mol_off, atom_mol, A, w.offi, w.p_c, eint_cap, w.cellerr_i, w.ideg,
-                     w.off_int, (int32_t*)nullptr);
+                     w.off_int, (int32_t*)nullptr, -1);
   hipLaunchKernelGGL(pbc_scan_kernel, one, dim3(1024), 0, st, w.deg, w.in_ptr, (int64_t)A);
   hipLaunchKernelGGL(pbc_scan_kernel, one, dim3(1024), 0, st, w.ideg, w.off_int, (int64_t)A);
   hipLaunchKernelGGL((pbx_in_kernel<true>), gw, b256, 0, st, mol_off, atom_mol, A, w.off, s_c, e_cap, w.cellerr, w.deg, w.in_ptr,
-                     w.in_edge);
+                     w.in_edge, -1);
   hipLaunchKernelGGL((pbqp_src_kernel<false>), gw, b256, 0, st, mol_off, atom_mol, A, w.off, s_c, s_offs, e_cap, w.cellerr, w.in_ptr,
                      w.in_src, w.pos_src, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
   hipLaunchKernelGGL((pbqp_src_kernel<true>), gw, b256, 0, st, mol_off, atom_mol, A, w.offi, w.p_c, w.p_offs, eint_cap, w.cellerr_i,

@@ -302,6 +302,53 @@ def pbc_index_padded_t(builder, R, cell, e_cap, t_cap, a_cap, n_groups, deg_boun
         ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_pbc_index_padded_t")
 
 
+def pbc_layout(N32, n_atoms, n_mol, a_cap, a_tot, mol_off, atom_mol, batch_seg, N_pad, mask, state):
+    """The capacity layout of a periodic batch from its structure sizes ON THE DEVICE (gn_pbc_layout; what
+    padded.capacity_layout computes): N32 (n_mol) int32, n_atoms (1) int32 -> mol_off (n_mol + 2) int32, atom_mol (a_cap) int32,
+    batch_seg (a_tot) int64, N_pad (n_mol + 1) int64, mask (a_cap) float32 — no read-back, capturable.  Sizes that do not add up
+    to n_atoms, hold a zero or exceed a_cap set bit 128 in state[0] / state[3] and leave every array as it was."""
+    require_device(N32, n_atoms, mol_off, atom_mol, batch_seg, N_pad, mask, state)
+    n_mol, a_cap, a_tot = int(n_mol), int(a_cap), int(a_tot)
+    assert 0 < n_mol <= a_cap <= a_tot
+    assert N32.dtype == torch.int32 and N32.numel() == n_mol and N32.is_contiguous()
+    assert n_atoms.dtype == torch.int32 and n_atoms.numel() == 1
+    assert mol_off.dtype == torch.int32 and mol_off.numel() == n_mol + 2 and mol_off.is_contiguous()
+    assert atom_mol.dtype == torch.int32 and atom_mol.numel() == a_cap and atom_mol.is_contiguous()
+    assert batch_seg.dtype == torch.int64 and batch_seg.numel() == a_tot and batch_seg.is_contiguous()
+    assert N_pad.dtype == torch.int64 and N_pad.numel() == n_mol + 1 and N_pad.is_contiguous()
+    assert mask.dtype == torch.float32 and mask.numel() == a_cap and mask.is_contiguous()
+    assert state.dtype == torch.int32 and state.numel() >= 8
+    check(_lib.load().gn_pbc_layout(ptr(N32), ptr(n_atoms), n_mol, a_cap, a_tot, ptr(mol_off), ptr(atom_mol), ptr(batch_seg),
+                                    ptr(N_pad), ptr(mask), ptr(state), stream()), "gn_pbc_layout")
+
+
+def pbc_index_padded_tv(builder, R, cell, e_cap, t_cap, a_cap, n_groups, deg_bound, ws, staging, bufs, state):
+    """`pbc_index_padded_t` for a builder whose layout changes from replay to replay (pbc.PeriodicCapacityGraphBuilder): R
+    (a_cap,3) — the batch, then the filler atoms —, `cell` (n_mol + 1 rows of (3,3)) and the builder's `pbc` (n_mol + 1,3), all
+    read at replay time with the layout `pbc_layout` wrote in the same step (gn_pbc_index_padded_tv; ws: uint8 of
+    pbc_index_ws_bytes(a_cap, e_cap), staging: int32[7 e_cap], state: int32[8], see the header)."""
+    require_device(R, cell, ws, staging, state)
+    assert builder.a_cap == int(a_cap) and builder.B <= int(a_cap)
+    assert R.dtype == torch.float32 and R.is_contiguous() and tuple(R.shape) == (builder.a_cap, 3)
+    assert cell.dtype == torch.float32 and cell.is_contiguous() and cell.shape[0] >= builder.B + 1 and tuple(cell.shape[1:]) == (3, 3)
+    assert builder.pbc.dtype == torch.uint8 and tuple(builder.pbc.shape) == (builder.B + 1, 3)
+    assert builder.mol_off.numel() == builder.B + 2 and builder.atom_mol.numel() == builder.a_cap
+    assert staging.dtype == torch.int32 and staging.numel() >= 7 * e_cap
+    assert state.dtype == torch.int32 and state.numel() >= 8
+    assert ws.dtype == torch.uint8 and ws.numel() >= pbc_index_ws_bytes(builder.a_cap, e_cap)
+    for k in ("id_c", "id_a", "id_swap", "id_undir"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == e_cap and bufs[k].is_contiguous()
+    assert bufs["cell_offsets"].dtype == torch.int32 and tuple(bufs["cell_offsets"].shape) == (e_cap, 3)
+    assert bufs["cell_offsets"].is_contiguous()
+    for k in ("id3_reduce_ca", "id3_expand_ba"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == t_cap and bufs[k].is_contiguous()
+    check(_lib.load().gn_pbc_index_padded_tv(
+        ptr(R), ptr(cell), ptr(builder.pbc), ptr(builder.mol_off), ptr(builder.atom_mol), builder.B, builder.cutoff,
+        ptr(ws), int(e_cap), int(t_cap), int(a_cap), int(n_groups), int(deg_bound), ptr(staging), ptr(bufs["id_c"]),
+        ptr(bufs["id_a"]), ptr(bufs["id_swap"]), ptr(bufs["id_undir"]), ptr(bufs["cell_offsets"]), ptr(bufs["id3_reduce_ca"]),
+        ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_pbc_index_padded_tv")
+
+
 PADDED_Q_KEYS = ("id_c", "id_a", "id_swap", "id_undir", "id3_reduce_ca", "id3_expand_ba", "id4_int_a", "id4_int_b",
                  "id4_reduce_intm_ca", "id4_expand_intm_db", "id4_reduce_intm_ab", "id4_expand_intm_ab",
                  "id4_reduce_ca", "id4_expand_db", "id4_reduce_cab", "id4_expand_abd")

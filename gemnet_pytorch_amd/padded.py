@@ -34,7 +34,10 @@ identity as its cell and returns the stress as well; `attach_builder(pbc.Periodi
 (gn_pbc_index_padded_t: positions AND cell read at replay time) inside the graph.  A GemNet-Q that opts in
 (`model.periodic_quadruplets` and `model.periodic_quadruplets_dynamic`) runs the same way with `quad_caps=`: `int_cell_offsets`
 is padded with zeros as well and `attach_builder(pbc.PeriodicQuadGraphBuilder)` builds all eighteen arrays inside the graph
-(gn_pbc_qindex_padded).
+(gn_pbc_qindex_padded).  With `a_cap` and a model that sets `periodic_atom_capacity` (GemNet-T / GemNet-dT) the structures of a
+periodic batch may change in size from call to call as well: the filler atoms belong to the dummy structure, `capacity_layout`
+below names the layout arrays, and `attach_builder(pbc.PeriodicCapacityGraphBuilder)` puts layout (gn_pbc_layout) and list
+(gn_pbc_index_padded_tv) inside the graph.
 
 Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
 `Trainer.enable_padded_graph` (the training step in the same form), `training.periodic.PeriodicPaddedTrainStep` (the training
@@ -191,6 +194,31 @@ def dummy_positions(n_groups, like, offset=1.0e3, quad=False, bond=1.0):
     return (base[:, None, :] + d[None, :, :]).reshape(-1, 3)
 
 
+def capacity_layout(N, n_mol, a_cap, a_tot):
+    """The layout arrays of a batch of `n_mol` structures of sizes N (A = sum N atoms) inside an atom capacity — what `_fill`
+    writes into `N` / `batch_seg` for molecules, plus the two arrays of pbc.PeriodicGraphBuilder and the loss mask; the
+    reference of gn_pbc_layout (csrc/pbc_index.hip).  Pure PyTorch on N's device, no host sync:
+      mol_off (n_mol + 2) int32: exclusive scan of N, then A, then a_cap — the filler atoms [A, a_cap) form "structure" n_mol;
+      atom_mol (a_cap) int32, fillers -> n_mol;  batch_seg (a_tot) int64, fillers and dummy atoms -> n_mol;
+      N (n_mol + 1) int64: the sizes, then a_tot - A;  mask (a_cap) float32: 1 on [0, A), 0 behind."""
+    N = torch.as_tensor(N).reshape(-1).to(torch.int64)
+    if int(N.shape[0]) != int(n_mol):
+        raise ValueError(f"N must hold {int(n_mol)} structure sizes; got {int(N.shape[0])}")
+    dev = N.device
+    csum = torch.cumsum(N, 0)
+    A = csum[-1:]
+    rows = torch.arange(int(a_tot), device=dev, dtype=torch.int64)
+    seg = torch.searchsorted(csum, rows, right=True)            # rows behind A -> n_mol
+    return {
+        "mol_off": torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), csum,
+                              torch.full((1,), int(a_cap), dtype=torch.int64, device=dev)]).to(torch.int32),
+        "atom_mol": seg[:int(a_cap)].to(torch.int32),
+        "batch_seg": seg,
+        "N": torch.cat([N, int(a_tot) - A]),
+        "mask": (rows[:int(a_cap)] < A).to(torch.float32),
+    }
+
+
 def periodic_quad_opted_in(model):
     """Does `model` opt in to periodic GemNet-Q on the paths that follow a moving system (both switches of model/gemnet.py)?"""
     return bool(getattr(model, "periodic_quadruplets", False)) and bool(getattr(model, "periodic_quadruplets_dynamic", False))
@@ -217,7 +245,12 @@ class PaddedGraphRunner:
     Periodic structures (`cell` (n_mol,3,3), pbc.py; GemNet-T, fixed layout): the static inputs gain `cell` — one more row for
     the dummy molecule, the identity: volume 1 — and `cell_offsets` (e_cap,3), zero on the pad edges; `runner(R, idx, cell=)`
     returns (E, F) as for molecules and `runner.stress()` the stress of the same step.  With images an atom's in-degree is not
-    bounded by the size of its structure: `max_in_degree` is required (`in_degree_of` gives it for a few observed lists)."""
+    bounded by the size of its structure: `max_in_degree` is required (`in_degree_of` gives it for a few observed lists).
+    Periodic structures WITH `a_cap` (a model that sets `periodic_atom_capacity = True`; GemNet-T / GemNet-dT): sizes, species,
+    cells and periodic axes of the n_mol structures change from call to call — `runner(R, idx, Z=, N=, cell=)`; the filler atoms
+    belong to the dummy structure (identity cell).  `attach_builder(pbc.PeriodicCapacityGraphBuilder)` puts the layout
+    (gn_pbc_layout) and the image neighbour list (gn_pbc_index_padded_tv) inside the graph:
+    `run_positions(R, Z=, N=, cell=, pbc=)`."""
 
     def __init__(self, model, Z, N, e_cap, t_cap, max_in_degree=None, n_groups=None, a_cap=None, index_dtype=torch.int32,
                  quad_caps=None, cell=None, pbc=None):
@@ -234,7 +267,11 @@ class PaddedGraphRunner:
             if self.quad and not periodic_quad_opted_in(model):
                 raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q")
             if a_cap is not None:
-                raise NotImplementedError("periodic cells: fixed structure layout only (no a_cap)")
+                if not getattr(model, "periodic_atom_capacity", False):
+                    raise NotImplementedError("periodic cells: fixed structure layout only (no a_cap)")
+                if self.quad:
+                    raise NotImplementedError("periodic cells with an atom capacity (a_cap): GemNet-T and GemNet-dT only, not "
+                                              "GemNet-Q")
             if max_in_degree is None:
                 raise ValueError("a periodic runner needs max_in_degree: with images an atom's in-degree is not bounded by the "
                                  "atoms of its structure (PaddedGraphRunner.in_degree_of)")
@@ -305,6 +342,7 @@ class PaddedGraphRunner:
         self.out = None
         self.flag = None
         self.builder = None                 # attach_builder: the index build runs inside the replayed graph
+        self._layout_mask = None            # (a_cap, periodic) the mask the in-graph layout kernel writes: _attach_capacity_builder
         self._filled = False
         if dev.type == "cuda":
             from .runtime import RangeFlag
@@ -373,6 +411,9 @@ class PaddedGraphRunner:
         if cell is not None and not self.periodic:
             raise ValueError("this runner was built without a cell")
         A = int(R.shape[0])
+        if self.periodic and self.variable_atoms and N is not None and int(N.shape[0]) != self.n_mol:
+            raise ValueError(f"batch of {A} atoms / {int(N.shape[0])} molecules exceeds a_cap = {self.a_cap} or changes the "
+                             f"number of molecules ({self.n_mol})")
         if A != self.A:
             if not self.variable_atoms or N is None or Z is None:
                 raise ValueError("the number of atoms changed: build the runner with a_cap and pass Z and N with every call")
@@ -386,6 +427,9 @@ class PaddedGraphRunner:
             buf["batch_seg"][:A].copy_(torch.repeat_interleave(torch.arange(self.n_mol, device=N.device), N.to(torch.int64),
                                                                 output_size=A))
             buf["batch_seg"][A:].fill_(self.n_mol)
+            if self.periodic and self.variable_atoms and self.builder is not None:
+                # (an attached capacity builder: the replay rebuilds layout and lists from the builder's sizes)
+                self.builder.set_layout(N, n_atoms=A, arrays=False)
             if A < self.A:      # atoms that were real in the previous batch become filler again
                 buf["R"][A:self.A].copy_(self._R_fill[A:self.A])
                 buf["Z"][A:self.A].fill_(1)
@@ -493,11 +537,12 @@ class PaddedGraphRunner:
             return 2 * (qf // self.G + 1) if qf % self.G else 2 * (qf // self.G) + rem
         return -(-(ep // 2) // self.G)
 
-    def __call__(self, R, idx, Z=None, N=None, cell=None):
+    def __call__(self, R, idx, Z=None, N=None, cell=None, pbc=None):
         """R (A, 3) float32 on the device, idx: the index dict of this batch, Z: its atomic numbers when they change from
         batch to batch, N: its molecule sizes when those change too (runner built with `a_cap`), cell: the new cells of a
         periodic runner -> (E (n_mol, targets), F (A, [targets,] 3)); the results live in the graph's static output buffers
-        until the next call (a periodic runner's stress: `stress()`)."""
+        until the next call (a periodic runner's stress: `stress()`).  `pbc`: the periodic axes of the batch — accepted for
+        symmetry with `run_positions`; the lists handed in already reflect them."""
         if self.flag is not None and self.flag.tripped():
             # an EARLIER replay returned non-finite energies / forces (seen without synchronising: one or two calls late;
             # a caller that waits for its results anyway checks `flag.tripped()` itself and calls `recover()` — md.py)
@@ -516,9 +561,12 @@ class PaddedGraphRunner:
         on the host — the MD step of ase_calculator.py:148-170 as ONE graph.  The buffers must hold a valid batch already
         (one `_fill`): a step that does not fit the capacities keeps the previous arrays, poisons its outputs with NaN and
         reports through `index_error()`."""
-        if self.variable_atoms:
+        from .pbc import PeriodicCapacityGraphBuilder, PeriodicGraphBuilder, PeriodicQuadGraphBuilder
+        cb = isinstance(builder, PeriodicCapacityGraphBuilder)
+        if self.variable_atoms and not (self.periodic and cb):
             raise NotImplementedError("the in-graph index build needs a fixed molecule layout (no a_cap)")
-        from .pbc import PeriodicGraphBuilder, PeriodicQuadGraphBuilder
+        if cb:
+            return self._attach_capacity_builder(builder)
         pb = isinstance(builder, PeriodicGraphBuilder)
         if pb != self.periodic or (pb and builder.B != self.n_mol):
             raise ValueError("builder and runner describe different systems (periodic / molecular)")
@@ -550,9 +598,37 @@ class PaddedGraphRunner:
         self.graph = None
         self.out = None
 
+    def _attach_capacity_builder(self, builder):
+        """`attach_builder` of a periodic runner with an atom capacity: the graph starts with layout -> index build -> plan ->
+        model.  The builder's sizes are set from the batch the buffers hold; its periodic axes are the caller's
+        (`builder.set_layout(N, pbc)` before, or `run_positions(..., pbc=)`)."""
+        if not (self.periodic and self.variable_atoms) or self.quad:
+            raise ValueError("builder and runner describe different systems (a capacity builder needs a periodic runner with a_cap)")
+        if builder.B != self.n_mol or builder.a_cap != self.a_cap or self.index_dtype != torch.int32:
+            raise ValueError("builder and runner describe different systems")
+        if not self._filled:
+            raise RuntimeError("attach_builder: fill the buffers with a first batch (runner._fill / runner(R, idx)) before")
+        from . import kernels as K
+        dev = self.inputs["R"].device
+        builder.set_layout(self.inputs["N"][:self.n_mol], n_atoms=self.A, arrays=False)
+        self.builder = builder
+        self._pbc_ws = torch.zeros(K.pbc_index_ws_bytes(self.a_cap, self.e_cap), dtype=torch.uint8, device=dev)
+        self._staging = torch.zeros(7 * self.e_cap, dtype=torch.int32, device=dev)
+        self._idx_state = torch.zeros(8, dtype=torch.int32, device=dev)
+        self._idx_host = torch.zeros(8, dtype=torch.int32).pin_memory()
+        self._layout_mask = torch.zeros(self.a_cap, dtype=torch.float32, device=dev)      # 1 on the atoms of the batch
+        self.graph = None
+        self.out = None
+
     def _index_in_graph(self):
         from . import kernels as K
-        if self.periodic and self.quad:
+        if self.periodic and self.variable_atoms:
+            b = self.builder
+            K.pbc_layout(b.N32, b.n_atoms, self.n_mol, self.a_cap, self.A_tot, b.mol_off, b.atom_mol, self.inputs["batch_seg"],
+                         self.inputs["N"], self._layout_mask, self._idx_state)
+            K.pbc_index_padded_tv(b, self.inputs["R"][:self.a_cap], self.inputs["cell"], self.e_cap, self.t_cap, self.a_cap,
+                                  self.G, self.pad_degree_bound(), self._pbc_ws, self._staging, self.inputs, self._idx_state)
+        elif self.periodic and self.quad:
             K.pbc_index_padded_q(self.builder, self.inputs["R"][:self.A], self.inputs["cell"], (self.e_cap, self.t_cap) + self.quad_caps,
                                  self.a_cap, self.G, self.pad_degree_bound(), self._pbc_ws, self._staging, self.inputs,
                                  self._idx_state)
@@ -586,11 +662,53 @@ class PaddedGraphRunner:
         self._idx_state.zero_()
         self._idx_host.zero_()
 
-    def run_positions(self, R, Z=None, cell=None):
+    def _load_variable(self, R, Z, N, pbc, who):
+        """Host side of a step of a periodic runner with an atom capacity whose lists are built inside the replay: the checks
+        (before anything is copied), the builder's sizes / axes / atom count, and the filler rows of R and Z that were real in
+        the previous batch."""
+        A = int(R.shape[0]) if R.dim() == 2 else -1
+        if R.dtype != self.inputs["R"].dtype or R.dim() != 2 or R.shape[1] != 3:
+            raise TypeError(f"{who}: positions must be {self.inputs['R'].dtype} of shape (A, 3); got {R.dtype} {tuple(R.shape)}")
+        n_given = self.n_mol if N is None else int(N.shape[0])
+        if A > self.a_cap or n_given != self.n_mol:
+            raise ValueError(f"batch of {A} atoms / {n_given} molecules exceeds a_cap = {self.a_cap} or changes the "
+                             f"number of molecules ({self.n_mol})")
+        if A != self.A and (N is None or Z is None):
+            raise ValueError("the number of atoms changed: build the runner with a_cap and pass Z and N with every call")
+        if Z is not None and int(Z.shape[0]) != A:
+            raise ValueError(f"Z must hold the {A} atomic numbers of the batch; got {int(Z.shape[0])}")
+        if N is not None or pbc is not None:
+            self.builder.set_layout(N, pbc, n_atoms=A, arrays=False)
+        if A < self.A:          # atoms that were real in the previous batch become filler again
+            self.inputs["R"][A:self.A].copy_(self._R_fill[A:self.A])
+            self.inputs["Z"][A:self.A].fill_(1)
+        self.A = A
+
+    def run_positions(self, R, Z=None, cell=None, N=None, pbc=None):
         """One step with the index build inside the graph: R (A, 3) float32 on the device -> (E, F) as `__call__`; `cell`
-        (n_mol,3,3): the new cells of a periodic runner (the list is built for them inside the replay)."""
+        (n_mol,3,3): the new cells of a periodic runner (the list is built for them inside the replay).  A periodic runner with
+        an atom capacity also takes the sizes `N`, the species `Z` and the periodic axes `pbc` (n_mol,3) of the batch: the
+        layout is rebuilt inside the replay as well."""
         if self.builder is None:
             raise RuntimeError("run_positions needs attach_builder")
+        if self.periodic and self.variable_atoms:
+            if self.flag is not None and self.flag.tripped():
+                self.recover()
+            if self.index_error():
+                raise ValueError(f"an earlier step did not fit the capacities ({self.e_cap}, {self.t_cap}, {self.quad_caps}): index error bits "
+                                 f"{self.index_error()}, sizes {self.index_sizes()} — its outputs were NaN; build a larger runner")
+            self._load_variable(R, Z, N, pbc, "run_positions")
+            if Z is not None:
+                self.inputs["Z"][:self.A].copy_(Z)
+            if cell is not None:
+                self._set_cell(cell)
+            self.inputs["R"][:self.A].copy_(R)
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+            return self._results()
+        if N is not None or pbc is not None:
+            raise ValueError("N / pbc per call need a periodic runner with an atom capacity (a_cap)")
         if R.dtype != self.inputs["R"].dtype or tuple(R.shape) != (self.A, 3):
             # the neighbour list is built from the graph's own (fp32) position buffer: positions in another precision would
             # give other neighbours near the cutoff than the caller's own index build

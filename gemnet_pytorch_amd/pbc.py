@@ -19,6 +19,9 @@ The builder reads two sizes back per call.  For MD — a new list every step —
 captured graph (csrc/pbc_index.hip, kernels.pbc_index_padded_t): padded.PaddedGraphRunner(cell=...).attach_builder(builder),
 runtime.DynamicForceField(cell=...), md.predict_periodic.  The same holds for PeriodicQuadGraphBuilder (four read-backs per call)
 and a GemNet-Q that opts in with `model.periodic_quadruplets_dynamic`: csrc/pbc_index_qp.hip, kernels.pbc_index_padded_q.
+Batches whose structure SIZES change (a dataset) use `PeriodicCapacityGraphBuilder(n_mol, a_cap, cutoff)`: `set_layout(N, pbc)` per
+batch, the same dict from `builder(R, cell)`, and — attached to a PaddedGraphRunner(a_cap=, cell=) of a model that sets
+`periodic_atom_capacity` — layout and list inside the replay (kernels.pbc_layout, kernels.pbc_index_padded_tv).
 
 Training GemNet-Q with a cell (`model.periodic_quadruplets_training`, set by training.periodic.PeriodicTrainStep) differentiates
 the energy through ops_train._DistVec2 / _AngleVec2 / _AngleVec2Q / _QuadAnglesVec2 on the two leaves V and Vint
@@ -191,6 +194,88 @@ class PeriodicQuadGraphBuilder(PeriodicGraphBuilder):
                                      ptr(out["id4_reduce_cab"]), ptr(out["id4_expand_abd"]), ptr(out["Kidx4"]), stream()),
               "gn_pbc_qindex_quad")
         return {k: (out[k] if dtype == torch.int32 else out[k].to(dtype)) for k in KEYS + KEYS_Q}
+
+
+class PeriodicCapacityGraphBuilder(PeriodicGraphBuilder):
+    """`PeriodicGraphBuilder` whose layout can change: `n_mol` structures per batch inside an atom capacity `a_cap`, their sizes
+    N and periodic axes set per batch.  It owns `mol_off` (n_mol + 2), `atom_mol` (a_cap) and `pbc` (n_mol + 1,3) as device
+    buffers of the capacity shapes (the filler atoms between the batch and a_cap form "structure" n_mol:
+    padded.capacity_layout), and the sizes as the in-graph layout reads them: `N32` (n_mol) int32, `n_atoms` (1) int32.
+
+        builder = PeriodicCapacityGraphBuilder(n_mol, a_cap, cutoff, device=dev)
+        builder.set_layout(N, pbc)                     # host or device arrays
+        idx = builder(R, cell)                         # = PeriodicGraphBuilder(N, cutoff, pbc=pbc)(R, cell), array for array
+
+    Attached to a periodic `padded.PaddedGraphRunner` with `a_cap` the layout (gn_pbc_layout) and the list
+    (gn_pbc_index_padded_tv) are built inside the replay from these buffers."""
+
+    def __init__(self, n_mol, a_cap, cutoff, device="cuda"):
+        self.B, self.a_cap = int(n_mol), int(a_cap)
+        if not 0 < self.B <= self.a_cap:
+            raise ValueError(f"need 0 < n_mol <= a_cap; got n_mol = {self.B}, a_cap = {self.a_cap}")
+        self.A = None                       # atoms of the current layout (known on the host once a batch came by)
+        self.cutoff = float(cutoff)
+        self.device = torch.device(device)
+        dev = self.device
+        self.pbc = torch.ones(self.B + 1, 3, dtype=torch.uint8, device=dev)
+        self.mol_off = torch.zeros(self.B + 2, dtype=torch.int32, device=dev)
+        self.atom_mol = torch.full((self.a_cap,), self.B, dtype=torch.int32, device=dev)
+        self.N32 = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self.n_atoms = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._pbc_host = np.ones((self.B, 3), dtype=bool)
+
+    @property
+    def pbc_host(self):
+        if self._pbc_host is None:          # (axes handed in on the device: read back when a host check asks)
+            self._pbc_host = self.pbc[:self.B].cpu().numpy().astype(bool)
+        return self._pbc_host
+
+    def set_layout(self, N=None, pbc=None, n_atoms=None, arrays=True):
+        """Sizes N (n_mol,) and periodic axes pbc (n_mol,3) or (3,) of the next batch, host or device arrays (None: as they
+        are).  No host sync.  `n_atoms`: the atom count the in-graph layout checks sum(N) against (default: sum of a host N);
+        `arrays=False` leaves `mol_off` / `atom_mol` to the in-graph layout kernel."""
+        if N is not None:
+            on_dev = torch.is_tensor(N) and N.device.type != "cpu"
+            Nt = N if torch.is_tensor(N) else torch.as_tensor(np.asarray(N, dtype=np.int64))
+            Nt = Nt.reshape(-1)
+            if int(Nt.shape[0]) != self.B:
+                raise ValueError(f"N must hold {self.B} structure sizes; got {int(Nt.shape[0])}")
+            if not on_dev and n_atoms is None:
+                n_atoms = int(Nt.sum())
+            self.N32.copy_(Nt)
+            self.A = None if n_atoms is None else int(n_atoms)
+            if arrays:
+                from .padded import capacity_layout
+                lay = capacity_layout(self.N32, self.B, self.a_cap, self.a_cap)
+                self.mol_off.copy_(lay["mol_off"])
+                self.atom_mol.copy_(lay["atom_mol"])
+        if n_atoms is not None:
+            self.A = int(n_atoms)
+            self.n_atoms.fill_(int(n_atoms))
+        if pbc is not None:
+            if torch.is_tensor(pbc) and pbc.device.type != "cpu":
+                p = pbc.reshape(-1, 3)
+                if p.shape[0] not in (1, self.B):
+                    raise ValueError(f"pbc must have shape ({self.B}, 3) or (3,); got {tuple(pbc.shape)}")
+                self.pbc[:self.B].copy_(p.expand(self.B, 3) != 0)
+                self._pbc_host = None
+            else:
+                p = np.asarray(pbc.numpy() if torch.is_tensor(pbc) else pbc, dtype=bool).reshape(-1, 3)
+                if p.shape[0] not in (1, self.B):
+                    raise ValueError(f"pbc must have shape ({self.B}, 3) or (3,); got {p.shape}")
+                self._pbc_host = np.broadcast_to(p, (self.B, 3)).copy()
+                self.pbc[:self.B].copy_(torch.from_numpy(self._pbc_host.astype(np.uint8)))
+        return self
+
+    def _build(self, R, cell):
+        """The host-sized build for the current layout: the kernels of `PeriodicGraphBuilder` on the capacity buffers (their
+        first n_mol + 1 / A entries are that builder's arrays)."""
+        A = int(R.shape[0])
+        if self.A is None:
+            self.A = int(self.N32.sum().item())
+        if A != self.A or A > self.a_cap:
+            raise ValueError(f"positions of {A} atoms for a layout of {self.A} (a_cap = {self.a_cap}): set_layout(N, pbc) first")
+        return super()._build(R, cell)
 
 
 def build_indices_periodic(R, N, cell, cutoff, pbc=None, dtype=torch.int64):

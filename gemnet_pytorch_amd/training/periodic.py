@@ -88,7 +88,8 @@ class PeriodicPaddedTrainStep(PaddedTrainStep):
     """`PeriodicTrainStep` for batches whose positions, cells, species and image neighbour lists change EVERY step (frames of a
     trajectory; the structure layout N is fixed), replayed from ONE captured hipGraph: `PaddedTrainStep` on a periodic
     `padded.PaddedGraphRunner` (the dummy molecule has a cell of its own, pad edges carry offset 0).  GemNet-T (E, F, S: the
-    stress term with rho_stress > 0) and GemNet-dT (E, F); GemNet-Q and an atom capacity (`a_cap`) raise.
+    stress term with rho_stress > 0) and GemNet-dT (E, F); GemNet-Q and an atom capacity (`a_cap`) raise — the latter also for a model
+    that sets `periodic_atom_capacity` (inference only: padded.PaddedGraphRunner).
 
         ts = PeriodicPaddedTrainStep(model, Z, N, e_cap, t_cap, cell=cell0, pbc=pbc, max_in_degree=deg, rho_stress=0.01,
                                      fused_optimizer=True)
@@ -121,6 +122,11 @@ class PeriodicPaddedTrainStep(PaddedTrainStep):
         if not getattr(model, "triplets_only", True):
             raise NotImplementedError("PeriodicPaddedTrainStep: GemNet-T and GemNet-dT (triplets_only=True) only, not GemNet-Q "
                                       "(periodic GemNet-Q trains on fixed index arrays: PeriodicTrainStep)")
+        if kw.get("a_cap") is not None and getattr(model, "periodic_atom_capacity", False):
+            # (without the switch the runner's own refusal stands, word for word)
+            raise NotImplementedError("PeriodicPaddedTrainStep: an atom capacity (a_cap) with a cell is served in inference only "
+                                      "(padded.PaddedGraphRunner with model.periodic_atom_capacity); training keeps the fixed "
+                                      "structure layout")
         direct = bool(getattr(model, "direct_forces", False))
         if direct and float(rho_stress) > 0:
             raise ValueError("PeriodicPaddedTrainStep(rho_stress > 0): a direct-force model has no stress (its forces are not the "

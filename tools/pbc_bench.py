@@ -34,6 +34,12 @@ changes): `stream_eager_ms` (PeriodicGraphBuilder + eager PeriodicTrainStep), `s
 PeriodicPaddedTrainStep.step: one graph, lists handed in), `stream_graph_ms` (step_positions: the list built inside the replay)
 and `fixed_captured_ms` (the fixed-list captured step on frame 0: the floor), alternating in one process (`*_rounds`), optimizer
 included, + the capacities, the report of the in-graph build and the peak memory.
+`--ragged [--direct]` times the force evaluation on batches of a periodic DATASET: four water boxes per batch, their sides drawn from
+{2, 3, 4} per slot and per batch (24 / 81 / 192 atoms: sizes, species, cells and lists all change), three ways in alternating
+rounds: `ragged_eager_ms` (pbc.PeriodicCapacityGraphBuilder + eager model: all the fixed layout offers for this workload),
+`ragged_padded_ms` (builder + PaddedGraphRunner(a_cap=, cell=): one graph, lists handed in) and `ragged_graph_ms` (`run_positions`:
+layout and list built inside the replay), + the capacities (from the first 8 batches), the share of pad rows and filler atoms,
+the report of the in-graph build and the peak memory.
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -338,6 +344,87 @@ def stream_train_times(R, Zd, Nd, cell, A, args, sized_on=8):
     return out
 
 
+def ragged_times(args, n_mol=4, n_batches=16, sized_on=8):
+    """`--ragged`: a NEW batch of `n_mol` water boxes of different sizes every call (E, F, S; `--direct`: E, F), three ways in
+    alternating rounds: capacity builder + eager model, builder + padded replay, `run_positions`.  The capacities come from the
+    first `sized_on` batches (PaddedGraphRunner.suggest_capacities / in_degree_of, the largest atom count); later batches that
+    do not fit them are left out of the stream (`batches_left_out`)."""
+    from gemnet_pytorch_amd.padded import PaddedGraphRunner
+    from gemnet_pytorch_amd.pbc import PeriodicCapacityGraphBuilder, PeriodicGraphBuilder
+    torch.cuda.reset_peak_memory_stats()
+    rs = np.random.RandomState(9)
+    batches = []
+    for b in range(n_batches):
+        parts = [water_box(int(side), seed=100 * b + k) for k, side in enumerate(rs.choice([2, 3, 4], n_mol))]
+        Nh = [len(p[0]) for p in parts]
+        R = torch.tensor(np.concatenate([p[0] for p in parts]), dtype=torch.float32, device="cuda")
+        cell = torch.tensor(np.stack([p[2] for p in parts]), dtype=torch.float32, device="cuda")
+        batches.append(dict(R=R, Z=torch.tensor(np.concatenate([p[1] for p in parts]), device="cuda").long(),
+                            N=torch.tensor(Nh, device="cuda"), Nh=Nh, cell=cell,
+                            idx=PeriodicGraphBuilder(Nh, args.cutoff, device="cuda")(R, cell, dtype=torch.int32)))
+    sizes = [PaddedGraphRunner.sizes_of(b["idx"]) for b in batches]
+    degs = [PaddedGraphRunner.in_degree_of(b["idx"]) for b in batches]
+    e_cap, t_cap = PaddedGraphRunner.suggest_capacities(sizes[:sized_on])
+    deg = int(max(degs[:sized_on]) * 1.08) + 1
+    a_cap = max(sum(b["Nh"]) for b in batches[:sized_on])
+    pad_max = e_cap - int(min(s[0] for s in sizes[:sized_on]) * 0.75)
+    groups = max(1, -(-(-(-pad_max // 4)) // max(deg // 2, 1)))
+    model = make_model(args.cutoff, direct=args.direct, coupled=args.coupled).to("cuda").eval()
+    model.periodic_atom_capacity = True
+    kw = {} if args.direct else dict(stress=True)
+
+    def runner():
+        b0 = batches[0]
+        return PaddedGraphRunner(model, b0["Z"], b0["N"], e_cap, t_cap, max_in_degree=deg, n_groups=groups, a_cap=a_cap,
+                                 cell=b0["cell"])
+
+    padded, graph = runner(), runner()
+    keep = [b for b, s, d in zip(batches, sizes, degs) if sum(b["Nh"]) <= a_cap and padded.fits(s) and d <= deg]
+    used = [s for b, s, d in zip(batches, sizes, degs) if sum(b["Nh"]) <= a_cap and padded.fits(s) and d <= deg]
+    out = {"direct": bool(args.direct), "structures_per_batch": n_mol, "batches": len(keep), "batches_left_out": n_batches - len(keep),
+           "atoms": sorted({sum(b["Nh"]) for b in keep}), "a_cap": a_cap, "e_cap": e_cap, "t_cap": t_cap, "max_in_degree": deg,
+           "dummy_groups": groups, "filler_atom_share": 1.0 - float(np.mean([sum(b["Nh"]) for b in keep])) / a_cap,
+           "pad_edge_share": 1.0 - float(np.mean([s[0] for s in used])) / e_cap,
+           "pad_triplet_share": 1.0 - float(np.mean([s[1] for s in used])) / t_cap}
+    print(json.dumps(out), flush=True)
+    cb = PeriodicCapacityGraphBuilder(n_mol, a_cap, args.cutoff, device="cuda")
+    cb_graph = PeriodicCapacityGraphBuilder(n_mol, a_cap, args.cutoff, device="cuda")
+    b0 = keep[0]
+    graph._fill(b0["R"], b0["idx"], b0["Z"], b0["N"], b0["cell"])
+    graph.attach_builder(cb_graph)
+    pos = {k: 0 for k in ("ragged_eager", "ragged_padded", "ragged_graph")}
+
+    def nxt(k):
+        pos[k] = (pos[k] + 1) % len(keep)
+        return keep[pos[k]]
+
+    def lists(b):
+        cb.set_layout(b["Nh"])
+        return cb(b["R"], b["cell"], dtype=torch.int32)
+
+    def f_eager():
+        b = nxt("ragged_eager")
+        return model(dict(R=b["R"], Z=b["Z"], N=b["N"], cell=b["cell"], **lists(b)), **kw)
+
+    def f_padded():
+        b = nxt("ragged_padded")
+        return padded(b["R"], lists(b), Z=b["Z"], N=b["N"], cell=b["cell"])
+
+    def f_graph():
+        b = nxt("ragged_graph")
+        return graph.run_positions(b["R"], Z=b["Z"], N=b["N"], cell=b["cell"])
+
+    fns = {"ragged_eager": f_eager, "ragged_padded": f_padded, "ragged_graph": f_graph}
+    for k, (med, rounds) in alternated(fns, args.steps, args.warmup).items():
+        out[f"{k}_ms"], out[f"{k}_rounds"] = med, rounds
+    torch.cuda.synchronize()
+    out["index_error"] = int(graph.index_error())
+    out["index_sizes_last"] = list(graph.index_sizes())
+    out["range_trips"] = {"ragged_padded": padded.flag.trips, "ragged_graph": graph.flag.trips}
+    out["peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    return out
+
+
 def alternated(fns, steps, warmup, rounds=3):
     """{name: fn} timed in turns, `rounds` times each -> {name: (median ms, [ms of every round])}."""
     times = {k: [] for k in fns}
@@ -397,6 +484,8 @@ def main():
     ap.add_argument("--train", action="store_true", help="time the periodic training step instead of the force evaluation")
     ap.add_argument("--stream", action="store_true", help="--train: a new frame (positions, cell, list) every step — eager, padded, "
                     "in-graph list, and the fixed-list captured step as the floor; with --direct for the direct-force model")
+    ap.add_argument("--ragged", action="store_true", help="force evaluation on batches of four water boxes of changing sizes: capacity "
+                    "builder + eager, padded replay, layout + list inside the replay; with --direct for the direct-force model")
     ap.add_argument("--direct", action="store_true", help="time a direct-force model beside the autograd-force model")
     ap.add_argument("--coupled", action="store_true", help="--direct: forces_coupled=True")
     ap.add_argument("--quad", action="store_true", help="time GemNet-Q (periodic_quadruplets) on the box")
@@ -409,6 +498,11 @@ def main():
     from gemnet_pytorch_amd.pbc import PeriodicGraphBuilder
     from gemnet_pytorch_amd.runtime import DynamicForceField, ForceGraphs
 
+    if args.ragged:
+        if args.train or args.stream or args.quad:
+            ap.error("--ragged times the force evaluation of GemNet-T / GemNet-dT: use it alone or with --direct")
+        print(json.dumps(dict({"cutoff": args.cutoff}, **ragged_times(args))))
+        return
     R, Z, cell = water_box(args.side)
     A = len(R)
     Rd = torch.tensor(R, dtype=torch.float32, device="cuda")
