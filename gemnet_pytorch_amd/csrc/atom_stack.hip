@@ -1,4 +1,5 @@
-// The forward of the atom-row MLP stack as a kernel of its own (include/gemnet_hip.h, gn_atom_stack_fwd_f32).
+// The forward of the atom-row MLP stack as a kernel of its own (include/gemnet_hip.h, gn_atom_stack_fwd_f32), and, in the second
+// half of the file, its first-order adjoint (gn_atom_stack_bwd_f32).
 //
 // Why: the stacks that run on ATOM rows (AtomUpdateBlock: Dense + ResidualLayers + the tail projections of the concat layer,
 // M = 1 024 rows, 128 -> 128) are 64 workgroups of one 16-row tile each on 256 CUs: pure latency, and the chain
@@ -246,6 +247,268 @@ int launch_fwd_tails(const as_fwd_args& a, int tails, hipStream_t st) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ------------------------------------------------------------------------------------------------------------- adjoint
+// The first-order adjoint of the stack (gn_atom_stack_bwd_f32): the fused program of ops._Stack.backward, a LINEAR program, which
+// chain_split_kernel<1, 2, true, true> runs in the row-scaled form of the two fp16 planes (meta & 0x100 there).  The program's
+// two LDS slots are used very differently: slot 1 (X) is the operand of every GEMM, slot 0 (G, the running gradient) is only
+// ever read and rewritten element by element (residual of a GEMM, stand-alone SCALE).  So here
+//   * G lives in registers in accumulator layout AS ITS TWO PLANES plus its row scale: what the interpreter writes to the slot
+//     and reads back is split and joined at the same places under the same power-of-two scale, it just never travels;
+//   * X rotates through three LDS tiles, so that an op may write its output (or second output) while slower waves still read
+//     its operand: one barrier per op and none in front of an epilogue, none behind a tail GEMM that only updates G;
+//   * the stand-alone SCALE ops behind the last tail GEMM (the form with a skip gradient of its own) run inside its epilogue;
+//   * all LOADs sit in front of the first barrier; the stored factor of an op is requested in front of its first MFMA.
+// Arithmetic in the interpreter's order: acc -> * 1 / sigma(operand) -> * mul -> (+ residual) * beta -> out -> * sigma(result),
+// split; second output = Z2 * v.  Every multiplication that the interpreter's compiler may or may not have contracted with an
+// addition is one by a power of two, exact either way; contraction stays off in this file.
+// Knock-outs of diagnosis builds (never defined in the product library; tools/atom_stack_bwd_bench.py):
+//   AS_BWD_EXP == 1  no weight fetch      AS_BWD_EXP == 2  no factor loads (ones)
+//   AS_BWD_EXP == 3  no row-scale reductions (sigma = 1)      AS_BWD_EXP == 4  no barriers between the ops (timing only)
+#ifndef AS_BWD_EXP
+#define AS_BWD_EXP 0
+#endif
+#ifndef AS_BWD_AHEAD
+// Weight sets in flight or resident ahead of the running op.  Measured at M = 1 024 (us per launch, form A / B / no tails):
+// 1 -> 7.21 / 7.01 / 5.49, 2 -> 7.43 / 7.14 / 5.66, 3 -> 7.59 / 7.33 / 5.73 (profiles/atom_stack_bwd_timeline.txt): as in the
+// forward, what is requested early delays the fragments the first op waits for; one set ahead is the least that hides a fetch.
+#define AS_BWD_AHEAD 1
+#endif
+
+struct as_bwd_args {
+  const float* g;
+  const float* gt[2];              // cotangents of the tails
+  int M;
+  const uint4* W[AS_MAX_GEMMS];    // packed transposed planes in program order
+  const float* F[5];               // stored factors in the order of use
+  float alpha0, a_out, a_s;        // LOAD alpha; SCALE with the skip output (T = 0, form A); plain SCALE of form A
+  float bt[2], bl[2];              // beta of the tail GEMMs / of the second GEMM of every layer, program order
+  float* g_skip;
+  float* gx;
+};
+
+__device__ __forceinline__ float4 as_mul4(const float4 v, const float a) { return make_float4(v.x * a, v.y * a, v.z * a, v.w * a); }
+
+// L ResidualLayers, T tails, A: the skip gradient is an output of its own (SCALE ops stay stand-alone in the fused program)
+template <int L, int T, bool A>
+__global__ __launch_bounds__(NT) void atom_stack_bwd_kernel(const as_bwd_args P) {
+  static_assert(L >= 1 && L <= 2 && (T == 0 || T == 2), "adjoint programs of the atom stack");
+  constexpr int NG = T + 2 * L + 1;
+  constexpr int PLANE = 16 * ROWB;
+  constexpr int SLOT = 2 * PLANE;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * SLOT];     // G (once, to change layout) | X0 X1 X2
+  __shared__ float rs[3][16];                                               // row scales of the LOADs: g, gt[0], gt[1]
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int l15 = lane & 15;
+  const int lg = lane >> 4;
+  const int M = P.M;
+  const int row0 = (int)blockIdx.x * 16;
+
+  uint4 w[NG][4][2];
+  auto wload = [&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    if constexpr (j < NG) {
+      const uint4* __restrict__ const base = P.W[j] + (size_t)wave * (4 * 2 * 64) + lane;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) w[j][c][p] = AS_BWD_EXP == 1 ? make_uint4(0x3c003c00u + lane, 0u, 0u, 0u) : base[(c * 2 + p) * 64];
+    }
+  };
+  auto plane_ptr = [&](int buf, int p) -> unsigned char* { return smem + buf * SLOT + p * PLANE; };      // buf 0: G, 1 + i: X_i
+  auto sw_off = [&](int row, int col) -> int { return row * ROWB + ((((col >> 3) ^ row) & 15) << 4) + ((col & 4) << 1); };
+  auto put_planes = [&](int buf, int off, const uint2 H, const uint2 Lo) {
+    *reinterpret_cast<uint2*>(plane_ptr(buf, 0) + off) = H;
+    *reinterpret_cast<uint2*>(plane_ptr(buf, 1) + off) = Lo;
+  };
+  auto sigma_of = [&](const float4 v) -> float {      // row scale of a LOAD: one row = 32 consecutive lanes
+    if constexpr (AS_BWD_EXP == 3) return 1.f;
+    const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+    return row_sigma(group_max(m, 32));
+  };
+  // a stand-alone SCALE of the interpreter on planes held in registers: read (join), * alpha / sigma, [* Z]; the caller
+  // stores the true-scale value where the op has an output and splits value * sigma again
+  auto scale_read = [&](const uint2 H, const uint2 Lo, const float alpha, const float sc) -> float4 {
+    return as_mul4(join4h(H, Lo), alpha * inv_pow2(sc));
+  };
+
+  // ---- the LOADs (linear layout: 16 rows x 32 float4, one per thread); the rows are requested first
+  const int lr = tid >> 5, lc = (tid & 31) << 2;
+  const bool in = row0 + lr < M;
+  const size_t loff = (size_t)(row0 + lr) * SW + lc;
+  float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), tv0 = gv, tv1 = gv, zv = gv;
+  if (in) {
+    gv = *reinterpret_cast<const float4*>(P.g + loff);
+    if constexpr (T > 0) tv0 = *reinterpret_cast<const float4*>(P.gt[0] + loff);
+    if constexpr (T > 1) tv1 = *reinterpret_cast<const float4*>(P.gt[1] + loff);
+    if constexpr (T == 0) zv = AS_BWD_EXP == 2 ? make_float4(1.f, 1.f, 1.f, 1.f) : *reinterpret_cast<const float4*>(P.F[0] + loff);
+  }
+  wload(std::integral_constant<int, 0>{});
+  if constexpr (AS_BWD_AHEAD > 1) wload(std::integral_constant<int, 1>{});
+  if constexpr (AS_BWD_AHEAD > 2) wload(std::integral_constant<int, 2>{});
+  {
+    const int o = sw_off(lr, lc);
+    const float4 v = as_mul4(gv, P.alpha0);
+    const float sig = sigma_of(v);
+    uint2 H, Lo;
+    split4h(as_mul4(v, sig), H, Lo);
+    if (lc == 0) rs[0][lr] = sig;
+    if constexpr (T == 0) {
+      if constexpr (A) {
+        // SCALE 0 <- 0 * a_out with the skip gradient as its output, SCALE 0 <- 0 * a_s, SCALE 1 <- 0 * Z
+        float4 u = scale_read(H, Lo, P.a_out, sig);
+        if (in) *reinterpret_cast<float4*>(P.g_skip + loff) = u;
+        split4h(as_mul4(u, sig), H, Lo);
+        u = scale_read(H, Lo, P.a_s, sig);
+        split4h(as_mul4(u, sig), H, Lo);
+        put_planes(0, o, H, Lo);
+        u = scale_read(H, Lo, 1.f, sig);
+        if (in) { u.x *= zv.x; u.y *= zv.y; u.z *= zv.z; u.w *= zv.w; }
+        split4h(as_mul4(u, sig), H, Lo);
+        put_planes(1, o, H, Lo);
+      } else {
+        // the LOAD's second tensor: v * alpha2 (1) * Z2
+        put_planes(0, o, H, Lo);
+        float4 u = v;
+        if (in) { u.x *= zv.x; u.y *= zv.y; u.z *= zv.z; u.w *= zv.w; }
+        split4h(as_mul4(u, sig), H, Lo);
+        put_planes(1, o, H, Lo);
+      }
+    } else {
+      put_planes(0, o, H, Lo);
+      const float s0 = sigma_of(tv0);
+      split4h(as_mul4(tv0, s0), H, Lo);
+      put_planes(1, o, H, Lo);
+      if (lc == 0) rs[1][lr] = s0;
+      if constexpr (T > 1) {
+        const float s1 = sigma_of(tv1);
+        split4h(as_mul4(tv1, s1), H, Lo);
+        put_planes(2, o, H, Lo);
+        if (lc == 0) rs[2][lr] = s1;
+      }
+    }
+  }
+  lds_barrier();
+
+  // accumulator layout of this lane: row l15 of the tile, columns 16 wave + 4 lg .. + 3
+  const int n0 = wave * 16 + (lg << 2);
+  const bool ok = row0 + l15 < M;
+  const uint32_t off = (uint32_t)(row0 + l15) * (uint32_t)SW + (uint32_t)n0;   // M <= 4 096 rows
+  const int my = sw_off(l15, n0);
+  // G: its planes and its row scale, from here on in registers; rs1: the row scale of X
+  uint2 GH = *reinterpret_cast<const uint2*>(plane_ptr(0, 0) + my), GL = *reinterpret_cast<const uint2*>(plane_ptr(0, 1) + my);
+  float rs0 = rs[0][l15], rs1 = rs0;
+
+  auto gemm = [&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    constexpr bool tail = j < T;
+    constexpr bool fin = j == NG - 1;
+    constexpr int m = j - T;                                       // main GEMMs: even = first of a layer's adjoint (mul), odd = second
+    constexpr bool mulop = !tail && !fin && (m & 1) == 0;
+    constexpr bool resop = tail || (!fin && (m & 1) == 1);         // (. + G) * beta
+    constexpr bool scales = tail && j == T - 1 && A;               // out = g_skip and the two SCALE ops
+    constexpr bool second = resop && !scales && !(tail && j < T - 1);      // second output Z2 * v -> X
+    constexpr int fi = tail ? 0 : 1 + m;                           // stored factor of this op
+    constexpr bool factor = mulop || second || scales;
+    constexpr int a_buf = 1 + j % 3, y_buf = 1 + (j + 1) % 3;
+    // every operand of the op is requested before its first MFMA
+    uint4 xf[4][2];
+    {
+      const unsigned char* xb = smem + a_buf * SLOT + l15 * ROWB;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const unsigned char* xp = xb + ((((c << 2) | lg) ^ l15) << 4);
+        xf[c][0] = *reinterpret_cast<const uint4*>(xp);
+        xf[c][1] = *reinterpret_cast<const uint4*>(xp + PLANE);
+      }
+    }
+    float sa = rs1;
+    if constexpr (tail) sa = rs[1 + j][l15];
+    float4 fz = mulop ? make_float4(1.f, 1.f, 1.f, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (factor) {
+      if (ok) fz = AS_BWD_EXP == 2 ? make_float4(1.f, 1.f, 1.f, 1.f) : *reinterpret_cast<const float4*>(P.F[fi] + off);
+    }
+    v4f acc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = (v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f16x8 ah = __builtin_bit_cast(f16x8, w[j][c][0]), al = __builtin_bit_cast(f16x8, w[j][c][1]);
+      const f16x8 yh = __builtin_bit_cast(f16x8, xf[c][0]), yl = __builtin_bit_cast(f16x8, xf[c][1]);
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl, acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh, acc[2], 0, 0, 0);
+    }
+    const v4f corr = acc[1] + acc[2];
+    float4 v = make_float4(as_fma(corr[0], H_DOWN, acc[0][0]), as_fma(corr[1], H_DOWN, acc[0][1]),
+                           as_fma(corr[2], H_DOWN, acc[0][2]), as_fma(corr[3], H_DOWN, acc[0][3]));
+    wload(std::integral_constant<int, j + AS_BWD_AHEAD>{});     // this op's fragments are dead
+    v = as_mul4(v, inv_pow2(sa));                               // the products are sigma(operand) times the true values
+    if constexpr (fin) {
+      if (ok) *reinterpret_cast<float4*>(P.gx + off) = v;
+    } else if constexpr (mulop) {
+      v.x *= fz.x; v.y *= fz.y; v.z *= fz.z; v.w *= fz.w;
+      uint2 H, Lo;
+      split4h(ok ? as_mul4(v, sa) : make_float4(0.f, 0.f, 0.f, 0.f), H, Lo);
+      put_planes(y_buf, my, H, Lo);
+      rs1 = sa;
+      if constexpr (AS_BWD_EXP != 4) lds_barrier();
+    } else {
+      // what the op leaves behind takes the smaller scale (the larger magnitude) of its operand and of G
+      const float sy = fminf(sa, rs0);
+      const float4 q = as_mul4(join4h(GH, GL), inv_pow2(rs0));
+      const float b = tail ? P.bt[tail ? j : 0] : P.bl[tail ? 0 : (m >> 1)];
+      v.x = (v.x + q.x) * b; v.y = (v.y + q.y) * b; v.z = (v.z + q.z) * b; v.w = (v.w + q.w) * b;
+      if constexpr (scales) {
+        if (ok) *reinterpret_cast<float4*>(P.g_skip + off) = v;
+      }
+      split4h(ok ? as_mul4(v, sy) : make_float4(0.f, 0.f, 0.f, 0.f), GH, GL);
+      rs0 = sy;
+      if constexpr (scales) {
+        // SCALE 0 <- 0 * a_s and SCALE 1 <- 0 * Z of the interpreter, on the planes just written
+        float4 u = scale_read(GH, GL, P.a_s, sy);
+        split4h(as_mul4(u, sy), GH, GL);
+        u = scale_read(GH, GL, 1.f, sy);
+        if (ok) { u.x *= fz.x; u.y *= fz.y; u.z *= fz.z; u.w *= fz.w; }
+        uint2 H, Lo;
+        split4h(as_mul4(u, sy), H, Lo);
+        put_planes(y_buf, my, H, Lo);
+      } else if constexpr (second) {
+        float4 u = fz;
+        u.x *= v.x; u.y *= v.y; u.z *= v.z; u.w *= v.w;
+        uint2 H, Lo;
+        split4h(ok ? as_mul4(u, sy) : make_float4(0.f, 0.f, 0.f, 0.f), H, Lo);
+        put_planes(y_buf, my, H, Lo);
+      }
+      if constexpr (scales || second) {
+        rs1 = sy;
+        if constexpr (AS_BWD_EXP != 4) lds_barrier();
+      }
+    }
+  };
+  gemm(std::integral_constant<int, 0>{});
+  gemm(std::integral_constant<int, 1>{});
+  gemm(std::integral_constant<int, 2>{});
+  if constexpr (NG > 3) gemm(std::integral_constant<int, 3>{});
+  if constexpr (NG > 4) gemm(std::integral_constant<int, 4>{});
+  if constexpr (NG > 5) gemm(std::integral_constant<int, 5>{});
+  if constexpr (NG > 6) gemm(std::integral_constant<int, 6>{});
+}
+
+template <int L, int T, bool A>
+int launch_bwd(const as_bwd_args& a, hipStream_t st) {
+  hipLaunchKernelGGL((atom_stack_bwd_kernel<L, T, A>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int L>
+int launch_bwd_form(const as_bwd_args& a, int tails, int form, hipStream_t st) {
+  if (tails == 0) return form ? launch_bwd<L, 0, true>(a, st) : launch_bwd<L, 0, false>(a, st);
+  return form ? launch_bwd<L, 2, true>(a, st) : launch_bwd<L, 2, false>(a, st);
+}
+
 }  // namespace
 
 extern "C" int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tails, const void* const* W, float* const* z,
@@ -275,4 +538,30 @@ extern "C" int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tail
     case 1: return launch_fwd_tails<1>(a, tails, st);
     default: return launch_fwd_tails<2>(a, tails, st);
   }
+}
+
+extern "C" int gn_atom_stack_bwd_f32(const float* g, int M, int layers, int tails, int form, const float* const* gt,
+                                     const void* const* W, const float* const* F, float alpha0, float a_out, float a_s, float bt0,
+                                     float bt1, float bl0, float bl1, float* g_skip, float* gx, void* stream) {
+  if (M <= 0) return 0;
+  if (M > AS_MAX_ROWS || layers < 1 || layers > 2 || (tails != 0 && tails != 2) || form < 0 || form > 1) return (int)hipErrorInvalidValue;
+  if (!g || !gx || !W || !F || (tails && !gt) || (form == 1) != (g_skip != nullptr)) return (int)hipErrorInvalidValue;
+  if (!aligned16(g) || !aligned16(gx) || !aligned16(g_skip)) return (int)hipErrorInvalidValue;
+  as_bwd_args a = {};
+  a.g = g; a.M = M; a.alpha0 = alpha0; a.a_out = a_out; a.a_s = a_s; a.g_skip = g_skip; a.gx = gx;
+  a.bt[0] = bt0; a.bt[1] = bt1; a.bl[0] = bl0; a.bl[1] = bl1;
+  for (int j = 0; j < tails; ++j) {
+    if (!gt[j] || !aligned16(gt[j])) return (int)hipErrorInvalidValue;
+    a.gt[j] = gt[j];
+  }
+  for (int j = 0; j < tails + 2 * layers + 1; ++j) {
+    if (!W[j] || !aligned16(W[j])) return (int)hipErrorInvalidValue;
+    a.W[j] = static_cast<const uint4*>(W[j]);
+  }
+  for (int j = 0; j < 2 * layers + 1; ++j) {
+    if (!F[j] || !aligned16(F[j])) return (int)hipErrorInvalidValue;
+    a.F[j] = F[j];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return layers == 1 ? launch_bwd_form<1>(a, tails, form, st) : launch_bwd_form<2>(a, tails, form, st);
 }

@@ -1698,6 +1698,131 @@ def _atom_stack_fwd(M, m):
           "gn_atom_stack_fwd_f32")
 
 
+# The first-order adjoint of those stacks (ops._Stack.backward behind fuse_program) runs on the second kernel of the same file
+# (DESIGN.md section 25), bit-identical again; a switch of its own, so that GEMNET_ATOM_STACK=0 / 1 compare forwards only.
+USE_ATOM_STACK_BWD = os.environ.get("GEMNET_ATOM_STACK_BWD", "1") == "1"
+
+
+def _atom_adj_gemm(o):
+    """A GEMM op of 128 x 128 of a first-order adjoint program: no activation, no form gn_atom_stack_bwd_f32 leaves out."""
+    return (o["kind"] == "gemm" and tuple(o["W"].shape) == (ATOM_STACK_WIDTH, ATOM_STACK_WIDTH) and not o["act"]
+            and not o.get("pre_deriv") and o["alpha"] == 1.0 and o["a_slot"] == 1 and o["pre_out"] is None
+            and o["gadd1"] is None and o["gadd2"] is None and o["res_rows"] is None and o["res2"] is None
+            and o["out2"] is None and o.get("add") is None and o.get("add2") is None and o["alpha2"] == 1.0 and o["y2_src"] == 0)
+
+
+def _atom_adj_res(o, M):
+    """GEMM 1 -> 0 with the running gradient as its residual: (. + slot 0) * beta."""
+    return (_atom_adj_gemm(o) and o["slot"] == 0 and o["mul"] is None and type(o["res"]) is int and o["res"] == 0)
+
+
+def _atom_adj_second(o, M):
+    """... whose second output is slot 1 <- y * Z2 (a stored factor)."""
+    return _atom_adj_res(o, M) and o["out"] is None and o["y2"] == 1 and o["mode2"] == 1 and _atom_mat(o["Z2"], M)
+
+
+def _atom_adj_scale(o, dst, M, Z=False, out=False):
+    """SCALE dst <- slot 0 * alpha [* Z, a stored factor] [with a global output]."""
+    return (o["kind"] == "scale" and o["slot"] == dst and o["a_slot"] == 0 and o["width"] in (None, ATOM_STACK_WIDTH)
+            and o.get("add") is None and (_atom_mat(o["Z"], M) and o.get("mode", 0) == 1 and o["alpha"] == 1.0 if Z else o["Z"] is None)
+            and (_atom_mat(o["out"], M) if out else o["out"] is None))
+
+
+def atom_stack_adjoint_match(prog, mode=None):
+    """Is `prog` the FUSED first-order adjoint of an atom-row stack in a form csrc/atom_stack.hip runs?  With G = slot 0, X = slot 1:
+         T = 2:  LOAD g -> G;  LOAD gt1 -> X, GEMM (. + G) * beta -> G;  LOAD gt2 -> X, GEMM (. + G) * beta -> G
+                 form 0: that GEMM's second output X = G * Z        form 1: its output g_skip, SCALE G *= a, SCALE X = G * Z
+         T = 0:  form 0: LOAD g * alpha -> G with the second tensor X = G * Z
+                 form 1: LOAD g -> G, SCALE G *= a with output g_skip, SCALE G *= a, SCALE X = G * Z
+         L in {1, 2} times [GEMM X -> X times a stored factor;  GEMM (. + G) * beta -> G, second output X = G * Z];  GEMM X -> gx
+    at width 128 -> 128, 1 <= M <= 4 096, mode "h3", tall layout, factors stored as ssilu'(z).  -> the operands of
+    gn_atom_stack_bwd_f32, or None (running sums, parked skips, gathered adds, dz0 outputs, one tail, training sweeps: the chain launch)."""
+    M, ops = prog.M, prog.ops
+    if not (1 <= M <= ATOM_STACK_MAX_ROWS) or (mode or current_mode()) != "h3" or CHAIN_LAYOUT != "tall":
+        return None
+    if not (4 <= len(ops) <= 12) or any(o["kind"] == "store" for o in ops):
+        return None
+
+    def plain_load(o, slot):
+        return (o["kind"] == "load" and o["slot"] == slot and o["rows"] is None and o.get("add2") is None and _atom_mat(o["src"], M)
+                and o.get("alpha", 1.0) == 1.0 and o.get("y2", -1) < 0 and o.get("Z2") is None)
+    o = ops[0]
+    m = dict(g=None, gt=[], gemms=[], F=[], form=0, alpha0=1.0, a_out=1.0, a_s=1.0, bt=[1.0, 1.0], bl=[1.0, 1.0], g_skip=None, gx=None)
+    i = 1
+    if plain_load(o, 0):
+        if plain_load(ops[1], 1):                                   # two tails
+            if not (len(ops) >= 8 and _atom_adj_res(ops[2], M) and ops[2]["out"] is None and ops[2]["y2"] < 0 and ops[2]["Z2"] is None
+                    and plain_load(ops[3], 1) and _atom_adj_res(ops[4], M)):
+                return None
+            m["gt"], m["gemms"], m["bt"] = [ops[1]["src"], ops[3]["src"]], [ops[2], ops[4]], [ops[2]["beta"], ops[4]["beta"]]
+            t = ops[4]
+            if _atom_adj_second(t, M):
+                m["F"].append(t["Z2"])
+                i = 5
+            elif (_atom_mat(t["out"], M) and t["y2"] < 0 and t["Z2"] is None and _atom_adj_scale(ops[5], 0, M)
+                  and _atom_adj_scale(ops[6], 1, M, Z=True)):
+                m.update(form=1, g_skip=t["out"], a_s=ops[5]["alpha"])
+                m["F"].append(ops[6]["Z"])
+                i = 7
+            else:
+                return None
+        elif (_atom_adj_scale(ops[1], 0, M, out=True) and _atom_adj_scale(ops[2], 0, M) and _atom_adj_scale(ops[3], 1, M, Z=True)):
+            m.update(form=1, g_skip=ops[1]["out"], a_out=ops[1]["alpha"], a_s=ops[2]["alpha"])
+            m["F"].append(ops[3]["Z"])
+            i = 4
+        else:
+            return None
+    elif (o["kind"] == "load" and o["slot"] == 0 and o["rows"] is None and o.get("add2") is None and _atom_mat(o["src"], M)
+          and o.get("y2", -1) == 1 and o.get("alpha2", 1.0) == 1.0 and o.get("mode2", 0) == 1 and _atom_mat(o.get("Z2"), M)):
+        m["alpha0"] = o.get("alpha", 1.0)
+        m["F"].append(o["Z2"])
+    else:
+        return None
+    m["g"] = o["src"]
+    main = ops[i:]
+    L = (len(main) - 1) // 2
+    if len(main) not in (3, 5):
+        return None
+    for k in range(L):
+        a, b = main[2 * k], main[2 * k + 1]
+        if not (_atom_adj_gemm(a) and a["slot"] == 1 and a["res"] is None and a["out"] is None and a["y2"] < 0 and a["Z2"] is None
+                and a["mul_mode"] == 1 and _atom_mat(a["mul"], M) and _atom_adj_second(b, M)):
+            return None
+        m["F"] += [a["mul"], b["Z2"]]
+        m["bl"][k] = b["beta"]
+    f = main[-1]
+    if not (_atom_adj_gemm(f) and f["slot"] < 0 and f["mul"] is None and f["res"] is None and f["y2"] < 0 and f["Z2"] is None
+            and _atom_mat(f["out"], M)):
+        return None
+    m["gemms"] = m["gemms"] + list(main)
+    m.update(L=L, gx=f["out"])
+    return m
+
+
+def _atom_stack_bwd(M, m):
+    """Launch gn_atom_stack_bwd_f32 for a matched program (atom_stack_adjoint_match)."""
+    fmt = SPLIT_FORMAT["h3"]
+    require_device(m["g"], m["gx"], m["g_skip"], *m["gt"], *m["F"])
+    Ws = []
+    for g in m["gemms"]:
+        Wp = g.get("packed")
+        if Wp is None:
+            _mat(g["W"])
+            Wp = pack_weight_split(g["W"], fmt=fmt)
+        elif getattr(Wp, "_gn_fmt", 0) != fmt:
+            raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a launch in "
+                               f"mode 'h3' (format {fmt})")
+        Ws.append(Wp)
+    gt, F = m["gt"], m["F"]
+    arr = ctypes.c_void_p
+    check(_lib.load().gn_atom_stack_bwd_f32(ptr(m["g"]), int(M), int(m["L"]), len(gt), int(m["form"]),
+                                            (arr * max(1, len(gt)))(*[addr(a) for a in gt]), (arr * len(Ws))(*[addr(W) for W in Ws]),
+                                            (arr * len(F))(*[addr(a) for a in F]), float(m["alpha0"]), float(m["a_out"]),
+                                            float(m["a_s"]), float(m["bt"][0]), float(m["bt"][1]), float(m["bl"][0]),
+                                            float(m["bl"][1]), ptr(m["g_skip"]), ptr(m["gx"]), stream()),
+          "gn_atom_stack_bwd_f32")
+
+
 def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
     """Run a ChainProgram (one launch).
     groups > 0 (gn_chain_split_grouped_f32): `prog` describes group 0 — M rows, operands = the first slab of stacked tensors
@@ -1711,6 +1836,10 @@ def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
         m = atom_stack_match(prog, mode)
         if m is not None:
             return _atom_stack_fwd(prog.M, m)
+    if USE_ATOM_STACK_BWD and not groups and prog.M <= ATOM_STACK_MAX_ROWS:
+        m = atom_stack_adjoint_match(prog, mode)
+        if m is not None:
+            return _atom_stack_bwd(prog.M, m)
     nprod = CHAIN_MODES[mode]
     if nprod and not chain_split_supported(prog):
         nprod = 0

@@ -190,6 +190,25 @@ int gn_chain_split_grouped_f32(const gn_chain_args* args, int nprod, int groups,
  * (M,128) outputs.  layers 0..2, tails 0..2; every matrix contiguous and 16-byte aligned; else hipErrorInvalidValue. */
 int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tails, const void* const* W, float* const* z, float s,
                           const float* res2, float beta2, float* y, float* const* t, void* stream);
+/* The first-order adjoint of that stack (ops._Stack.backward behind kernels.fuse_program) as the second kernel of
+ * csrc/atom_stack.hip (additive, ABI 16).  With G the running gradient (LDS slot 0 of the chain program), X its slot 1:
+ *   tails == 0, form 0:  G = g * alpha0;  X = G * F[0]                                   (the LOAD with a second tensor)
+ *   tails == 0, form 1:  G = g;  g_skip = G = G * a_out;  G = G * a_s;  X = G * F[0]       (LOAD and three SCALE ops)
+ *   tails == 2:          G = g;  G = (gt[0] W[0] + G) * bt0;  G = (gt[1] W[1] + G) * bt1;
+ *            form 0:     X = G * F[0]                                                    (second output of the tail GEMM)
+ *            form 1:     g_skip = G;  G = G * a_s;  X = G * F[0]                            (two SCALE ops)
+ *   per layer k < layers:  X = (X W[tails + 2k]) * F[1 + 2k];  G = (X W[tails + 1 + 2k] + G) * bl_k;  X = G * F[2 + 2k]
+ *   gx = X W[tails + 2 layers]
+ * in the row-scaled two-fp16-plane arithmetic of gn_chain_split_f32 (nprod = GN_CHAIN_F16X2, a linear program), every
+ * rounding in the same place: gx and g_skip are bit for bit that launch's; nothing else is written.
+ * gt: host array of `tails` (M,128) cotangents of the tail projections; W: host array of tails + 2 layers + 1 packed TRANSPOSED
+ * weights (gn_pack_weight_split_fmt(..., trans = 1, GN_SPLIT_F16X2), N = K = 128) in program order; F: host array of
+ * 1 + 2 layers (M,128) factors ssilu'(pre-activation) as gn_atom_stack_fwd_f32 stored them, in the order of use.
+ * layers 1..2, tails 0 or 2, form 0..1 (g_skip only in form 1), 1 <= M <= 4 096 (M <= 0: nothing is launched); every matrix
+ * contiguous and 16-byte aligned; else hipErrorInvalidValue. */
+int gn_atom_stack_bwd_f32(const float* g, int M, int layers, int tails, int form, const float* const* gt, const void* const* W,
+                          const float* const* F, float alpha0, float a_out, float a_s, float bt0, float bt1, float bl0, float bl1,
+                          float* g_skip, float* gx, void* stream);
 /* W (N,K) fp32 with row pitch ldw — or, trans != 0, the (K,N) matrix whose transpose is the weight — -> three bf16
  * planes in MFMA-fragment order; `out` holds gn_pack_weight_split_bytes(N,K) bytes (16-byte aligned). */
 int gn_pack_weight_split(const float* W, int N, int K, int ldw, int trans, void* out, void* stream);
