@@ -576,6 +576,7 @@ extern "C" int gn_rbf_aggregate_grouped_fwd_f32(const float* const* m_list, cons
   if (n_atoms <= 0 || G == 0) return 0;
   agg_group_tab T = {};
   for (int g = 0; g < G; ++g) {
+    // (also what a caller with E = 0 gets — there is no E here to tell it from a forgotten pointer: include/gemnet_hip.h)
     if (!m_list[g] || !W_list[g]) return (int)hipErrorInvalidValue;
     T.m[g] = m_list[g];
     T.W[g] = W_list[g];

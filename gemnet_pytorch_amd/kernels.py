@@ -524,6 +524,10 @@ def rbf_aggregate_grouped_fwd(m_list, rbf, W_list, scales, perm, seg_off, n_atom
     rbf, scales = _f32c(rbf), _f32c(scales)
     G = len(m_list)
     assert len(W_list) == G and scales.numel() == G
+    if m_list[0].shape[0] == 0:
+        # no edge at all (a single atom, a dissociated pair): every segment is empty and an empty tensor has no address to put
+        # into the pointer table, which the launcher rejects — the sums are zero, nothing is launched
+        return torch.zeros((G, n_atoms, m_list[0].shape[1]), device=rbf.device, dtype=torch.float32)
     out = torch.empty((G, n_atoms, m_list[0].shape[1]), device=rbf.device, dtype=torch.float32)
     arr = ctypes.c_void_p * G
     check(_lib.load().gn_rbf_aggregate_grouped_fwd_f32(arr(*[addr(t) for t in m_list]), arr(*[addr(t) for t in W_list]),

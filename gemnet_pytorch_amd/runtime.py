@@ -315,7 +315,9 @@ class DynamicForceField:
                     return out
             err = r.index_error()
             r.reset_index_state()                   # this / an earlier step outgrew the capacities: size them anew below
-            if err & (32 | 64):                     # the cell itself: the builder's own check says what is wrong with it
+            # periodic builders: the cell itself, the builder's own check says what is wrong with it.  (The molecular GemNet-Q
+            # build reports I > i_cap and Q > q_cap in these two bits: capacities, re-sized below like the others.)
+            if self.periodic and err & (32 | 64):
                 bad = self._restore_cell()
                 self.builder.check_cell(bad)
                 raise ValueError(f"the in-graph neighbour list rejected the cell (index error bits {err})")

@@ -282,7 +282,11 @@ int gn_rbf_aggregate_bwd_f32(const float* g_out, const float* m, const float* rb
  *   forward: out (G, n_atoms, C) stacked; out[g] is bit for bit gn_rbf_aggregate_fwd_f32(m_list[g], rbf, W_list[g], scales[g]).
  *   adjoint: g_out (G, n_atoms, C) stacked; g_m_list[g] (E,C) bit for bit the single launch's g_m (bit g of `accum_m`: +=);
  *            ONE g_rbf (E,R) = sum over g = 0 .. G-1, in that order, of the single launches' g_rbf (accum_rbf != 0: g_rbf +=).
- *            A wave handles one edge for all groups: the indices, the rbf row and g_rbf are touched once per edge. */
+ *            A wave handles one edge for all groups: the indices, the rbf row and g_rbf are touched once per edge.
+ *   No edge at all (E = 0): the adjoint takes E and returns at once.  The forward has no E argument and cannot tell an empty
+ *   list from a forgotten pointer, so it answers a NULL entry of m_list / W_list with hipErrorInvalidValue where the single
+ *   launch accepts m == NULL with all segments empty: a caller without edges writes the zeros itself and does not call it
+ *   (kernels.rbf_aggregate_grouped_fwd does). */
 #define GN_AGG_MAX_GROUPS 8
 int gn_rbf_aggregate_grouped_fwd_f32(const float* const* m_list, const float* const* W_list, const float* scales, int G,
                                      const float* rbf, const int32_t* perm, const int32_t* seg_off, float* out, int64_t n_atoms,

@@ -119,6 +119,8 @@ def _nth(fn, x, order):
     with torch.enable_grad():
         xx = x.detach().clone().requires_grad_(True)
         y = fn(xx)
+        if y.numel() == 0:          # an empty list (no edge / no triplet): nothing to differentiate, and no -1 to infer
+            return y.detach()
         flat = y.reshape(y.shape[0], -1)
         cols = []
         for j in range(flat.shape[1]):
@@ -517,7 +519,7 @@ def quad_basis_bwd_packed(gY, R, qc, qa, qb, qd, S):
 
 def bil_fused_fwd(Y, x, B, W2T, sp, alpha=1.0, W2T_planes=None):
     Sm, P = bil_reduce_project(Y, x, B, sp)
-    return Sm, (P.reshape(P.shape[0], -1) @ W2T.t()) * alpha
+    return Sm, (P.reshape(P.shape[0], P.shape[1] * P.shape[2]) @ W2T.t()) * alpha
 
 
 def _angle_uv(u, v):
@@ -599,7 +601,7 @@ def cbf_project_supported(rad, y, W):
 
 
 def cbf_project_fwd(rad, ie32, y, W):
-    return (rad[ie32.long()] * y[:, :, None]).reshape(y.shape[0], -1) @ W.t()
+    return (rad[ie32.long()] * y[:, :, None]).reshape(y.shape[0], y.shape[1] * rad.shape[2]) @ W.t()
 
 
 def cbf_project_bwd(g, rad, seg_off, y, W):

@@ -185,3 +185,28 @@ def test_quadruplet_step_that_outgrows_the_capacities_is_reported_and_leaves_the
     E3, F3 = run.run_positions(R)
     torch.cuda.synchronize()
     assert torch.equal(E3, E1) and torch.equal(F3, F1) and run.index_error() == 0
+
+
+def test_quadruplet_force_field_resizes_when_the_quadruplet_list_outgrows_its_capacity():
+    """DynamicForceField on a molecular GemNet-Q: a 16-atom molecule contracted to 0.9 of its size keeps its edges inside e_cap
+    but has 15 % more quadruplets than the first step (err bits 2 | 64: T > t_cap, Q > q_cap).  Bits 32 / 64 are capacities of
+    the molecular build (include/gemnet_hip.h, gn_index_gpu_padded_q) and cell errors of the periodic ones only: the step is
+    re-sized and repeated (it used to look for the cell of a force field that has none)."""
+    mol = make_molecule(16, 7)
+    R0, Z = mol["R"].astype(np.float32), torch.tensor(mol["Z"], device=DEV).long()
+    c = R0.mean(0, keepdims=True)
+    model = new_model(quad=True)
+    ff = DynamicForceField(model, Z, [16], 5.0, 10.0)
+    builder = DeviceGraphBuilder(np.array([16]), 5.0, 10.0, False, device=DEV)
+    sizes = []
+    for s in (1.0, 1.0, 0.9, 1.0):
+        R = torch.tensor((R0 - c) * s + c, device=DEV, dtype=torch.float32)
+        E, F = ff(R)
+        idx = builder(R)
+        Er, Fr = model(dict(Z=Z, R=R.clone(), N=torch.tensor([16], device=DEV), **idx))
+        torch.cuda.synchronize()
+        sizes.append(PaddedGraphRunner.sizes_of(idx))
+        assert torch.equal(E, Er.detach()) and torch.equal(F, Fr.detach()), (s, float((F - Fr).abs().max()))
+    e_cap0 = int(sizes[0][0] * 1.12) // 12 * 12 + 24          # the first runner's capacities (margin 0.08)
+    assert sizes[2][0] <= e_cap0 and sizes[2][4] > int(1.08 * sizes[0][4]) + 4, sizes
+    assert ff.recaptures == 1

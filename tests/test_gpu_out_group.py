@@ -77,6 +77,31 @@ def test_grouped_aggregation_forward_is_bit_identical_to_the_single_launches(agg
 
 
 @gpu
+@pytest.mark.parametrize("A", [1, 17])
+def test_grouped_aggregation_without_any_edge(A):
+    """E = 0 (a single atom, a dissociated pair as a batch of its own): m, rbf and the CSR permutation are empty tensors.  The
+    grouped forward returns the zeros of tests/cpu_kernels.py and of the single launches (it used to fail with hip error 1:
+    an empty tensor has no address for the launcher's pointer table); the adjoint returns empty gradients."""
+    import cpu_kernels as CK
+    G = 3
+    g = torch.Generator().manual_seed(A)
+    ia = put(torch.zeros(0, dtype=torch.int32))
+    perm, seg = K.csr_build(ia, A)
+    m = [put(torch.zeros(0, C)) for _ in range(G)]
+    W = [put(torch.randn(C, NR, generator=g) / 4) for _ in range(G)]
+    rbf, scales = put(torch.zeros(0, NR)), put(0.5 + torch.rand(G, generator=g))
+    out = K.rbf_aggregate_grouped_fwd(m, rbf, W, scales, perm, seg, A)
+    assert out.shape == (G, A, C)
+    seg_cpu = torch.zeros(A + 1, dtype=torch.int32)
+    for i in range(G):
+        ref = CK.rbf_aggregate_fwd(m[i].cpu().double(), rbf.cpu().double(), W[i].cpu().double(), None, seg_cpu, A, float(scales[i]))
+        assert ref.shape == (A, C) and torch.equal(out[i].cpu().double(), ref) and not bool(ref.any())
+        assert torch.equal(out[i], K.rbf_aggregate_fwd(m[i], rbf, W[i], perm, seg, A, float(scales[i])))
+    g_m, g_rbf = K.rbf_aggregate_grouped_bwd(put(torch.randn(G, A, C, generator=g)), m, rbf, W, scales, ia)
+    assert all(t.shape == (0, C) for t in g_m) and g_rbf.shape == (0, NR)
+
+
+@gpu
 @pytest.mark.parametrize("G", [1, 2, 5])
 def test_grouped_aggregation_adjoint_matches_the_single_launches(agg, G):
     acc = [agg.prev_m.clone() if i == agg.acc_group else None for i in range(G)]
