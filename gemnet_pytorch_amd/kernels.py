@@ -1202,6 +1202,33 @@ def direct_force_bwd(gF, V, id_swap, id_a, n_atoms, out=None):
     return out
 
 
+COL_VAR_WIDTHS = (8, 16, 32, 64, 128)
+
+
+def col_var(x, idx32, acc, slot, w):
+    """acc[slot] += w * torch.var(x[idx32], dim=0).mean() in float64, the gathered rows never written (gn_col_var_f32: one pass
+    over memory, shifted float64 sums, a fixed grid and a fixed-order final reduction — no atomics, bit-reproducible, nothing
+    read back).  x (n_src, C) float32 contiguous, C in COL_VAR_WIDTHS; idx32 (n,) int32 or None (the rows of x as they are);
+    acc: a float64 device tensor.  Fewer than two rows, another width, a non-contiguous or non-float32 x raise before a launch."""
+    require_device(x, idx32, acc)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError(f"col_var: a contiguous float32 (n_src, C) array expected; got {x.dtype} {tuple(x.shape)} "
+                        f"strides {tuple(x.stride())}")
+    n_src, C = int(x.shape[0]), int(x.shape[1])
+    if C not in COL_VAR_WIDTHS:
+        raise ValueError(f"col_var: width {C} is not one of {COL_VAR_WIDTHS}")
+    if idx32 is not None and (idx32.dtype != torch.int32 or idx32.dim() != 1 or not idx32.is_contiguous()):
+        raise TypeError("col_var: idx must be a contiguous int32 vector")
+    n = n_src if idx32 is None else int(idx32.shape[0])
+    if n < 2 or n_src < 1:
+        raise ValueError(f"col_var: a variance needs at least two rows; got {n}")
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or not 0 <= int(slot) < acc.numel():
+        raise ValueError("col_var: acc must be a contiguous float64 tensor with the slot inside it")
+    ws = torch.empty((_lib.GN_COL_VAR_MAX_BLOCKS * 2 * C,), device=x.device, dtype=torch.float64)
+    check(_lib.load().gn_col_var_f32(ptr(x), ptr(idx32), ptr(ws), ptr(acc), n_src, n, C, int(slot), float(w), stream()),
+          "gn_col_var_f32")
+
+
 class ChainProgram:
     """A program for gn_chain_f32: ops over the three LDS slots of a row tile (see include/gemnet_hip.h).
     Operands named `mul/res/res2` are either an int (LDS slot) or a tensor (global (M,N))."""

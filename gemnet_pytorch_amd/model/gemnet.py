@@ -104,6 +104,10 @@ class GemNet(torch.nn.Module):
         # with cell= and quad_caps=, runtime.DynamicForceField(cell=), md.DeviceMolecule / predict_periodic) accept this model —
         # the quadruplet index build inside the captured graph (csrc/pbc_index_qp.hip).  False: they raise as before
         self.periodic_quadruplets_dynamic = False
+        # opt-in: scale-factor fitting (AutomaticFit.fitting_mode) on periodic batches, in eval mode, for GemNet-T, GemNet-dT
+        # (with `periodic_direct_forces`) and GemNet-Q (with `periodic_quadruplets`): _forward_periodic_fit, driven by
+        # training.periodic.fit_scale_factors.  False: a fit-mode call with a cell raises
+        self.periodic_scale_fitting = False
         # arithmetic of the LDS-resident Dense stacks: None = the package default ("h3": fp32 operands as two fp16 planes,
         # three products), "split6" = three bf16 planes / six products (fp32 exponent range), "f32" = the f32-input MFMA — all
         # three at fp32 accuracy (force MAE 1e-6 .. 4e-6 eV/A against float64).  Single-plane bf16 / three-product modes exist
@@ -585,6 +589,8 @@ class GemNet(torch.nn.Module):
         `force_graph = True`) returns the same outputs with an autograd graph to the parameters; without it that call raises.
         A GemNet-Q (`triplets_only=False`) needs `periodic_quadruplets = True` for a cell at all and, for that second-order graph,
         `periodic_quadruplets_training = True` as well (training.periodic.PeriodicTrainStep sets all three); else it raises.
+        While the scale factors are being fitted (`AutomaticFit.fitting_mode`) a periodic batch needs `periodic_scale_fitting = True`
+        and eval mode (`_forward_periodic_fit`, training.periodic.fit_scale_factors); else it raises.
         Range guard of the default Dense arithmetic: the "h3" forward programs keep activations in two fp16 planes, so a
         value beyond 65 504 becomes inf — fitted scale factors keep activations O(1), a model with
         unfitted ones (the starting state of fit_scaling.py, foreign checkpoints) need not.  A non-finite result of an eager
@@ -704,6 +710,9 @@ class GemNet(torch.nn.Module):
         # (and widths the split-operand chain kernel takes in every sweep, see _train2_widths_ok: the CPU emulation takes any)
         t2 = (bool(graph) and ops.USE_TRAIN2 and not AutomaticFit.fitting_mode and mode != "f32" and self.num_targets == 1
               and (not R.is_cuda or self._train2_widths_ok()))
+        if cell is not None and AutomaticFit.fitting_mode:
+            # (`periodic_scale_fitting`, eval mode, fixed index arrays, no capture: _check_periodic turned the rest away)
+            return self._forward_periodic_fit(R, plan, cell)
         if cell is not None and self.direct_forces:
             # (training mode: `periodic_training` is on — _check_periodic turned the rest away; eval mode never looks at it)
             if self.training:
@@ -762,6 +771,18 @@ class GemNet(torch.nn.Module):
 
     def _check_periodic(self, inputs, stress=False):
         """What a cell is not supported with raises (no silent molecular result)."""
+        who = "periodic cells" if self.triplets_only else "periodic cells (GemNet-Q)"
+        if AutomaticFit.fitting_mode and getattr(self, "periodic_scale_fitting", False):
+            # scale-factor fitting with a cell (opt-in): one eval-mode pass over fixed index arrays per batch, outside a capture
+            # (AutoScaleFit counts rows on the host and fit() reads the sums back) — the rest of this method judges the family
+            if self.training or self.force_graph:
+                raise NotImplementedError(f"{who}: scale-factor fitting with a cell runs in eval mode without a force graph "
+                                          "(model.eval(), force_graph = None)")
+            if inputs.get("_guard_rows") is not None:
+                raise NotImplementedError(f"{who}: scale-factor fitting with a cell runs on fixed index arrays only — the dummy "
+                                          "rows of a padded batch would enter the statistics")
+            if inputs["R"].is_cuda and torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError(f"{who}: scale-factor fitting with a cell cannot run inside a stream capture")
         if not self.triplets_only:
             if not getattr(self, "periodic_quadruplets", False):
                 raise NotImplementedError("periodic cells: GemNet-T (triplets_only=True) only, not GemNet-Q (eval-mode GemNet-Q "
@@ -791,10 +812,9 @@ class GemNet(torch.nn.Module):
                 raise NotImplementedError("periodic cells: a direct-force model has no stress (its forces are not the "
                                           "gradient of its energy)")
         # (the messages of a quadruplet model name it: every refusal of a periodic GemNet-Q batch says "GemNet-Q")
-        who = "periodic cells" if self.triplets_only else "periodic cells (GemNet-Q)"
         if self.num_targets != 1:
             raise NotImplementedError(f"{who}: one target only")
-        if AutomaticFit.fitting_mode:
+        if AutomaticFit.fitting_mode and not getattr(self, "periodic_scale_fitting", False):
             raise NotImplementedError(f"{who}: no scale-factor fitting with a cell")
         # (padded batches — padded.PaddedGraphRunner(cell=...) — are ordinary periodic batches: the dummy molecule has a cell
         #  row of its own and its pad edges carry offset 0; `_guard_rows` / `max_in_degree` mean what they mean for molecules)
@@ -827,6 +847,39 @@ class GemNet(torch.nn.Module):
             F = pbc.forces_q(G, Gint, plan)
             S = pbc.stress_q(V.detach(), G, Vint.detach(), Gint, plan, cell)
         return E_mol.detach(), F, S
+
+    def _forward_periodic_fit(self, R, plan, cell):
+        """The eval call's outputs — (E, F, S), or (E, F (A,1,3)) from a direct-force model — of a periodic batch while the scale
+        factors are being fitted (`periodic_scale_fitting`): the UNFUSED layer order on the edge vectors V (and Vint), the one the
+        factors' observation points sit in (`_forward_periodic_train`'s order), with constant weights and a first-order force
+        gradient only.  Inside `scaling.periodic_statistic()` the two bilinear sums hand their expand index to the factor and the
+        active factor takes the device statistic (gn_col_var_f32; GEMNET_FIT_STAT=0: a materialised gather + torch.var)."""
+        from .. import pbc
+        from .scaling import periodic_statistic
+        ctx = (ops.weight_cache(self._wcache), ops.fused_first_order(False), ops.param_grads(False), ops.train2(False, None),
+               ops.chain_mode(self.matmul_precision), ops.position_graph(False), periodic_statistic(True))
+        with contextlib.ExitStack() as stack:
+            for c in ctx:
+                stack.enter_context(c)
+            if self.direct_forces:
+                V = pbc.edge_vectors(R, plan, cell)
+                with torch.no_grad():
+                    E_mol, terms, _ = self._energy(R.detach(), plan, V=V, force_terms=True)
+                    F = pbc.direct_forces(torch.stack(terms), V, plan, self.forces_coupled)
+                return E_mol, F
+            V = pbc.edge_vectors(R, plan, cell).requires_grad_(True)
+            Vint = None if self.triplets_only else pbc.int_edge_vectors(R, plan, cell).requires_grad_(True)
+            with torch.enable_grad():
+                E_mol, _, _ = self._energy(R.detach(), plan, V=V, Vint=Vint)
+                if Vint is None:
+                    G = torch.autograd.grad(E_mol, V, grad_outputs=self._cotangent(E_mol, 0))[0]
+                else:
+                    G, Gint = torch.autograd.grad(E_mol, (V, Vint), grad_outputs=self._cotangent(E_mol, 0), allow_unused=True)
+        if Vint is None:
+            return E_mol.detach(), pbc.forces(G, plan), pbc.stress(V.detach(), G, plan, cell)
+        G = torch.zeros_like(V) if G is None else G
+        Gint = torch.zeros_like(Vint) if Gint is None else Gint
+        return E_mol.detach(), pbc.forces_q(G, Gint, plan), pbc.stress_q(V.detach(), G, Vint.detach(), Gint, plan, cell)
 
     def _forward_periodic_direct(self, R, plan, cell):
         """E, F (A,1,3) of a periodic batch from a direct-force model (`periodic_direct_forces`): nothing is differentiated, so

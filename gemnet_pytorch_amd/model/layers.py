@@ -25,7 +25,7 @@ from scipy.optimize import brentq as _brentq
 
 from .. import ops
 from .initializers import he_orthogonal_init
-from .scaling import AutomaticFit, ScalingFactor
+from .scaling import AutomaticFit, ScalingFactor, periodic_statistic_active
 
 INV_SQRT_2 = 1 / (2.0 ** 0.5)
 INV_SQRT_3 = 1 / (3.0 ** 0.5)
@@ -478,7 +478,12 @@ class TripletInteraction(torch.nn.Module):
         # gather by id3_expand_ba is fused into the segmented reduce (no (T,C) tensor)
         x = self.mlp_cbf(rbf_W1, sph, x_ba, plan.trip)
         # the reference observes the variance of the GATHERED rows (interaction_block.py:678-682)
-        x = self.scale_cbf_sum(ops.gather_rows(x_ba, plan.trip.expand) if AutomaticFit.fitting_mode else x_ba, x)
+        if AutomaticFit.fitting_mode and periodic_statistic_active():
+            # a periodic fit (GemNet.periodic_scale_fitting): the factor reads the rows through the index, and only while it is
+            # the one being fitted — no (T, C) array
+            x = self.scale_cbf_sum(x_ba, x, ref_index=plan.trip.expand)
+        else:
+            x = self.scale_cbf_sum(ops.gather_rows(x_ba, plan.trip.expand) if AutomaticFit.fitting_mode else x_ba, x)
         x_ca = self.up_projection_ca(x)
         x_ac = ops.gather_rows(self.up_projection_ac(x), plan.id_swap)
         return (x_ca + x_ac) * INV_SQRT_2
@@ -528,7 +533,10 @@ class QuadrupletInteraction(torch.nn.Module):
         x_db = ops.gather_rows(x_db, plan.intm_db)                 # (I, emb_quad)
         x_db = self.scale_cbf(x_db, x_db * self.mlp_cbf(cbf))
         x = self.mlp_sbf(rbf_W1, sph, x_db, plan.quad)             # gather by id4_expand_abd fused
-        x = self.scale_sbf_sum(ops.gather_rows(x_db, plan.quad.expand) if AutomaticFit.fitting_mode else x_db, x)
+        if AutomaticFit.fitting_mode and periodic_statistic_active():
+            x = self.scale_sbf_sum(x_db, x, ref_index=plan.quad.expand)           # (as in TripletInteraction: no (Q, C) array)
+        else:
+            x = self.scale_sbf_sum(ops.gather_rows(x_db, plan.quad.expand) if AutomaticFit.fitting_mode else x_db, x)
         x_ca = self.up_projection_ca(x)
         x_ac = ops.gather_rows(self.up_projection_ac(x), plan.id_swap)
         return (x_ca + x_ac) * INV_SQRT_2

@@ -15,13 +15,43 @@ Implementation: the fitting order lives in one explicit `_FitSchedule` object; `
 (`activeVar`, `queue`, `fitting_mode`) are read-through properties of it, so there is no scattered class state.
 """
 import collections
+import contextlib
 import logging
 import math
+import os
 
 import numpy as np
 import torch
 
 from .utils import read_value_json, update_json
+
+# The statistic of a fit on PERIODIC batches (GemNet.periodic_scale_fitting): "1" (default) — gn_col_var_f32 (csrc/fit_stat.hip):
+# the variance of the rows x[ref_index] in one pass over memory, float64 sums in a device-resident accumulator, no gathered
+# array; "0" — the ATen statistic of the molecular fit on the same wiring (a materialised gather + torch.var, float32 sums).
+USE_FIT_STAT = os.environ.get("GEMNET_FIT_STAT", "1") == "1"
+_PERIODIC = False
+
+
+@contextlib.contextmanager
+def periodic_statistic(enabled=True):
+    """While enabled (GemNet's fit-mode pass over a periodic batch) the two bilinear sums hand their expand index to the factor
+    instead of a gathered array, and the active factor takes the device statistic (USE_FIT_STAT)."""
+    global _PERIODIC
+    old = _PERIODIC
+    _PERIODIC = bool(enabled)
+    try:
+        yield
+    finally:
+        _PERIODIC = old
+
+
+def periodic_statistic_active():
+    return _PERIODIC
+
+
+def _kernel_statistic(t):
+    """Does an observation of `t` go to the kernel?  (tests/pbc_fit_common.py answers for its host restatement.)"""
+    return USE_FIT_STAT and _PERIODIC and t.is_cuda and t.dtype == torch.float32
 
 
 class _FitSchedule:
@@ -121,12 +151,26 @@ class AutoScaleFit(AutomaticFit):
         self._sum_var_ref = 0.0
         self._sum_var_out = 0.0
         self._rows = 0
+        self._dev_sums = None       # float64 (2,) on the device: [sum rows * var_ref, sum rows * var_out] (the kernel statistic)
 
-    def observe(self, x_ref, y):
+    def observe(self, x_ref, y, ref_index=None):
+        """`ref_index` (an ops.RowIndex): the reference rows are x_ref[ref_index] — not formed when the kernel reads them."""
         if self.fitted or not self.is_active():
             return
         rows = y.shape[0]
+        if _kernel_statistic(y):
+            from .. import kernels as K
+            if self._dev_sums is None:
+                self._dev_sums = torch.zeros(2, device=y.device, dtype=torch.float64)
+            with torch.no_grad():
+                K.col_var(x_ref.detach(), None if ref_index is None else ref_index.idx32, self._dev_sums, 0, float(rows))
+                K.col_var(y.detach(), None, self._dev_sums, 1, float(rows))
+            self._rows += rows
+            return
         with torch.no_grad():
+            if ref_index is not None:
+                from .. import ops
+                x_ref = ops.gather_rows(x_ref.detach(), ref_index)
             self._sum_var_ref = self._sum_var_ref + rows * torch.var(x_ref, dim=0).mean()
             self._sum_var_out = self._sum_var_out + rows * torch.var(y, dim=0).mean()
         self._rows += rows
@@ -137,8 +181,12 @@ class AutoScaleFit(AutomaticFit):
         if self._rows == 0:
             raise ValueError(f"Did not track the variable {self.name}. "
                              "Add observe calls to track the variance before and after.")
-        var_ref = float(self._sum_var_ref) / self._rows
-        var_out = float(self._sum_var_out) / self._rows
+        sum_ref, sum_out = float(self._sum_var_ref), float(self._sum_var_out)
+        if self._dev_sums is not None:          # the one read-back of the kernel statistic
+            dev = self._dev_sums.cpu().tolist()
+            sum_ref, sum_out = sum_ref + dev[0], sum_out + dev[1]
+        var_ref = sum_ref / self._rows
+        var_out = sum_out / self._rows
         correction = float(np.float32(math.sqrt(var_ref / var_out)))   # the json holds float32-rounded factors
         logging.info(f"Variable: {self.name}, Var_in: {var_ref:.3f}, Var_out: {var_out:.3f} "
                      f"=> Scaling factor: {correction:.3f}")
@@ -157,9 +205,9 @@ class ScalingFactor(torch.nn.Module):
 
         self._cached = None  # (tensor version, python float)
 
-    def forward(self, x_ref, y):
+    def forward(self, x_ref, y, ref_index=None):
         y = y * self.scale_factor
-        self.autofit.observe(x_ref, y)
+        self.autofit.observe(x_ref, y, ref_index)
         return y
 
     def value(self) -> float:

@@ -28,11 +28,55 @@ GemNet-Q (`triplets_only=False`, forces by autograd) trains on the batches of `P
 opts the model in (`periodic_quadruplets`, `periodic_training` and `periodic_quadruplets_training`).  The second-order force graph
 then runs on the edge vectors V and the interaction-edge vectors Vint (ops_train._AngleVec2Q / _QuadAnglesVec2,
 csrc/pbc_quad_train.hip; pbc.force_stress_q); `rho_stress > 0` and `capture()` work as for GemNet-T.  A direct-force GemNet-Q, several
-targets, scale-factor fitting and the padded / in-graph runners in training mode still raise.
+targets, scale-factor fitting (without `periodic_scale_fitting`) and the padded / in-graph runners in training mode still raise.
+
+The scale factors themselves are fitted on periodic batches by `fit_scale_factors` (below): the loop of fit_scaling.py on a model
+that opted in with `periodic_scale_fitting`, for GemNet-T, GemNet-dT and autograd-force GemNet-Q.
 """
 import torch
 
 from .ddp import USE_FUSED_LOSS, PaddedTrainStep, TrainStep, _PeriodicLoss
+
+
+def fit_scale_factors(model, batches, num_batches=25, stress=False):
+    """Fit every scale factor the model's scale file does not hold yet on periodic batches: the loop of fit_scaling.py:153-159.
+
+        AutomaticFit.set2fitmode()
+        model = GemNet(**cfg, scale_file=path).to("cuda")
+        model.periodic_scale_fitting = True            # + the family's own switch (periodic_direct_forces / periodic_quadruplets)
+        fitted = fit_scale_factors(model, batches)
+
+    `batches`: a sequence (or any re-iterable) of periodic input dicts (Z, R, N, cell + the arrays of pbc.PeriodicGraphBuilder /
+    PeriodicQuadGraphBuilder), cycled.  Per factor, in creation order: `num_batches` eval-mode calls, then its `fit()` (the one
+    read-back of its statistic), which writes it to the scale file.  -> {name: value} as written.  On the way out — also after an
+    error — fit mode is off and the schedule reset; the model is in eval mode and the next call runs the ordinary fused path
+    with the fitted factors (the caches of derived weight forms are dropped)."""
+    import itertools
+
+    from ..model.scaling import AutomaticFit
+    if not AutomaticFit.fitting_mode:
+        raise RuntimeError("fit_scale_factors: build the model after AutomaticFit.set2fitmode()")
+    if not getattr(model, "periodic_scale_fitting", False):
+        raise RuntimeError("fit_scale_factors: opt the model in first (model.periodic_scale_fitting = True)")
+    batches = list(batches) if not isinstance(batches, (list, tuple)) else batches
+    if not batches or int(num_batches) < 1:
+        raise ValueError("fit_scale_factors needs at least one batch and num_batches >= 1")
+    fitted = {}
+    model.eval()
+    try:
+        stream = itertools.cycle(batches)
+        while not AutomaticFit.fitting_completed():
+            for _ in range(int(num_batches)):
+                model(next(stream), stress=stress)
+            var = AutomaticFit.activeVar
+            var.fit()
+            fitted[var.name] = float(var.variable.detach().cpu())
+    finally:
+        AutomaticFit.fitting_mode = False
+        AutomaticFit.reset()
+        model._wcache = {}
+        model._packs.clear()
+    return fitted
 
 
 class PeriodicTrainStep(TrainStep):

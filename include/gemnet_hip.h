@@ -1040,6 +1040,23 @@ int gn_quad_angles_vec_jvp_f32(const float* V, const float* Vint, const float* t
                                const int32_t* q_db, const int32_t* q_abd, const int32_t* intm_ab, float* tang, int64_t Q,
                                void* stream);
 
+/* ---- the statistic of the scale-factor fit (csrc/fit_stat.hip; additive, ABI 16) ---------------------------------------------
+ * scaling.py:143-147 (AutoScaleFit.observe) without the gathered array: x (n_src,C) float32 contiguous and 16-byte aligned,
+ * idx (n) int32 or NULL (= the rows 0..n-1; then n <= n_src),
+ *   acc[slot] += w * 1/C sum_c Var_c,   Var_c = the unbiased variance of column c over the n rows x[idx[q], :]
+ * i.e. w * torch.var(x[idx], dim=0).mean() in float64.  C is one of 8, 16, 32, 64, 128 (every width of a scale point of the
+ * model: emb_size_quad / _trip / _bil_* / _edge / _atom of the published and of the test configurations).  The gathered rows are
+ * never written.  float64 accumulation of shifted sums (the shift is the first row, d = x - x[idx[0]] is exact in float64): a
+ * column mean that is large against the spread costs no digits, equal rows give exactly 0.  No atomics: a fixed grid (a
+ * function of n and C) of at most GN_COL_VAR_MAX_BLOCKS blocks over contiguous row ranges writes 2 C partial sums each to ws
+ * (GN_COL_VAR_MAX_BLOCKS * 2 * C doubles), a second one-block launch adds them in block order and updates acc[slot]:
+ * bit-reproducible.  An idx entry outside [0, n_src) reads nothing and counts as a copy of the first row.  acc is read and
+ * written by one thread of the second launch: calls on one stream accumulate in call order.  Nothing is read back.
+ * Another C, n < 2, n_src < 1, slot < 0 or a misaligned x: hipErrorInvalidValue before any launch. */
+#define GN_COL_VAR_MAX_BLOCKS 2048
+int gn_col_var_f32(const float* x, const int32_t* idx, double* ws, double* acc, int64_t n_src, int64_t n, int C, int slot,
+                   double w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,9 @@ rounds: `ragged_eager_ms` (pbc.PeriodicCapacityGraphBuilder + eager model: all t
 `ragged_padded_ms` (builder + PaddedGraphRunner(a_cap=, cell=): one graph, lists handed in) and `ragged_graph_ms` (`run_positions`:
 layout and list built inside the replay), + the capacities (from the first 8 batches), the share of pad rows and filler atoms,
 the report of the in-graph build and the peak memory.
+`--fit [--quad]` times one FIT-MODE forward (scale-factor fitting on the box, GemNet.periodic_scale_fitting) with the bilinear
+sum's factor of block 1 active: `fit_kernel_ms` (the statistic of csrc/fit_stat.hip, rows read through the expand index) against
+`fit_aten_ms` (GEMNET_FIT_STAT=0: a materialised gather + torch.var), alternating, + the peak memory of one pass of each.
 Prints one JSON line.  The share of the periodic kernels comes from a separate kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/pbc_bench.py --steps 20
 (kernel names pbc_* / *_vec_* are the periodic path; edge_basis_* / trip_basis_* without _vec are its molecular twins)."""
@@ -85,9 +88,10 @@ def timed(fn, steps, warmup):
     return t0.elapsed_time(t1) / steps
 
 
-def make_model(cutoff=5.0, direct=False, coupled=False, quad=False, int_cutoff=10.0):
+def make_model(cutoff=5.0, direct=False, coupled=False, quad=False, int_cutoff=10.0, scale_file=None):
     """The 4-block, 128-wide GemNet-T of this tool (seeded weights, fitted scale factors), on the host; `direct`: the
-    direct-force model of the same architecture with the periodic switch set."""
+    direct-force model of the same architecture with the periodic switch set.  `scale_file`: another scale json than the
+    package's (--fit: one factor missing)."""
     from gemnet_pytorch_amd.model.gemnet import GemNet
     from oracle import gemnet_oracle as GO
     cfg = dict(num_spherical=7, num_radial=6, num_blocks=4, emb_size_atom=128, emb_size_edge=128, emb_size_trip=64,
@@ -97,7 +101,7 @@ def make_model(cutoff=5.0, direct=False, coupled=False, quad=False, int_cutoff=1
         cfg.update(direct_forces=True, forces_coupled=bool(coupled))
     if quad:
         cfg.update(triplets_only=False, int_cutoff=float(int_cutoff))
-    scale_file = os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
+    scale_file = scale_file or os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json")
     params = GO.make_params(cfg, 1, GO.load_scale_factors(scale_file), dtype=torch.float32)
     model = GemNet(**cfg, scale_file=scale_file)
     model.load_state_dict(GO.expand_to_reference_state_dict(params))
@@ -475,6 +479,52 @@ def direct_times(per, R, A, Zd, Nd, celld, args):
     return out
 
 
+def fit_times(per, args):
+    """--fit [--quad]: one fit-mode forward (GemNet.periodic_scale_fitting) on the box with the bilinear sum's factor of block 1
+    (`TripInteraction_1_sum_cbf`, --quad: `QuadInteraction_1_sum_sbf`) as the active one: the kernel statistic (GEMNET_FIT_STAT=1:
+    rows read through the expand index, gn_col_var_f32) against the ATen statistic (=0: materialised gather + torch.var),
+    alternating in one process, three rounds; + the peak device memory of one pass of each."""
+    import tempfile
+
+    from gemnet_pytorch_amd.model import scaling
+    from gemnet_pytorch_amd.model.scaling import AutomaticFit
+    from gemnet_pytorch_amd.model.utils import write_json
+    from oracle import gemnet_oracle as GO
+    target = "QuadInteraction_1_sum_sbf" if args.quad else "TripInteraction_1_sum_cbf"
+    have = GO.load_scale_factors(os.path.join(ROOT, "gemnet_pytorch_amd", "scaling_factors.json"))
+    have.pop(target)
+    out = {"active_factor": target}
+    old = scaling.USE_FIT_STAT
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "scaling.json")
+        write_json(path, dict(comment="pbc_bench --fit", **have))
+        AutomaticFit.set2fitmode()
+        try:
+            model = make_model(args.cutoff, quad=args.quad, int_cutoff=args.int_cutoff, scale_file=path).to("cuda").eval()
+            model.periodic_scale_fitting = True
+            assert AutomaticFit.activeVar.name == target and not AutomaticFit.queue
+
+            def run(flag):
+                scaling.USE_FIT_STAT = flag
+                return model(per, stress=True)
+
+            for tag, flag in (("kernel", True), ("aten", False)):
+                run(flag)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                run(flag)
+                torch.cuda.synchronize()
+                out[f"fit_{tag}_peak_memory_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+            res = alternated({"fit_kernel": lambda: run(True), "fit_aten": lambda: run(False)}, args.steps, args.warmup)
+            for k, (med, rounds) in res.items():
+                out[f"{k}_ms"], out[f"{k}_rounds"] = med, rounds
+        finally:
+            scaling.USE_FIT_STAT = old
+            AutomaticFit.fitting_mode = False
+            AutomaticFit.reset()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=4)
@@ -491,6 +541,8 @@ def main():
     ap.add_argument("--quad", action="store_true", help="time GemNet-Q (periodic_quadruplets) on the box")
     ap.add_argument("--int-cutoff", type=float, default=5.0, help="--quad: the interaction cutoff (quadruplets ~ int_cutoff^3)")
     ap.add_argument("--eager-only", action="store_true", help="--direct / --train --quad: only eager direct-force calls / training steps (for a kernel trace)")
+    ap.add_argument("--fit", action="store_true", help="time one fit-mode forward (scale-factor fitting) with the kernel statistic "
+                    "against the ATen statistic; with --quad for GemNet-Q")
     args = ap.parse_args()
     import __graft_entry__ as ge
     ge.build()
@@ -509,6 +561,17 @@ def main():
     Zd = torch.tensor(Z, device="cuda").long()
     Nd = torch.tensor([A], device="cuda")
     celld = torch.tensor(cell[None], dtype=torch.float32, device="cuda")
+    if args.fit:
+        from gemnet_pytorch_amd.pbc import PeriodicQuadGraphBuilder
+        if args.quad:
+            idx = PeriodicQuadGraphBuilder([A], args.cutoff, args.int_cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
+            sizes = {"int_cutoff": args.int_cutoff, "quadruplets": int(idx["id4_reduce_ca"].shape[0])}
+        else:
+            idx = PeriodicGraphBuilder([A], args.cutoff, device="cuda")(Rd, celld, dtype=torch.int32)
+            sizes = {"triplets": int(idx["id3_reduce_ca"].shape[0])}
+        res = fit_times(dict(R=Rd, Z=Zd, N=Nd, cell=celld, **idx), args)
+        print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff, "edges": int(idx["id_a"].shape[0])}, **sizes, **res)))
+        return
     if args.quad:
         res = quad_train_times(Rd, Zd, Nd, celld, A, args) if args.train else quad_times(R, Rd, Zd, Nd, celld, A, args)
         print(json.dumps(dict({"atoms": A, "cutoff": args.cutoff}, **res)))
