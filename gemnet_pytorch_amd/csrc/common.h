@@ -15,6 +15,10 @@
     if (e__ != hipSuccess) return (int)e__;       \
   } while (0)
 
+// The clamp decision of the angle geometry is taken RELATIVE to the vectors' lengths: sin(angle) below this counts as the exact
+// degeneracy (collinear triplet, vanished rejection, planar quadruplet) — quad_math.h, geom_dual.h, geometry.hip; DESIGN.md 16
+#define GN_REL_SIN 1e-5f
+
 static inline int gn_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ScaledSiLU and its derivatives (reference: gemnet/model/layers/base_layers.py:51-58,

@@ -41,15 +41,20 @@ __device__ __forceinline__ V3<T> cross(const V3<T>& a, const V3<T>& b) {
 
 // First adjoint of theta(u, v) = atan2(max(|u x v|, 1e-9), u.v):  gu = g dtheta/du, gv = g dtheta/dv  (the clamp has a
 // zero gradient through y, gemnet.py:309: torch.max(y, 1e-9)).  Same formulas as trip_basis_bwd_kernel (geometry.hip).
-template <class T>
+// kRel (the position form, geometry2.hip): the clamp decision relative to the vectors, sin < GN_REL_SIN, as in geometry.hip —
+// off the axes the cross product of an exactly collinear triplet is a residue of 1e-7 |u| |v| whose direction is rounding
+// noise; y then enters as a constant.  The edge-vector twins (pbc_train.hip, pbc_quad_train.hip) keep the absolute decision.
+template <class T, bool kRel = false>
 __device__ __forceinline__ void angle_adjoint(const V3<T>& u, const V3<T>& v, const T g, V3<T>& gu, V3<T>& gv) {
   const T x = dot(u, v);
   const V3<T> w = cross(u, v);
-  const T yn = dsqrt(dot(w, w));
-  const bool clamped = val(yn) < 1e-9f;
+  const T w2 = dot(w, w);
+  const T yn = dsqrt(w2);
+  const bool clamped =
+      val(yn) < 1e-9f || (kRel && val(w2) <= (GN_REL_SIN * GN_REL_SIN) * val(dot(u, u)) * val(dot(v, v)));
   T y, zero;
   lift(zero, 0.f);
-  lift(y, 1e-9f);
+  lift(y, val(yn) < 1e-9f ? 1e-9f : val(yn));
   if (!clamped) y = yn;
   const T r2 = x * x + y * y;
   const T dx = -(y / r2) * g;

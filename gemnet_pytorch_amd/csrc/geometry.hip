@@ -95,9 +95,13 @@ __device__ __forceinline__ Ang angle_of(const float* __restrict__ R, int c, int 
   g.wx = g.uy * g.vz - g.uz * g.vy;
   g.wy = g.uz * g.vx - g.ux * g.vz;
   g.wz = g.ux * g.vy - g.uy * g.vx;
-  const float yn = sqrtf(g.wx * g.wx + g.wy * g.wy + g.wz * g.wz);
-  g.clamped = yn < 1e-9f;          // torch.max(y, 1e-9): gradient through y vanishes (gemnet.py:309)
-  g.y = g.clamped ? 1e-9f : yn;
+  const float w2 = g.wx * g.wx + g.wy * g.wy + g.wz * g.wz;
+  const float yn = sqrtf(w2);
+  g.y = yn < 1e-9f ? 1e-9f : yn;   // torch.max(y, 1e-9) ...
+  // ... whose gradient through y vanishes (gemnet.py:309).  The decision is taken relative to the vectors (GN_REL_SIN): off the
+  // axes the cross product of an exactly collinear triplet is a residue of 1e-7 |u| |v|, whose direction is rounding noise
+  const float u2 = g.ux * g.ux + g.uy * g.uy + g.uz * g.uz, v2 = g.vx * g.vx + g.vy * g.vy + g.vz * g.vz;
+  g.clamped = yn < 1e-9f || w2 <= (GN_REL_SIN * GN_REL_SIN) * u2 * v2;
   return g;
 }
 
@@ -255,7 +259,8 @@ __global__ __launch_bounds__(256) void quad_angles_bwd_kernel(const float4* __re
 // Tangent pass of the angle form (the double backward of quad_angles_bwd_kernel under trainer.py:346): for a position tangent
 // tR (A,3) — the cotangent dL/dF of the force — tang[q] = (dPhi_cab . tR, dTheta_cabd . tR, 0, 0): the directional derivatives
 // of the two angles, i.e. the gradient of  sum_q <G(q), tR>  w.r.t. the incoming g_ang.  Formed from the SAME closed-form
-// adjoints as the first-order kernel (unit cotangents), so first adjoint and tangent agree to rounding.
+// adjoints as the first-order kernel (unit cotangents) under the SAME decisions at the degeneracies (quad_math.h,
+// quad_angles_tan), so first adjoint and tangent agree to rounding — on a collinear or planar row both are zero.
 __global__ __launch_bounds__(256) void quad_angles_jvp_kernel(const float* __restrict__ R, const float* __restrict__ tR,
                                                               const int32_t* __restrict__ qc, const int32_t* __restrict__ qa,
                                                               const int32_t* __restrict__ qb, const int32_t* __restrict__ qd,
@@ -264,17 +269,10 @@ __global__ __launch_bounds__(256) void quad_angles_jvp_kernel(const float* __res
     const int64_t ia = qa[q], ib = qb[q], ic = qc[q], id = qd[q];
     const V3 Ra = v3(R + 3 * ia), Rb = v3(R + 3 * ib);
     const V3 uac = v3(R + 3 * ic) - Ra, uab = Rb - Ra, ubd = v3(R + 3 * id) - Rb;
-    const V3 uba = (-1.0f) * uab;
     const V3 ta = v3(tR + 3 * ia), tb = v3(tR + 3 * ib);
     const V3 dac = v3(tR + 3 * ic) - ta, dab = tb - ta, dbd = v3(tR + 3 * id) - tb;
-    const V3 p1 = reject(uac, uab), p2 = reject(ubd, uba);
-    V3 g_ab, g_ac, gp1, gp2, t1, t2, g_bd, g_ba;
-    angle_uv_bwd(uab, uac, 1.0f, g_ab, g_ac);
-    const float dphi = dot(g_ab, dab) + dot(g_ac, dac);
-    angle_uv_bwd(p1, p2, 1.0f, gp1, gp2);
-    reject_bwd(uac, uab, gp1, t1, t2);      // d p1 / d(uac, uab)
-    reject_bwd(ubd, uba, gp2, g_bd, g_ba);  // d p2 / d(ubd, uba);  d uba = -d uab
-    const float dth = dot(t1, dac) + dot(t2, dab) + dot(g_bd, dbd) - dot(g_ba, dab);
+    float dphi, dth;
+    quad_angles_tan(uac, uab, ubd, dac, dab, dbd, dphi, dth);
     tang[q] = make_float4(dphi, dth, 0.f, 0.f);
   }
 }

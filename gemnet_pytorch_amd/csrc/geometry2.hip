@@ -83,7 +83,7 @@ __global__ void angle_bwd_kernel(const float* __restrict__ g, const float* __res
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
     V3<float> u, v, gu, gv;
     load_uv(R, tc[t], ta[t], tb[t], u, v);
-    angle_adjoint<float>(u, v, g[t], gu, gv);
+    angle_adjoint<float, true>(u, v, g[t], gu, gv);
     Gc[3 * t] = gu.x; Gc[3 * t + 1] = gu.y; Gc[3 * t + 2] = gu.z;
     Gb[3 * t] = gv.x; Gb[3 * t + 1] = gv.y; Gb[3 * t + 2] = gv.z;
   }
@@ -102,11 +102,11 @@ __global__ void angle_jvp_kernel(const float* __restrict__ R, const float* __res
     const V3<Dual> Vv = {mk(v.x, dv.x), mk(v.y, dv.y), mk(v.z, dv.z)};
     V3<Dual> gu, gv;
     const float gt = g ? g[t] : 1.0f;
-    angle_adjoint<Dual>(U, Vv, mk(gt), gu, gv);
+    angle_adjoint<Dual, true>(U, Vv, mk(gt), gu, gv);
     if (thdot) {
       // value parts are g dtheta/d(u, v): the tangent of theta itself is their contraction with (du, dv) at g = 1
       V3<float> g1u, g1v;
-      angle_adjoint<float>(u, v, 1.0f, g1u, g1v);
+      angle_adjoint<float, true>(u, v, 1.0f, g1u, g1v);
       thdot[t] = dot(g1u, du) + dot(g1v, dv);
     }
     if (Hc) {

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void quad_basis_vec_fwd_kernel(const float* __
       V3 uac, uab, ubd;
       quad_vectors(V, Vint, ix, q, uac, uab, ubd);
       double sn, cs, s1, c1;
-      quad_angles_sc_rel(uac, uab, ubd, sn, cs, s1, c1);
+      quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
       ylm_row_sc(sn, cs, s1, c1, S, rows + threadIdx.x * SS);
     }
     __syncthreads();
@@ -103,11 +103,11 @@ __global__ __launch_bounds__(256) void quad_basis_vec_bwd_kernel(const float* __
       V3 uac, uab, ubd;
       quad_vectors(V, Vint, ix, q, uac, uab, ubd);
       double sn, cs, s1, c1;
-      quad_angles_sc_rel(uac, uab, ubd, sn, cs, s1, c1);
+      quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
       double g_first, g_second;   // d/d(polar angle = Phi_cab), d/d(azimuth = Theta_cabd)
       ylm_dot_grad_sc(sn, cs, s1, c1, S, rows + threadIdx.x * SS, g_first, g_second);
       V3 g_ac, g_ab, g_bd;
-      quad_angles_adj_rel(uac, uab, ubd, (float)g_first, (float)g_second, g_ac, g_ab, g_bd);
+      quad_angles_adj(uac, uab, ubd, (float)g_first, (float)g_second, g_ac, g_ab, g_bd);
       quad_store(Gc, Gbd, q, g_ac, g_ab, g_bd);
     }
     __syncthreads();
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void quad_angles_vec_fwd_kernel(const float* _
     V3 uac, uab, ubd;
     quad_vectors(V, Vint, ix, q, uac, uab, ubd);
     double sn, cs, s1, c1;
-    quad_angles_sc_rel(uac, uab, ubd, sn, cs, s1, c1);
+    quad_angles_sc(uac, uab, ubd, sn, cs, s1, c1);
     ang[q] = make_float4((float)sn, (float)cs, (float)s1, (float)c1);
   }
 }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void quad_angles_vec_bwd_kernel(const float4* 
     quad_vectors(V, Vint, ix, q, uac, uab, ubd);
     const float4 g = g_ang[q];
     V3 g_ac, g_ab, g_bd;
-    quad_angles_adj_rel(uac, uab, ubd, g.x, g.y, g_ac, g_ab, g_bd);
+    quad_angles_adj(uac, uab, ubd, g.x, g.y, g_ac, g_ab, g_bd);
     quad_store(Gc, Gbd, q, g_ac, g_ab, g_bd);
   }
 }

@@ -8,7 +8,7 @@
 //                        as value / first adjoint / tangent kernel: the two-array twins of gn_angle_vec_* (csrc/pbc_train.hip),
 //                        same arithmetic (the shared angle_adjoint<float> of geom_dual.h)
 //     quadruplet angles  value and first adjoint are gn_quad_angles_vec_fwd_f32 / _bwd_f32 (csrc/pbc_quad.hip), unchanged; the
-//                        tangent kernel here evaluates the SAME body as that first adjoint (quad_math.h, quad_angles_adj_t<true>)
+//                        tangent kernel here evaluates the SAME body as that first adjoint (quad_math.h, quad_angles_adj)
 //                        with unit cotangents and dots the result with the tangent vectors, so adjoint and tangent take identical
 //                        decisions at the degeneracies of a crystal: c - a - b collinear => dPhi = 0; a vanished rejection or a
 //                        planar quadruplet => dTheta = 0.
@@ -91,9 +91,9 @@ __global__ __launch_bounds__(256) void quad_angles_vec_jvp_kernel(const float* _
     const qm::V3 dac = tV ? neg3(tV + 3 * eca) : zero, dab = tVint ? neg3(tVint + 3 * k) : zero,
                  dbd = tV ? neg3(tV + 3 * edb) : zero;
     qm::V3 g_ac, g_ab, g_bd;
-    qm::quad_angles_adj_t<true>(uac, uab, ubd, 1.0f, 0.0f, g_ac, g_ab, g_bd);
+    qm::quad_angles_adj(uac, uab, ubd, 1.0f, 0.0f, g_ac, g_ab, g_bd);
     const float dphi = qm::dot(g_ac, dac) + qm::dot(g_ab, dab) + qm::dot(g_bd, dbd);
-    qm::quad_angles_adj_t<true>(uac, uab, ubd, 0.0f, 1.0f, g_ac, g_ab, g_bd);
+    qm::quad_angles_adj(uac, uab, ubd, 0.0f, 1.0f, g_ac, g_ab, g_bd);
     const float dth = qm::dot(g_ac, dac) + qm::dot(g_ab, dab) + qm::dot(g_bd, dbd);
     tang[q] = make_float4(dphi, dth, 0.f, 0.f);
   }

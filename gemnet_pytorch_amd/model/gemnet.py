@@ -195,42 +195,17 @@ class GemNet(torch.nn.Module):
         R_ab = ops.gather_rows(R, plan.t_b) - Ra
         return GemNet.calculate_neighbor_angles(R_ac, R_ab)
 
-    @staticmethod
-    def calculate_angles(R, plan):
-        """Quadruplet angles (gemnet.py:334-418): Phi_cab (Q,), Phi_abd (I,), Theta_cabd (Q,)."""
-        q = plan.quad_geom
-        Ra = ops.gather_rows(R, q["a_of_exp"])
-        Rb = ops.gather_rows(R, q["b_of_exp"])
-        Rd = ops.gather_rows(R, q["d_of_exp"])
-        R_ba, R_bd = Ra - Rb, Rd - Rb
-        angle_abd = GemNet.calculate_neighbor_angles(R_ba, R_bd)
-        R_bd_proj = ops.gather_rows(GemNet.vector_rejection(R_bd, R_ba), plan.quad.expand)
-
-        Rc = ops.gather_rows(R, q["c_of_red"])
-        Ra2 = ops.gather_rows(R, q["a_of_red"])
-        Rb2 = ops.gather_rows(R, q["b_of_red"])
-        R_ac, R_ab = Rc - Ra2, Rb2 - Ra2
-        angle_cab = ops.gather_rows(GemNet.calculate_neighbor_angles(R_ab, R_ac)[:, None], q["reduce_cab"])[:, 0]
-        R_ac_proj = ops.gather_rows(GemNet.vector_rejection(R_ac, R_ab), q["reduce_cab"])
-        angle_cabd = GemNet.calculate_neighbor_angles(R_ac_proj, R_bd_proj)
-        return angle_cab, angle_abd, angle_cabd
-
     REL_SIN2 = 1e-10        # kRelSin^2 of csrc/quad_math.h
 
     @staticmethod
-    def calculate_angles_vec(V, Vint, plan):
-        """`calculate_angles` of a periodic batch on the edge vectors V (E,3) and the interaction-edge vectors Vint (n_int,3), in
-        ATen and differentiable to any order: Phi_cab (Q,), Phi_abd (I,), Theta_cabd (Q,) from uac = -V[ca], uab = -Vint[k],
-        ubd = -V[db] per quadruplet and u = Vint[k], v = -V[db] per intermediate triplet (csrc/pbc_quad.hip).  The clamp
-        decisions of the two quadruplet angles are those of csrc/quad_math.h, relative to the vectors' lengths and taken on
-        detached values: c - a - b collinear => Phi_cab is a constant; a vanished rejection => Theta_cabd = pi / 2, a constant;
-        a planar quadruplet => Theta_cabd (0 or pi) is a constant."""
+    def quad_angles_of_vectors(uac, uab, ubd):
+        """Phi_cab, Theta_cabd (Q,) of the quadruplets c -> a - b <- d from uac = c - a, uab = b - a, ubd = d - b (Q,3), in ATen
+        and differentiable to any order — the composite closure of molecules (`calculate_angles`) and of periodic batches
+        (`calculate_angles_vec`).  The clamp decisions are those of csrc/quad_math.h, relative to the vectors' lengths and taken
+        on detached values: c - a - b collinear => Phi_cab is a constant; a vanished rejection => Theta_cabd = pi / 2, a
+        constant; a planar quadruplet => Theta_cabd (0 or pi) is a constant."""
         rel2 = GemNet.REL_SIN2
         sq = lambda x: torch.sum(x * x, dim=-1)       # noqa: E731
-        angle_abd = GemNet.calculate_neighbor_angles(ops.gather_rows(Vint, plan.intm_ab), -ops.gather_rows(V, plan.intm_db))
-        uac = -ops.gather_rows(V, plan.quad.reduce)
-        uab = -ops.gather_rows(ops.gather_rows(Vint, plan.intm_ab), plan.quad.expand)
-        ubd = -ops.gather_rows(ops.gather_rows(V, plan.intm_db), plan.quad.expand)
         with torch.no_grad():
             p1, p2 = GemNet.vector_rejection(uac, uab), GemNet.vector_rejection(ubd, -uab)
             parallel = lambda u, v: sq(torch.linalg.cross(u, v, dim=-1)) <= rel2 * sq(u) * sq(v)       # noqa: E731
@@ -243,6 +218,39 @@ class GemNet(torch.nn.Module):
         tac, tab, tbd = (torch.where(fixed, x.detach(), x) for x in (uac, uab, ubd))
         angle_cabd = GemNet.calculate_neighbor_angles(GemNet.vector_rejection(tac, tab), GemNet.vector_rejection(tbd, -tab))
         angle_cabd = torch.where(vanished, torch.full_like(angle_cabd, math.pi / 2), angle_cabd)
+        return angle_cab, angle_cabd
+
+    @staticmethod
+    def calculate_angles(R, plan):
+        """Quadruplet angles (gemnet.py:334-418): Phi_cab (Q,), Phi_abd (I,), Theta_cabd (Q,).  The vectors are formed per
+        intermediate triplet, as the reference forms them, and gathered to the quadruplets, where the two quadruplet angles
+        take the decisions of `quad_angles_of_vectors` (an exactly planar or linear molecule in general orientation)."""
+        q = plan.quad_geom
+        Ra = ops.gather_rows(R, q["a_of_exp"])
+        Rb = ops.gather_rows(R, q["b_of_exp"])
+        Rd = ops.gather_rows(R, q["d_of_exp"])
+        R_ba, R_bd = Ra - Rb, Rd - Rb
+        angle_abd = GemNet.calculate_neighbor_angles(R_ba, R_bd)
+
+        Rc = ops.gather_rows(R, q["c_of_red"])
+        Ra2 = ops.gather_rows(R, q["a_of_red"])
+        Rb2 = ops.gather_rows(R, q["b_of_red"])
+        R_ac, R_ab = Rc - Ra2, Rb2 - Ra2
+        angle_cab, angle_cabd = GemNet.quad_angles_of_vectors(ops.gather_rows(R_ac, q["reduce_cab"]),
+                                                              ops.gather_rows(R_ab, q["reduce_cab"]),
+                                                              ops.gather_rows(R_bd, plan.quad.expand))
+        return angle_cab, angle_abd, angle_cabd
+
+    @staticmethod
+    def calculate_angles_vec(V, Vint, plan):
+        """`calculate_angles` of a periodic batch on the edge vectors V (E,3) and the interaction-edge vectors Vint (n_int,3):
+        Phi_cab (Q,), Phi_abd (I,), Theta_cabd (Q,) from uac = -V[ca], uab = -Vint[k], ubd = -V[db] per quadruplet and
+        u = Vint[k], v = -V[db] per intermediate triplet (csrc/pbc_quad.hip)."""
+        angle_abd = GemNet.calculate_neighbor_angles(ops.gather_rows(Vint, plan.intm_ab), -ops.gather_rows(V, plan.intm_db))
+        uac = -ops.gather_rows(V, plan.quad.reduce)
+        uab = -ops.gather_rows(ops.gather_rows(Vint, plan.intm_ab), plan.quad.expand)
+        ubd = -ops.gather_rows(ops.gather_rows(V, plan.intm_db), plan.quad.expand)
+        angle_cab, angle_cabd = GemNet.quad_angles_of_vectors(uac, uab, ubd)
         return angle_cab, angle_abd, angle_cabd
 
     # ---------------------------------------------------------------------------------- forward

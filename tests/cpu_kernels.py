@@ -7,6 +7,7 @@ kernel semantics documented in include/gemnet_hip.h.  It is not importable from 
 package and is never used when a GPU is present (the -m gpu tests call the real library).
 """
 import contextlib
+import math
 
 import torch
 
@@ -209,11 +210,7 @@ def edge_basis_bwd(gD, g_rbf, g_rad, R, idx_c, idx_a, freq, z, nrm, cutoff, p):
 
 
 def _angle(R, tc, ta, tb):
-    u = R[tc.long()] - R[ta.long()]
-    v = R[tb.long()] - R[ta.long()]
-    x = (u * v).sum(1)
-    y = torch.linalg.cross(u, v, dim=-1).norm(dim=-1).clamp(min=1e-9)
-    return torch.atan2(y, x)
+    return _angle_uv_rel(R[tc.long()] - R[ta.long()], R[tb.long()] - R[ta.long()])
 
 
 def trip_basis_fwd(R, tc, ta, tb, S, want_theta=False):
@@ -226,10 +223,7 @@ def trip_basis_bwd(gY, R, tc, ta, tb):
         Rc = R[tc.long()].detach().clone().requires_grad_(True)
         Ra = R[ta.long()].detach()
         Rb = R[tb.long()].detach().clone().requires_grad_(True)
-        u, v = Rc - Ra, Rb - Ra
-        x = (u * v).sum(1)
-        y = torch.linalg.cross(u, v, dim=-1).norm(dim=-1).clamp(min=1e-9)
-        Y = B.real_sph_harm_l0(gY.shape[1], torch.atan2(y, x))
+        Y = B.real_sph_harm_l0(gY.shape[1], _angle_uv_rel(Rc - Ra, Rb - Ra))
         Gc, Gb = torch.autograd.grad((gY * Y).sum(), (Rc, Rb))
     return Gc, Gb
 
@@ -381,8 +375,7 @@ def bil_dy_multi(dSm_list, x_list, sp, ang=None):
 
 
 def quad_angles_fwd(R, qc, qa, qb, qd):
-    phi, th = _quad_angles(R[qc.long()], R[qa.long()], R[qb.long()], R[qd.long()])
-    return torch.stack([torch.sin(phi), torch.cos(phi), torch.sin(th), torch.cos(th)], dim=1)
+    return angle_form(*_quad_angles_rel(R[qc.long()], R[qa.long()], R[qb.long()], R[qd.long()]))
 
 
 def quad_angles_bwd(g_ang, R, qc, qa, qb, qd, packed=False):
@@ -391,8 +384,8 @@ def quad_angles_bwd(g_ang, R, qc, qa, qb, qd, packed=False):
         Rb = R[qb.long()].detach().clone().requires_grad_(True)
         Rd = R[qd.long()].detach().clone().requires_grad_(True)
         Ra = R[qa.long()].detach()
-        phi, th = _quad_angles(Rc, Ra, Rb, Rd)
-        Gc, Gb, Gd = torch.autograd.grad((g_ang[:, 0] * phi + g_ang[:, 1] * th).sum(), (Rc, Rb, Rd))
+        phi, th = _quad_angles_rel(Rc, Ra, Rb, Rd)
+        Gc, Gb, Gd = _grad0((g_ang[:, 0] * phi + g_ang[:, 1] * th).sum(), (Rc, Rb, Rd))
     if not packed:
         return Gc, Gb, Gd
     Gbd = torch.zeros((Gb.shape[0], 8), dtype=Gb.dtype)
@@ -421,7 +414,7 @@ def _ang_to_dY(ang, tang):
 
 def quad_angles_jvp(R, tR, qc, qa, qb, qd):
     idx = [i.long() for i in (qc, qa, qb, qd)]
-    t = _jvp(lambda Rx: torch.stack(_quad_angles(Rx[idx[0]], Rx[idx[1]], Rx[idx[2]], Rx[idx[3]]), dim=1), R, tR)
+    t = _jvp(lambda Rx: torch.stack(_quad_angles_rel(Rx[idx[0]], Rx[idx[1]], Rx[idx[2]], Rx[idx[3]]), dim=1), R, tR)
     out = torch.zeros((t.shape[0], 4), dtype=R.dtype)
     out[:, 0:2] = t
     return out
@@ -494,8 +487,58 @@ def _quad_angles(Rc, Ra, Rb, Rd):
     return ang(uab, uac), ang(rej(uac, uab), rej(ubd, -uab))
 
 
+REL_SIN2 = 1e-10        # kRelSin^2 of csrc/quad_math.h
+
+
+def _sq(x):
+    return (x * x).sum(-1)
+
+
+def _rej(x, n):
+    return x - ((x * n).sum(-1) / _sq(n))[:, None] * n
+
+
+def quad_decisions(uac, uab, ubd):
+    """The three relative tests of csrc/quad_math.h -> (flat: c - a - b collinear; vanished: a rejection has vanished; fixed:
+    vanished, or the quadruplet is planar — the azimuth sits on its clamp)."""
+    par = lambda u, v: _sq(torch.linalg.cross(u, v, dim=-1)) <= REL_SIN2 * _sq(u) * _sq(v)       # noqa: E731
+    p1, p2 = _rej(uac, uab), _rej(ubd, -uab)
+    vanished = (_sq(p1) <= REL_SIN2 * _sq(uac)) | (_sq(p2) <= REL_SIN2 * _sq(ubd))
+    return par(uab, uac), vanished, vanished | par(p1, p2)
+
+
+def quad_angles_rel(uac, uab, ubd):
+    """(Phi_cab, Theta_cabd) with the decisions of quad_math.h: on a `flat` row Phi is a constant, on a `fixed` row Theta is
+    (pi / 2 where a rejection vanished).  What the kernels compute, for molecules and crystals alike; `_quad_angles` above is
+    the reference's formula, which agrees wherever no decision is taken."""
+    flat, vanished, fixed = (m.detach() for m in quad_decisions(uac.detach(), uab.detach(), ubd.detach()))
+    w = lambda m, x: torch.where(m[:, None], x.detach(), x)       # noqa: E731
+    phi = _angle_uv(w(flat, uab), w(flat, uac))
+    tac, tab, tbd = w(fixed, uac), w(fixed, uab), w(fixed, ubd)
+    th = _angle_uv(_rej(tac, tab), _rej(tbd, -tab))
+    return phi, torch.where(vanished, torch.full_like(th, math.pi / 2), th)
+
+
+def angle_form(phi, th):
+    """(sin, cos) of the two angles; the convention rows (Theta = pi / 2 exactly) are (1, 0) exactly, as the kernels write them."""
+    conv = th == math.pi / 2
+    return torch.stack([torch.sin(phi), torch.cos(phi), torch.where(conv, torch.ones_like(th), torch.sin(th)),
+                        torch.where(conv, torch.zeros_like(th), torch.cos(th))], dim=1)
+
+
+def _quad_angles_rel(Rc, Ra, Rb, Rd):
+    return quad_angles_rel(Rc - Ra, Rb - Ra, Rd - Rb)
+
+
+def _grad0(y, xs):
+    """autograd.grad with zeros for the inputs a row's decisions cut off from the result."""
+    if not y.requires_grad:
+        return tuple(torch.zeros_like(x) for x in xs)
+    return tuple(torch.zeros_like(x) if g is None else g for x, g in zip(xs, torch.autograd.grad(y, xs, allow_unused=True)))
+
+
 def quad_basis_fwd(R, qc, qa, qb, qd, S):
-    phi, th = _quad_angles(R[qc.long()], R[qa.long()], R[qb.long()], R[qd.long()])
+    phi, th = _quad_angles_rel(R[qc.long()], R[qa.long()], R[qb.long()], R[qd.long()])
     return B.real_sph_harm_full(S, phi, th)
 
 
@@ -505,8 +548,8 @@ def quad_basis_bwd(gY, R, qc, qa, qb, qd, S):
         Rb = R[qb.long()].detach().clone().requires_grad_(True)
         Rd = R[qd.long()].detach().clone().requires_grad_(True)
         Ra = R[qa.long()].detach()
-        phi, th = _quad_angles(Rc, Ra, Rb, Rd)
-        Gc, Gb, Gd = torch.autograd.grad((gY * B.real_sph_harm_full(S, phi, th)).sum(), (Rc, Rb, Rd))
+        phi, th = _quad_angles_rel(Rc, Ra, Rb, Rd)
+        Gc, Gb, Gd = _grad0((gY * B.real_sph_harm_full(S, phi, th)).sum(), (Rc, Rb, Rd))
     return Gc, Gb, Gd
 
 
@@ -525,6 +568,16 @@ def bil_fused_fwd(Y, x, B, W2T, sp, alpha=1.0, W2T_planes=None):
 def _angle_uv(u, v):
     x = (u * v).sum(1)
     y = torch.linalg.cross(u, v, dim=-1).norm(dim=-1).clamp(min=1e-9)
+    return torch.atan2(y, x)
+
+
+def _angle_uv_rel(u, v):
+    """`_angle_uv` as the molecular triplet kernels differentiate it (geometry.hip, geometry2.hip): the clamp decision relative
+    to the vectors — below sin = 1e-5 no gradient passes through |u x v|, which enters as a constant."""
+    x = (u * v).sum(1)
+    rel = (_sq(torch.linalg.cross(u, v, dim=-1)) <= REL_SIN2 * _sq(u) * _sq(v)).detach()[:, None]
+    # (detached vectors, not a detached norm: the norm of an exactly vanishing cross product has no finite derivative)
+    y = torch.linalg.cross(torch.where(rel, u.detach(), u), torch.where(rel, v.detach(), v), dim=-1).norm(dim=-1).clamp(min=1e-9)
     return torch.atan2(y, x)
 
 
@@ -552,7 +605,7 @@ def dist_jvp(R, tR, gD, id_c, id_a, want_D=True, want_H=True):
 
 def angle_fwd(R, tc, ta, tb):
     Ra = R[ta.long()]
-    return _angle_uv(R[tc.long()] - Ra, R[tb.long()] - Ra)
+    return _angle_uv_rel(R[tc.long()] - Ra, R[tb.long()] - Ra)
 
 
 def angle_bwd(g, R, tc, ta, tb):
@@ -560,7 +613,7 @@ def angle_bwd(g, R, tc, ta, tb):
         Ra = R[ta.long()]
         u = (R[tc.long()] - Ra).detach().clone().requires_grad_(True)
         v = (R[tb.long()] - Ra).detach().clone().requires_grad_(True)
-        Gc, Gb = torch.autograd.grad(_angle_uv(u, v), (u, v), g)
+        Gc, Gb = torch.autograd.grad(_angle_uv_rel(u, v), (u, v), g)
     return Gc, Gb
 
 
@@ -571,7 +624,7 @@ def angle_jvp(R, tR, g, tc, ta, tb, want_theta=True, want_H=True):
         v = (R[tb.long()] - Ra).detach().clone().requires_grad_(True)
         du, dv = (tR[tc.long()] - tRa).detach(), (tR[tb.long()] - tRa).detach()
         gg = (torch.ones(u.shape[0], dtype=R.dtype) if g is None else g.detach().clone()).requires_grad_(True)
-        Gu, Gv = torch.autograd.grad(_angle_uv(u, v), (u, v), gg, create_graph=True)
+        Gu, Gv = torch.autograd.grad(_angle_uv_rel(u, v), (u, v), gg, create_graph=True)
         s = (Gu * du).sum() + (Gv * dv).sum()
         thd, Hc, Hb = torch.autograd.grad(s, (gg, u, v))
     return (thd if want_theta else None), (Hc if want_H else None), (Hb if want_H else None)

@@ -9,7 +9,6 @@ condition (a property of the oracle), with E_b the cluster energy of `pbc_q_comm
 arrays of IO.build_indices(..., cutoff, int_cutoff, False))."""
 import contextlib
 import glob
-import math
 import os
 
 import numpy as np
@@ -195,44 +194,17 @@ def angle_vec2_jvp(U, iu, W, iw, tU, tW):
     return out
 
 
-REL_SIN2 = 1e-10        # kRelSin^2 of csrc/quad_math.h
-
-
-def _sq(x):
-    return (x * x).sum(-1)
-
-
-def _rej(x, n):
-    return x - ((x * n).sum(-1) / _sq(n))[:, None] * n
-
-
-def quad_decisions(uac, uab, ubd):
-    """The three relative tests of csrc/quad_math.h -> (flat: c - a - b collinear; vanished: a rejection has vanished; fixed:
-    vanished, or the quadruplet is planar — the azimuth sits on its clamp)."""
-    par = lambda u, v: _sq(torch.linalg.cross(u, v, dim=-1)) <= REL_SIN2 * _sq(u) * _sq(v)       # noqa: E731
-    p1, p2 = _rej(uac, uab), _rej(ubd, -uab)
-    vanished = (_sq(p1) <= REL_SIN2 * _sq(uac)) | (_sq(p2) <= REL_SIN2 * _sq(ubd))
-    return par(uab, uac), vanished, vanished | par(p1, p2)
+# the relative clamp decisions of csrc/quad_math.h: stated once, in tests/cpu_kernels.py (the molecular launchers take them too)
+REL_SIN2, _sq, _rej = cpu_kernels.REL_SIN2, cpu_kernels._sq, cpu_kernels._rej
+quad_decisions, quad_angles_rel = cpu_kernels.quad_decisions, cpu_kernels.quad_angles_rel
 
 
 def quad_vectors(V, Vint, q_ca, q_db, q_abd, intm_ab):
     return -V[q_ca.long()], -Vint[intm_ab.long()[q_abd.long()]], -V[q_db.long()]
 
 
-def quad_angles_rel(uac, uab, ubd):
-    """(Phi_cab, Theta_cabd) with the decisions of quad_math.h<kRel = true>: on a `flat` row Phi is a constant, on a `fixed` row
-    Theta is (pi / 2 where a rejection vanished)."""
-    flat, vanished, fixed = (m.detach() for m in quad_decisions(uac.detach(), uab.detach(), ubd.detach()))
-    w = lambda m, x: torch.where(m[:, None], x.detach(), x)       # noqa: E731
-    phi = cpu_kernels._angle_uv(w(flat, uab), w(flat, uac))
-    tac, tab, tbd = w(fixed, uac), w(fixed, uab), w(fixed, ubd)
-    th = cpu_kernels._angle_uv(_rej(tac, tab), _rej(tbd, -tab))
-    return phi, torch.where(vanished, torch.full_like(th, math.pi / 2), th)
-
-
 def quad_angles_vec_fwd_k(V, Vint, q_ca, q_db, q_abd, intm_ab):
-    phi, th = quad_angles_rel(*quad_vectors(V, Vint, q_ca, q_db, q_abd, intm_ab))
-    return torch.stack([torch.sin(phi), torch.cos(phi), torch.sin(th), torch.cos(th)], dim=1)
+    return cpu_kernels.angle_form(*quad_angles_rel(*quad_vectors(V, Vint, q_ca, q_db, q_abd, intm_ab)))
 
 
 def quad_angles_vec_bwd_k(g_ang, V, Vint, q_ca, q_db, q_abd, intm_ab):
