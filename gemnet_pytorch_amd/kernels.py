@@ -14,7 +14,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (GN_ANG_F16, GN_CHAIN_MAX_OPS, GN_CHAIN_ROW, GN_SPLIT_F16X2_ROW, GemmArgs, addr, check, ptr,
+from ._lib import (GN_ANG_F16, GN_CHAIN_MAX_GROUPS, GN_CHAIN_MAX_OPS, GN_CHAIN_ROW, GN_SPLIT_F16X2_ROW, GemmArgs, addr, check, ptr,
                    require_device, stream)
 
 
@@ -1662,7 +1662,12 @@ def atom_stack_match(prog, mode=None):
          the LDS residual (. + slot 1) * s];  on the last of them the stack's output and (L > 0) the optional global skip
          (. + res2) * beta2;  T in {0, 1, 2} tail GEMMs 1 -> their own output
     at width 128 -> 128, 1 <= M <= 4 096, mode "h3" in the tall layout.  -> dict(x, W [ops], z, s, res2, beta2, y, t) or None
-    (gathered adds, parked or intermediate skips, a residual of the Dense, other widths / modes: not this kernel)."""
+    (gathered adds, parked or intermediate skips, a residual of the Dense, other widths / modes: not this kernel).  A program
+    does not say whether it is group 0 of a grouped launch: `chain` asks this matcher for single launches only."""
+    return _atom_fwd_match(prog, mode)
+
+
+def _atom_fwd_match(prog, mode):
     M, ops = prog.M, prog.ops
     if not (1 <= M <= ATOM_STACK_MAX_ROWS) or (mode or current_mode()) != "h3" or CHAIN_LAYOUT != "tall":
         return None
@@ -1759,6 +1764,14 @@ def _atom_adj_scale(o, dst, M, Z=False, out=False):
             and (_atom_mat(o["out"], M) if out else o["out"] is None))
 
 
+def _atom_seed(seed, M):
+    """(g_E (M,1), w_out (G,128)): the operands of a LOAD that forms the energy head's adjoint itself (grouped launch only)."""
+    return (isinstance(seed, tuple) and len(seed) == 2 and all(torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()
+                                                              for t in seed)
+            and tuple(seed[0].shape) == (M, 1) and seed[1].dim() == 2 and seed[1].shape[1] == ATOM_STACK_WIDTH
+            and seed[1].data_ptr() % 16 == 0)
+
+
 def atom_stack_adjoint_match(prog, mode=None):
     """Is `prog` the FUSED first-order adjoint of an atom-row stack in a form csrc/atom_stack.hip runs?  With G = slot 0, X = slot 1:
          T = 2:  LOAD g -> G;  LOAD gt1 -> X, GEMM (. + G) * beta -> G;  LOAD gt2 -> X, GEMM (. + G) * beta -> G
@@ -1767,7 +1780,13 @@ def atom_stack_adjoint_match(prog, mode=None):
                  form 1: LOAD g -> G, SCALE G *= a with output g_skip, SCALE G *= a, SCALE X = G * Z
          L in {1, 2} times [GEMM X -> X times a stored factor;  GEMM (. + G) * beta -> G, second output X = G * Z];  GEMM X -> gx
     at width 128 -> 128, 1 <= M <= 4 096, mode "h3", tall layout, factors stored as ssilu'(z).  -> the operands of
-    gn_atom_stack_bwd_f32, or None (running sums, parked skips, gathered adds, dz0 outputs, one tail, training sweeps: the chain launch)."""
+    gn_atom_stack_bwd_f32, or None (running sums, parked skips, gathered adds, dz0 outputs, one tail, training sweeps, a LOAD
+    that carries a `seed`: the chain launch).  Like atom_stack_match, `chain` asks it for single launches only."""
+    return _atom_adjoint_match(prog, mode)
+
+
+def _atom_adjoint_match(prog, mode, seeded=False):
+    """seeded (the grouped matcher only): the T = 0 form 0 LOAD may carry `seed` = (g_E, w_out) in place of a cotangent tensor."""
     M, ops = prog.M, prog.ops
     if not (1 <= M <= ATOM_STACK_MAX_ROWS) or (mode or current_mode()) != "h3" or CHAIN_LAYOUT != "tall":
         return None
@@ -1776,7 +1795,7 @@ def atom_stack_adjoint_match(prog, mode=None):
 
     def plain_load(o, slot):
         return (o["kind"] == "load" and o["slot"] == slot and o["rows"] is None and o.get("add2") is None and _atom_mat(o["src"], M)
-                and o.get("alpha", 1.0) == 1.0 and o.get("y2", -1) < 0 and o.get("Z2") is None)
+                and o.get("alpha", 1.0) == 1.0 and o.get("y2", -1) < 0 and o.get("Z2") is None and o.get("seed") is None)
     o = ops[0]
     m = dict(g=None, gt=[], gemms=[], F=[], form=0, alpha0=1.0, a_out=1.0, a_s=1.0, bt=[1.0, 1.0], bl=[1.0, 1.0], g_skip=None, gx=None)
     i = 1
@@ -1803,13 +1822,14 @@ def atom_stack_adjoint_match(prog, mode=None):
             i = 4
         else:
             return None
-    elif (o["kind"] == "load" and o["slot"] == 0 and o["rows"] is None and o.get("add2") is None and _atom_mat(o["src"], M)
+    elif (o["kind"] == "load" and o["slot"] == 0 and o["rows"] is None and o.get("add2") is None
+          and (_atom_mat(o["src"], M) if o.get("seed") is None else seeded and _atom_seed(o["seed"], M))
           and o.get("y2", -1) == 1 and o.get("alpha2", 1.0) == 1.0 and o.get("mode2", 0) == 1 and _atom_mat(o.get("Z2"), M)):
         m["alpha0"] = o.get("alpha", 1.0)
         m["F"].append(o["Z2"])
     else:
         return None
-    m["g"] = o["src"]
+    m["g"], m["seed"] = o["src"], o.get("seed")
     main = ops[i:]
     L = (len(main) - 1) // 2
     if len(main) not in (3, 5):
@@ -1854,6 +1874,80 @@ def _atom_stack_bwd(M, m):
           "gn_atom_stack_bwd_f32")
 
 
+# The stage of the grouped OutputBlocks (ops._OutputGroup: G stacks of Dense + ResidualLayers on A atom rows each, and their
+# adjoint) on grouped launches of the same two kernels, bit-identical to gn_chain_split_grouped_f32; the
+# adjoint forms the energy head's seed in its LOAD.  A switch of its own, independent of the two above.
+USE_ATOM_STACK_GROUPED = os.environ.get("GEMNET_OUT_GROUP_ATOMS", "1") == "1"
+ATOM_STACK_PLANE_BYTES = 8 * 4 * 2 * 64 * 16      # one packed 128 x 128 weight of format "h3"
+
+
+def _atom_slabs(t, M, groups, group_pitch):
+    """Is `t` (group 0's slab) followed, in its own storage, by the slabs of the other groups?"""
+    need = (t.storage_offset() + ((groups - 1) * group_pitch + M) * ATOM_STACK_WIDTH) * t.element_size()
+    return need <= t.untyped_storage().nbytes()
+
+
+def atom_stack_grouped_match(prog, groups, group_pitch, mode=None):
+    """Is the grouped launch `chain(prog, groups=, group_pitch=)` the forward or the fused adjoint of the grouped output-block stage in
+    the form csrc/atom_stack.hip runs?  The program of group 0 must be one atom_stack_match / atom_stack_adjoint_match accept, with
+         forward: L in {1, 2}, no tails, no skip (an activation on the Dense: every form of the kernel has one)
+         adjoint: L in {1, 2}, T = 0, form 0 — LOAD g * alpha -> G with the second tensor X = G * Z; the LOAD's cotangent is a tensor
+                  or `seed` = (g_E (M,1), w_out (G,128)) (ops._OutputGroup.backward)
+    1 <= G <= 8, group_pitch >= M, every `packed` the (G, 65 536) stacked planes of pack_weight_split_stacked in format "h3", every row
+    operand followed by the other groups' slabs.  -> ("fwd" | "bwd", operands) or None (the grouped chain launch)."""
+    M = prog.M
+    if not (1 <= groups <= GN_CHAIN_MAX_GROUPS and group_pitch >= M >= 1):
+        return None
+    m, kind = _atom_fwd_match(prog, mode), "fwd"
+    if m is not None:
+        if m["L"] < 1 or m["t"] or m["res2"] is not None:
+            return None
+        rows = [m["x"], m["y"], *m["z"]]
+    else:
+        m, kind = _atom_adjoint_match(prog, mode, seeded=True), "bwd"
+        if m is None or m["form"] != 0 or m["gt"] or m["g_skip"] is not None:
+            return None
+        if m["seed"] is not None and m["seed"][1].shape[0] != groups:
+            return None
+        rows = [m["gx"], *m["F"]] + ([m["g"]] if m["seed"] is None else [])
+    for g in m["gemms"]:
+        Wp = g.get("packed")
+        if not (torch.is_tensor(Wp) and tuple(Wp.shape) == (groups, ATOM_STACK_PLANE_BYTES) and Wp.is_contiguous()
+                and Wp.data_ptr() % 16 == 0 and getattr(Wp, "_gn_fmt", 0) == SPLIT_FORMAT["h3"]):
+            return None
+    if not all(_atom_slabs(t, M, groups, group_pitch) for t in rows):
+        return None
+    return kind, m
+
+
+def _atom_stack_grouped(M, groups, group_pitch, kind, m):
+    """Launch gn_atom_stack_fwd_grouped_f32 / gn_atom_stack_bwd_grouped_f32 for a matched program (atom_stack_grouped_match)."""
+    arr = ctypes.c_void_p
+    Ws = [g["packed"] for g in m["gemms"]]
+    span = ((int(groups) - 1) * int(group_pitch) + int(M)) * ATOM_STACK_WIDTH * 4
+    if kind == "fwd":
+        reads, writes = [m["x"]], [m["y"], *m["z"]]
+    else:
+        reads, writes = [*m["F"]] + ([m["g"]] if m["seed"] is None else []), [m["gx"]]
+    require_device(*reads, *writes, *Ws, *(m.get("seed") or ()))
+    if _lib.TRACE is not None:
+        # the arguments name group 0's slab of every row operand; the launch touches all of them (hbcheck.py)
+        _lib.note(reads=[(t.data_ptr(), span) for t in reads], writes=[(t.data_ptr(), span) for t in writes])
+    W_arr = (arr * len(Ws))(*[addr(W) for W in Ws])
+    if kind == "fwd":
+        z = m["z"]
+        check(_lib.load().gn_atom_stack_fwd_grouped_f32(ptr(m["x"]), int(M), int(groups), int(group_pitch), int(m["L"]), W_arr,
+                                                        (arr * len(z))(*[addr(a) for a in z]), float(m["s"]), ptr(m["y"]), stream()),
+              "gn_atom_stack_fwd_grouped_f32")
+        return
+    F, seed = m["F"], m["seed"] or (None, None)
+    check(_lib.load().gn_atom_stack_bwd_grouped_f32(ptr(m["g"]) if m["seed"] is None else None, ptr(seed[0]), ptr(seed[1]), int(M),
+                                                    int(groups), int(group_pitch), int(m["L"]), W_arr,
+                                                    (arr * len(F))(*[addr(a) for a in F]), float(m["alpha0"]), float(m["bl"][0]),
+                                                    float(m["bl"][1]), ptr(m["gx"]), stream()),
+          "gn_atom_stack_bwd_grouped_f32")
+
+
 def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
     """Run a ChainProgram (one launch).
     groups > 0 (gn_chain_split_grouped_f32): `prog` describes group 0 — M rows, operands = the first slab of stacked tensors
@@ -1871,6 +1965,13 @@ def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
         m = atom_stack_adjoint_match(prog, mode)
         if m is not None:
             return _atom_stack_bwd(prog.M, m)
+    if USE_ATOM_STACK_GROUPED and groups and tile_rows is None and prog.M <= ATOM_STACK_MAX_ROWS:     # (a tile height asks for the chain kernel)
+        m = atom_stack_grouped_match(prog, groups, group_pitch, mode)
+        if m is not None:
+            return _atom_stack_grouped(prog.M, groups, group_pitch, *m)
+    if any(o["kind"] == "load" and o.get("seed") is not None for o in ops):
+        raise RuntimeError("chain: a LOAD that forms its rows from `seed` exists on the grouped atom-row kernel only "
+                           "(kernels.atom_stack_grouped_match refused this program, a tile height was asked for, or GEMNET_OUT_GROUP_ATOMS=0)")
     nprod = CHAIN_MODES[mode]
     if nprod and not chain_split_supported(prog):
         nprod = 0

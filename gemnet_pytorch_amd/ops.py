@@ -1605,11 +1605,14 @@ class _OutputGroup(torch.autograd.Function):
             zs = [None] + zs
         A = ri.n_rows
         n_layers = (len(gemms) - 1) // 2
-        g_y = K.energy_head_bwd(g_E.contiguous(), w_out)                 # (G, A, C): the seed of every block's adjoint
-        width = g_y.shape[2]
-        # the program of _Stack.backward (no skips, no residuals of the first Dense) for group 0 of the stacked operands
+        g_E = g_E.contiguous()
+        width = w_out.shape[1]
+        # the program of _Stack.backward (no skips, no residuals of the first Dense) for group 0 of the stacked operands.  Its seed
+        # g_y[g, a, :] = g_E[a] * w_out[g, :] is written as operands of the LOAD (`seed`; `src` only carries the shape): the
+        # grouped atom-row kernel forms it while loading, every other launch gets the tensor from energy_head_bwd below
         prog = K.ChainProgram(A)
-        prog.load(0, g_y[0])
+        prog.load(0, w_out[:1].expand(A, width))
+        prog.ops[0]["seed"] = (g_E, w_out)
         cur, oth = 0, 1
         for k in range(n_layers - 1, -1, -1):
             z1, z2 = zs[1 + 2 * k], zs[2 + 2 * k]
@@ -1623,9 +1626,13 @@ class _OutputGroup(torch.autograd.Function):
         if zs[0] is not None:
             prog.scale(oth, cur, 1.0, Z=zs[0][0], width=width, mode=1)
             src = oth
-        g_x = torch.empty((G, A, gemms[0][0].shape[1]), device=g_y.device, dtype=g_y.dtype)
+        g_x = torch.empty((G, A, gemms[0][0].shape[1]), device=w_out.device, dtype=w_out.dtype)
         prog.gemm(gemms[0][0].t(), packed=_stacked_packed(gemms[0], True), a_slot=src, y_slot=-1, out=g_x[0])
-        K.chain(K.fuse_program(prog), groups=G, group_pitch=A)
+        prog = K.fuse_program(prog)
+        if not (K.USE_ATOM_STACK_GROUPED and K.atom_stack_grouped_match(prog, G, A) is not None):
+            g_y = K.energy_head_bwd(g_E, w_out)                          # (G, A, C): the seed of every block's adjoint
+            prog.ops[0].update(src=g_y[0], seed=None)
+        K.chain(prog, groups=G, group_pitch=A)
         # aggregation adjoint: per block the running gradient of its m (the interaction block's own consumers add onto it
         # later, in their kernels), one g_rbf summed over the blocks in-kernel
         entered = [acc.enter() if acc is not None else (None, True) for acc in ctx.acc_m]

@@ -209,6 +209,28 @@ int gn_atom_stack_fwd_f32(const float* x, int M, int layers, int tails, const vo
 int gn_atom_stack_bwd_f32(const float* g, int M, int layers, int tails, int form, const float* const* gt, const void* const* W,
                           const float* const* F, float alpha0, float a_out, float a_s, float bt0, float bt1, float bl0, float bl1,
                           float* g_skip, float* gx, void* stream);
+/* Grouped launches of the two atom-row kernels (csrc/atom_stack.hip; additive, ABI 16): the SAME stack for `groups` <=
+ * GN_CHAIN_MAX_GROUPS independent row ranges with their own weights, as gn_chain_split_grouped_f32 lays them out — the stage of the
+ * grouped OutputBlocks (Dense with activation + `layers` ResidualLayers, no tails, no skip).  The grid is (row tiles of one
+ * group, groups); by default a workgroup owns two 16-row tiles that share every weight fragment it fetches (a build-time choice
+ * of csrc/atom_stack.hip, AS_GROUP_TILES, not part of this contract).  Group g reads and writes rows g * group_pitch + [0, M)
+ * of every row operand (x, z[j], y; g, F[j], gx: stacked
+ * row-major tensors of 128 columns, the host arrays name group 0's slab) and multiplies by the g-th of the packed weights that lie
+ * back to back behind every W[j] (65 536 bytes each).  A tile never spans two groups: rows >= M of a group's last tile are neither
+ * read as valid nor written.  layers 1..2, 1 <= groups <= 8, group_pitch >= M, 1 <= M <= 4 096 (M <= 0: nothing is launched), every
+ * pointer 16-byte aligned; else hipErrorInvalidValue and no launch.  Results: bit for bit those of gn_chain_split_grouped_f32 on the
+ * same program (nprod = GN_CHAIN_F16X2, either tile height), i.e. of `groups` single launches.
+ * Forward: the program of gn_atom_stack_fwd_f32 with tails = 0 and no res2. */
+int gn_atom_stack_fwd_grouped_f32(const float* x, int M, int groups, int group_pitch, int layers, const void* const* W,
+                                  float* const* z, float s, float* y, void* stream);
+/* Adjoint: the program of gn_atom_stack_bwd_f32 with tails = 0, form 0 (G = g * alpha0; X = G * F[0]; the layers; gx).  The
+ * cotangent is EITHER the stacked tensor g (g_E = w_out = NULL) OR the seed of the energy head's adjoint formed in the LOAD
+ * (g = NULL): g[grp, a, :] = g_E[a] * w_out[grp, :] with g_E (M,1) and w_out (groups,128), one fp32 product per element as
+ * gn_energy_head_bwd_f32 rounds it, then treated like a loaded value — bit for bit gn_energy_head_bwd_f32 followed by the
+ * tensor form. */
+int gn_atom_stack_bwd_grouped_f32(const float* g, const float* g_E, const float* w_out, int M, int groups, int group_pitch,
+                                  int layers, const void* const* W, const float* const* F, float alpha0, float bl0, float bl1,
+                                  float* gx, void* stream);
 /* W (N,K) fp32 with row pitch ldw — or, trans != 0, the (K,N) matrix whose transpose is the weight — -> three bf16
  * planes in MFMA-fragment order; `out` holds gn_pack_weight_split_bytes(N,K) bytes (16-byte aligned). */
 int gn_pack_weight_split(const float* W, int N, int K, int ldw, int trans, void* out, void* stream);
