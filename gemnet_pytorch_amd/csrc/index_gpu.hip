@@ -14,7 +14,13 @@
 // Distances are evaluated exactly like np.linalg.norm(R[:,None]-R[None,:], axis=-1) <= cutoff in R's dtype:
 // d = R_i - R_j, s = (d0*d0 + d1*d1) + d2*d2 with every operation rounded (no FMA contraction), correctly
 // rounded sqrt, comparison against the cutoff cast to that dtype.
+//
+// Atom capacity (gn_index_gpu_layout + gn_index_gpu_padded_tv): molecules whose sizes change from replay to replay.  The layout
+// kernels of layout_cap.h turn the device-resident sizes N into mol_off / sq_off / atom_mol; the triplets-only capacity build then
+// runs over a_cap atom rows with grids and workspace sized by a_cap and n_max (the capacity of one molecule).  The atoms between
+// the batch and the capacity belong to "molecule" n_mol and leave the per-atom kernels with degree 0 before a position is read.
 #include "common.h"
+#include "layout_cap.h"
 
 namespace {
 
@@ -62,13 +68,21 @@ __global__ void idx_adj_kernel(const T* __restrict__ R, const int32_t* __restric
 }
 
 // per atom: degree, number of upper neighbours, interaction degree, molecule id
+// m_fill (here and in the edge / in-edge kernels below): the "molecule" of the filler atoms of an atom capacity
+// (gn_index_gpu_padded_tv; -1: none) — they have degree 0 and no adjacency block, wherever they sit: no position is read
 __global__ void idx_deg_kernel(const int32_t* __restrict__ mol_off, const int32_t* __restrict__ sq_off,
                                const int32_t* __restrict__ atom_mol, int A, int quad,
                                const uint8_t* __restrict__ adj, const uint8_t* __restrict__ iadj,
-                               int32_t* __restrict__ deg, int32_t* __restrict__ up, int32_t* __restrict__ ideg) {
+                               int32_t* __restrict__ deg, int32_t* __restrict__ up, int32_t* __restrict__ ideg, int m_fill) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= A) return;
   const int m = atom_mol[g];
+  if (m == m_fill) {
+    deg[g] = 0;
+    up[g] = 0;
+    if (quad) ideg[g] = 0;
+    return;
+  }
   const int a0 = mol_off[m], n = mol_off[m + 1] - a0, x = g - a0;
   const uint8_t* __restrict__ row = adj + sq_off[m] + (size_t)x * n;
   int d = 0, u = 0, di = 0;
@@ -130,10 +144,11 @@ __global__ void idx_edges_kernel(const int32_t* __restrict__ mol_off, const int3
                                  int32_t* __restrict__ id_a, int32_t* __restrict__ id_c,
                                  int32_t* __restrict__ id_undir, int32_t* __restrict__ id_swap,
                                  int32_t* __restrict__ int_a, int32_t* __restrict__ int_b,
-                                 int32_t* __restrict__ Mx, int32_t* __restrict__ MI, int e_cap, int eint_cap) {
+                                 int32_t* __restrict__ Mx, int32_t* __restrict__ MI, int e_cap, int eint_cap, int m_fill) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= A) return;
   const int m = atom_mol[g];
+  if (m == m_fill) return;
   const int a0 = mol_off[m], n = mol_off[m + 1] - a0, x = g - a0;
   const int H = off_half[A];
   if (2 * (int64_t)H > e_cap) return;       // capacity forms (gn_index_gpu_padded_*): nothing is written, the step is flagged
@@ -170,11 +185,12 @@ __global__ void idx_in_kernel(const int32_t* __restrict__ mol_off, const int32_t
                               const int32_t* __restrict__ atom_mol, int A, const uint8_t* __restrict__ adj,
                               const int32_t* __restrict__ Mx, const int32_t* __restrict__ in_ptr,
                               int32_t* __restrict__ in_edge, int32_t* __restrict__ pos_in,
-                              const int32_t* __restrict__ half_total, int e_cap) {
+                              const int32_t* __restrict__ half_total, int e_cap, int m_fill) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= A) return;
   if (half_total && 2 * (int64_t)*half_total > e_cap) return;
   const int m = atom_mol[g];
+  if (m == m_fill) return;
   const int a0 = mol_off[m], n = mol_off[m + 1] - a0, x = g - a0;
   const size_t base = (size_t)sq_off[m] + (size_t)x * n;
   int k = 0;
@@ -265,7 +281,13 @@ struct PadT {
 };
 
 __global__ void idx_commit_pad_t_kernel(PadT p, const int32_t* __restrict__ half_total, const int32_t* __restrict__ t_total,
-                                        int e_cap, int t_cap, int a_cap, int G, int deg_bound, int32_t* __restrict__ state) {
+                                        int e_cap, int t_cap, int a_cap, int G, int deg_bound, int32_t* __restrict__ state,
+                                        int layout_gate) {
+  // layout_gate (gn_index_gpu_padded_tv): the layout call of the same step refused the sizes — state[3] holds its bit 128 and
+  // stays as it is, and nothing the model reads is written.  Every thread reads state[3] while thread 0 may store this
+  // call's err into it below: err never holds bit 128 and an accepted layout left state[3] = 0, so the bit tested is the
+  // same before and after that store
+  if (layout_gate && (state[3] & 128)) return;
   const int64_t E = 2 * (int64_t)*half_total, T = E <= e_cap ? (int64_t)*t_total : 0;
   int err = 0;
   if (E > e_cap) err |= 1;
@@ -629,7 +651,7 @@ extern "C" int gn_index_gpu_stage1(const void* R, int r_is_f64, const int32_t* m
   GN_LAUNCH_CHECK();
   const dim3 ga(gn_cdiv(A, 256));
   hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, quad, w.adj, w.iadj, w.deg,
-                     w.up, w.ideg);
+                     w.up, w.ideg, -1);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.up, w.off_half, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.deg, w.in_ptr, (int64_t)A, w.overflow);
   if (quad) hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.ideg, w.off_int, (int64_t)A, w.overflow);
@@ -645,9 +667,9 @@ extern "C" int gn_index_gpu_stage1(const void* R, int r_is_f64, const int32_t* m
   if (E == 0) return 0;
   if (!id_a) return 0;    // size query only
   hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, quad, w.adj, w.iadj,
-                     w.off_half, w.off_int, id_a, id_c, id_undir, id_swap, int_a, int_b, w.Mx, w.MI, 0x7fffffff, 0x7fffffff);
+                     w.off_half, w.off_int, id_a, id_c, id_undir, id_swap, int_a, int_b, w.Mx, w.MI, 0x7fffffff, 0x7fffffff, -1);
   hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, w.adj, w.Mx, w.in_ptr,
-                     w.in_edge, w.pos_in, (const int32_t*)nullptr, 0);
+                     w.in_edge, w.pos_in, (const int32_t*)nullptr, 0, -1);
   hipLaunchKernelGGL(idx_cnt3_kernel, dim3(gn_cdiv(E, 256)), dim3(256), 0, st, id_a, w.deg, (int)E, w.cnt);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, E, w.overflow);
   GN_LAUNCH_CHECK();
@@ -709,14 +731,15 @@ extern "C" int gn_index_gpu_stage2(const int32_t* mol_off, const int32_t* sq_off
 }
 
 // Capacity form of the triplets-only build: no read-back, capturable.  See include/gemnet_hip.h.
-extern "C" int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, int B, int A,
-                                     int nmax, int64_t sum_n2, double cutoff, void* ws, int e_cap, int t_cap, int a_cap,
-                                     int n_groups, int deg_bound, int32_t* staging, int32_t* id_c, int32_t* id_a,
-                                     int32_t* id_swap, int32_t* id_undir, int32_t* id3_reduce_ca, int32_t* id3_expand_ba,
-                                     int32_t* state, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (A <= 0 || B <= 0 || e_cap <= 0 || t_cap <= 0 || n_groups <= 0 || (e_cap & 1) || (t_cap & 1)) return (int)hipErrorInvalidValue;
-  if (sum_n2 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+// The launches of gn_index_gpu_padded_t over A atom rows and B molecules; sum_n2: the bytes of the adjacency blocks (their upper
+// bound for the atom-capacity form).  atom_mol / m_fill / layout_gate: the atom-capacity form (gn_index_gpu_padded_tv) — the
+// molecule of every atom row comes from the layout call of the same step, the rows of molecule m_fill are fillers of degree 0,
+// and a layout that call refused lets the commit write nothing; NULL / -1 / 0: the fixed layout.
+static int idx_run_padded_t(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, const int32_t* atom_mol,
+                            int B, int A, int nmax, int64_t sum_n2, int m_fill, int layout_gate, double cutoff, void* ws,
+                            int e_cap, int t_cap, int a_cap, int n_groups, int deg_bound, int32_t* staging, int32_t* id_c,
+                            int32_t* id_a, int32_t* id_swap, int32_t* id_undir, int32_t* id3_reduce_ca, int32_t* id3_expand_ba,
+                            int32_t* state, hipStream_t st) {
   idx_ws w;
   const int64_t emax = sum_n2 - A;
   idx_layout((char*)ws, A, sum_n2, emax, 0, 0, &w);
@@ -725,7 +748,10 @@ extern "C" int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t*
           *s_red = staging + 4 * (size_t)e_cap, *s_exp = staging + 4 * (size_t)e_cap + t_cap;
   hipError_t e = hipMemsetAsync(w.overflow, 0, sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(idx_atom_mol_kernel, dim3(B), dim3(64), 0, st, mol_off, B, w.atom_mol, (int32_t*)nullptr);
+  if (!atom_mol) {
+    hipLaunchKernelGGL(idx_atom_mol_kernel, dim3(B), dim3(64), 0, st, mol_off, B, w.atom_mol, (int32_t*)nullptr);
+    atom_mol = w.atom_mol;
+  }
   dim3 gadj(gn_cdiv((int64_t)nmax * nmax, 256), B);
   if (r_is_f64)
     hipLaunchKernelGGL((idx_adj_kernel<double>), gadj, dim3(256), 0, st, (const double*)R, mol_off, sq_off, cutoff, cutoff, 0,
@@ -734,19 +760,19 @@ extern "C" int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t*
     hipLaunchKernelGGL((idx_adj_kernel<float>), gadj, dim3(256), 0, st, (const float*)R, mol_off, sq_off, (float)cutoff,
                        (float)cutoff, 0, w.adj, w.iadj);
   const dim3 ga(gn_cdiv(A, 256));
-  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 0, w.adj, w.iadj, w.deg, w.up, w.ideg);
+  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, 0, w.adj, w.iadj, w.deg, w.up, w.ideg, m_fill);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.up, w.off_half, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.deg, w.in_ptr, (int64_t)A, w.overflow);
   GN_LAUNCH_CHECK();
   const int32_t* half_total = w.off_half + A;
-  hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 0, w.adj, w.iadj, w.off_half,
-                     w.off_int, s_a, s_c, s_undir, s_swap, (int32_t*)nullptr, (int32_t*)nullptr, w.Mx, w.MI, e_cap, 0);
-  hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
-                     w.pos_in, half_total, e_cap);
+  hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, 0, w.adj, w.iadj, w.off_half,
+                     w.off_int, s_a, s_c, s_undir, s_swap, (int32_t*)nullptr, (int32_t*)nullptr, w.Mx, w.MI, e_cap, 0, m_fill);
+  hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
+                     w.pos_in, half_total, e_cap, m_fill);
   if (n > 0) {
     hipLaunchKernelGGL(idx_cnt3_cap_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, s_a, w.deg, half_total, n, e_cap, w.cnt);
     hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, (int64_t)n, w.overflow);
-    hipLaunchKernelGGL(idx_trip_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, w.atom_mol, s_a, s_c, n, w.adj,
+    hipLaunchKernelGGL(idx_trip_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, atom_mol, s_a, s_c, n, w.adj,
                        w.Mx, w.off3, s_red, s_exp, (int32_t*)nullptr, half_total, e_cap, t_cap, (const int32_t*)nullptr);
   } else {
     e = hipMemsetAsync(w.off3, 0, sizeof(int32_t), st);
@@ -756,9 +782,53 @@ extern "C" int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t*
   PadT p{s_c, s_a, s_swap, s_undir, s_red, s_exp, id_c, id_a, id_swap, id_undir, id3_reduce_ca, id3_expand_ba};
   const int64_t work = e_cap > t_cap ? e_cap : t_cap;
   hipLaunchKernelGGL(idx_commit_pad_t_kernel, dim3((unsigned)(gn_cdiv(work, 256) < 2048 ? gn_cdiv(work, 256) : 2048)), dim3(256), 0,
-                     st, p, half_total, (const int32_t*)(w.off3 + n), e_cap, t_cap, a_cap, n_groups, deg_bound, state);
+                     st, p, half_total, (const int32_t*)(w.off3 + n), e_cap, t_cap, a_cap, n_groups, deg_bound, state, layout_gate);
   GN_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, int B, int A,
+                                     int nmax, int64_t sum_n2, double cutoff, void* ws, int e_cap, int t_cap, int a_cap,
+                                     int n_groups, int deg_bound, int32_t* staging, int32_t* id_c, int32_t* id_a,
+                                     int32_t* id_swap, int32_t* id_undir, int32_t* id3_reduce_ca, int32_t* id3_expand_ba,
+                                     int32_t* state, void* stream) {
+  if (A <= 0 || B <= 0 || e_cap <= 0 || t_cap <= 0 || n_groups <= 0 || (e_cap & 1) || (t_cap & 1)) return (int)hipErrorInvalidValue;
+  if (sum_n2 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  return idx_run_padded_t(R, r_is_f64, mol_off, sq_off, nullptr, B, A, nmax, sum_n2, -1, 0, cutoff, ws, e_cap, t_cap, a_cap, n_groups,
+                          deg_bound, staging, id_c, id_a, id_swap, id_undir, id3_reduce_ca, id3_expand_ba, state,
+                          static_cast<hipStream_t>(stream));
+}
+
+// ---- atom capacity: molecules whose sizes change from replay to replay (gn_index_gpu_layout + gn_index_gpu_padded_tv) -------
+// The layout kernels (layout_cap.h, shared with gn_pbc_layout) turn the device-resident sizes N into mol_off / sq_off /
+// atom_mol / batch_seg / the padded N / the mask; the build above then runs over a_cap atom rows and n_mol molecules with every
+// grid and the workspace sized by the capacities (a molecule holds at most n_max atoms, so the adjacency blocks take at most
+// a_cap * n_max bytes: the workspace is that of gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, 1)).  The real atoms come first, so the canonical order of the real rows is that of the batch on its own.
+extern "C" int gn_index_gpu_layout(const int32_t* N, const int32_t* n_atoms, int n_mol, int a_cap, int a_tot, int n_max,
+                                   int32_t* mol_off, int32_t* sq_off, int32_t* atom_mol, int64_t* batch_seg, int64_t* N_pad,
+                                   float* mask, int32_t* state, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n_mol <= 0 || a_cap < n_mol || a_tot < a_cap || n_max <= 0 || (int64_t)a_cap * n_max > 0x7fffffffLL)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(cap_layout_scan_kernel, dim3(1), dim3(1024), 0, st, N, n_atoms, n_mol, a_cap, a_tot, n_max, mol_off, sq_off,
+                     N_pad, state);
+  hipLaunchKernelGGL(cap_layout_atoms_kernel, dim3(gn_cdiv(a_tot, 256)), dim3(256), 0, st, mol_off, n_mol, a_cap, a_tot, state,
+                     atom_mol, batch_seg, mask);
+  GN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gn_index_gpu_padded_tv(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off,
+                                      const int32_t* atom_mol, int n_mol, int n_max, double cutoff, void* ws, int e_cap, int t_cap,
+                                      int a_cap, int n_groups, int deg_bound, int32_t* staging, int32_t* id_c, int32_t* id_a,
+                                      int32_t* id_swap, int32_t* id_undir, int32_t* id3_reduce_ca, int32_t* id3_expand_ba,
+                                      int32_t* state, void* stream) {
+  if (n_mol <= 0 || a_cap < n_mol || n_max <= 0 || e_cap <= 0 || t_cap <= 0 || n_groups <= 0 || (e_cap & 1) || (t_cap & 1) || !atom_mol)
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)a_cap * n_max > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  return idx_run_padded_t(R, r_is_f64, mol_off, sq_off, atom_mol, n_mol, a_cap, n_max, (int64_t)a_cap * n_max, n_mol, 1, cutoff, ws,
+                          e_cap, t_cap, a_cap, n_groups, deg_bound, staging, id_c, id_a, id_swap, id_undir, id3_reduce_ca,
+                          id3_expand_ba, state, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gn_index_poison_f32(float* x, int64_t n, const int32_t* state, void* stream) {
@@ -797,16 +867,16 @@ extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t*
     hipLaunchKernelGGL((idx_adj_kernel<float>), gadj, dim3(256), 0, st, (const float*)R, mol_off, sq_off, (float)cutoff,
                        (float)int_cutoff, 1, w.adj, w.iadj);
   const dim3 ga(gn_cdiv(A, 256));
-  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 1, w.adj, w.iadj, w.deg, w.up, w.ideg);
+  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 1, w.adj, w.iadj, w.deg, w.up, w.ideg, -1);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.up, w.off_half, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.deg, w.in_ptr, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.ideg, w.off_int, (int64_t)A, w.overflow);
   GN_LAUNCH_CHECK();
   const int32_t *half_total = w.off_half + A, *eint_total = w.off_int + A;
   hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 1, w.adj, w.iadj, w.off_half,
-                     w.off_int, s_a, s_c, s_undir, s_swap, s_int_a, s_int_b, w.Mx, w.MI, e_cap, eint_cap);
+                     w.off_int, s_a, s_c, s_undir, s_swap, s_int_a, s_int_b, w.Mx, w.MI, e_cap, eint_cap, -1);
   hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
-                     w.pos_in, half_total, e_cap);
+                     w.pos_in, half_total, e_cap, -1);
   if (n <= 0 || ni <= 0) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(idx_cnt3_cap_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, s_a, w.deg, half_total, n, e_cap, w.cnt);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, (int64_t)n, w.overflow);

@@ -18,12 +18,13 @@
 // written, so the arrays keep the previous step's valid contents (gn_index_poison_f32 then turns the outputs into NaN).
 //
 // Atom capacity (gn_pbc_layout + gn_pbc_index_padded_tv): batches whose structure sizes change from replay to replay.  The
-// layout kernels turn the device-resident sizes N into mol_off / atom_mol / batch_seg / the padded N / the loss mask (one block
+// layout kernels (layout_cap.h, shared with the molecular gn_index_gpu_layout) turn the device-resident sizes N into mol_off / atom_mol / batch_seg / the padded N / the loss mask (one block
 // scans the structures, a grid over the atom rows bisects mol_off; error bit 128 and no write when the sizes do not add up to
 // n_atoms, hold a zero or exceed a_cap).  The index build then runs the SAME kernels over a_cap atom rows: the atoms between
 // the batch and the capacity belong to "structure" n_mol and leave their waves at once with count 0 and degree 0, wherever they
 // sit; the real atoms come first, so the canonical order of the real rows is that of the batch on its own.
 #include "common.h"
+#include "layout_cap.h"
 #include "pbc_index_cap.h"
 
 namespace {
@@ -133,89 +134,6 @@ int pbx_run(const float* R, const float* cell, const uint8_t* pbc, const int32_t
   return 0;
 }
 
-// ---- the capacity layout from device-resident structure sizes (gn_pbc_layout) ------------------------------------------------
-// One block: sum and validity of N first (an invalid layout sets bit 128 and writes no array), then the exclusive scan in rounds
-// of 1024 structures with a carry, as pbc_scan_kernel.
-__global__ __launch_bounds__(1024) void pbx_layout_scan_kernel(const int32_t* __restrict__ N, const int32_t* __restrict__ n_atoms,
-                                                               int n_mol, int a_cap, int a_tot, int32_t* __restrict__ mol_off,
-                                                               int64_t* __restrict__ N_pad, int32_t* __restrict__ state) {
-  __shared__ int64_t wsum[16];
-  __shared__ int wbad[16];
-  __shared__ int64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int64_t sum = 0;
-  int bad = 0;
-  for (int b = tid; b < n_mol; b += 1024) {
-    const int32_t v = N[b];
-    sum += v;
-    bad |= v < 1;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    sum += __shfl_xor(sum, o, 64);
-    bad |= __shfl_xor(bad, o, 64);
-  }
-  if (lane == 0) { wsum[wave] = sum; wbad[wave] = bad; }
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  int64_t total = 0;
-  bad = 0;
-  for (int w = 0; w < 16; ++w) { total += wsum[w]; bad |= wbad[w]; }
-  if (bad || total != (int64_t)n_atoms[0] || total > (int64_t)a_cap) {      // (block-uniform)
-    if (tid == 0) { state[0] |= 128; state[3] = 128; }
-    return;
-  }
-  __syncthreads();                                            // wsum is reused by the scan
-  for (int base = 0; base < n_mol; base += 1024) {
-    const int b = base + tid;
-    const int64_t v = b < n_mol ? (int64_t)N[b] : 0;
-    int64_t s = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t t = __shfl_up(s, o, 64);
-      if (lane >= o) s += t;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int64_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const int64_t carry = carry_s;
-    if (b < n_mol) {
-      mol_off[b] = (int32_t)(carry + woff + s - v);
-      N_pad[b] = v;
-    }
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + s;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    mol_off[n_mol] = (int32_t)total;                          // the filler atoms [A, a_cap) form "structure" n_mol
-    mol_off[n_mol + 1] = a_cap;
-    N_pad[n_mol] = (int64_t)a_tot - total;                    // fillers + dummy atoms: the dummy molecule of padded.py
-    state[3] = 0;
-  }
-}
-
-// one thread per atom row of a_tot: its structure by bisection in mol_off (strictly ascending over [0, n_mol]: every N_b >= 1)
-__global__ __launch_bounds__(256) void pbx_layout_atoms_kernel(const int32_t* __restrict__ mol_off, int n_mol, int a_cap, int a_tot,
-                                                               const int32_t* __restrict__ state, int32_t* __restrict__ atom_mol,
-                                                               int64_t* __restrict__ batch_seg, float* __restrict__ mask) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a_tot || (state[3] & 128)) return;
-  int m = n_mol;
-  if (i < a_cap) {
-    int lo = 0, hi = n_mol + 1;                               // first index in [0, n_mol] with mol_off > i, or n_mol + 1
-    while (lo < hi) {
-      const int md = (lo + hi) >> 1;
-      if (mol_off[md] <= i) lo = md + 1; else hi = md;
-    }
-    m = lo - 1;
-    atom_mol[i] = m;
-    mask[i] = i < mol_off[n_mol] ? 1.0f : 0.0f;
-  }
-  batch_seg[i] = m;
-}
-
 }  // namespace
 
 extern "C" int gn_pbc_index_padded_t(const float* R, const float* cell, const uint8_t* pbc, const int32_t* mol_off,
@@ -233,8 +151,10 @@ extern "C" int gn_pbc_layout(const int32_t* N, const int32_t* n_atoms, int n_mol
                              int32_t* atom_mol, int64_t* batch_seg, int64_t* N_pad, float* mask, int32_t* state, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n_mol <= 0 || a_cap < n_mol || a_tot < a_cap) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(pbx_layout_scan_kernel, dim3(1), dim3(1024), 0, st, N, n_atoms, n_mol, a_cap, a_tot, mol_off, N_pad, state);
-  hipLaunchKernelGGL(pbx_layout_atoms_kernel, dim3(gn_cdiv(a_tot, 256)), dim3(256), 0, st, mol_off, n_mol, a_cap, a_tot, state,
+  // (layout_cap.h; no bound on one structure's size, no adjacency offsets)
+  hipLaunchKernelGGL(cap_layout_scan_kernel, dim3(1), dim3(1024), 0, st, N, n_atoms, n_mol, a_cap, a_tot, 0, mol_off, (int32_t*)nullptr,
+                     N_pad, state);
+  hipLaunchKernelGGL(cap_layout_atoms_kernel, dim3(gn_cdiv(a_tot, 256)), dim3(256), 0, st, mol_off, n_mol, a_cap, a_tot, state,
                      atom_mol, batch_seg, mask);
   GN_LAUNCH_CHECK();
   return 0;

@@ -83,6 +83,121 @@ class DeviceGraphBuilder:
         return {k: (out[k] if dtype == torch.int32 else out[k].to(dtype)) for k in keys}
 
 
+class DeviceCapacityGraphBuilder(DeviceGraphBuilder):
+    """`DeviceGraphBuilder` whose layout can change: `n_mol` molecules per batch inside an atom capacity `a_cap`, none larger
+    than `n_max` atoms, their sizes N set per batch — the molecular sibling of pbc.PeriodicCapacityGraphBuilder.  It owns
+    `mol_off` (n_mol + 2), `sq_off` (n_mol + 1), `atom_mol` (a_cap) and the workspace as device buffers of the capacity shapes
+    (the filler atoms between the batch and a_cap form "molecule" n_mol: padded.capacity_layout), and the sizes as the
+    in-graph layout reads them: `N32` (n_mol) int32, `n_atoms` (1) int32.
+
+        builder = DeviceCapacityGraphBuilder(n_mol, a_cap, n_max, cutoff, device=dev)
+        builder.set_layout(N)                          # host or device array
+        idx = builder(R)                               # = DeviceGraphBuilder(N, cutoff, cutoff, triplets_only=True)(R)
+
+    Attached to a molecular `padded.PaddedGraphRunner` with `a_cap` the layout (gn_index_gpu_layout) and the lists
+    (gn_index_gpu_padded_tv) are built inside the replay from these buffers.  Triplets-only models (GemNet-T); GemNet-Q with
+    an atom capacity inside the graph is not served."""
+
+    def __init__(self, n_mol, a_cap, n_max, cutoff, triplets_only=True, device="cuda"):
+        if not triplets_only:
+            raise NotImplementedError("DeviceCapacityGraphBuilder: triplets-only models (GemNet-T) only, not GemNet-Q "
+                                      "(quadruplet lists with an atom capacity are not built inside the graph)")
+        self.B, self.a_cap, self.n_max = int(n_mol), int(a_cap), int(n_max)
+        if not 0 < self.B <= self.a_cap:
+            raise ValueError(f"need 0 < n_mol <= a_cap; got n_mol = {self.B}, a_cap = {self.a_cap}")
+        if not 0 < self.n_max <= self.a_cap:
+            raise ValueError(f"need 0 < n_max <= a_cap; got n_max = {self.n_max}, a_cap = {self.a_cap}")
+        if self.a_cap * self.n_max >= 2 ** 31:
+            raise ValueError(f"a_cap * n_max = {self.a_cap * self.n_max} exceeds int32 (the adjacency blocks of the batch)")
+        self.A = None                       # atoms of the current layout (known on the host once a batch came by)
+        self.cutoff, self.int_cutoff, self.triplets_only = float(cutoff), float(cutoff), True
+        self.device = torch.device(device)
+        dev = self.device
+        self.mol_off = torch.zeros(self.B + 2, dtype=torch.int32, device=dev)
+        self.sq_off = torch.zeros(self.B + 1, dtype=torch.int32, device=dev)
+        self.atom_mol = torch.full((self.a_cap,), self.B, dtype=torch.int32, device=dev)
+        self.N32 = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self.n_atoms = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._N_host = None                 # the sizes as the host knows them (None: handed in on the device)
+        self._arrays = False                # do mol_off / sq_off / atom_mol hold the layout of N32?
+        self._ws = None
+
+    @property
+    def ws(self):
+        """The workspace of the capacity shapes (kernels.index_cap_ws_bytes), allocated on first use."""
+        if self._ws is None:
+            from . import kernels as K
+            self._ws = torch.empty(max(K.index_cap_ws_bytes(self.a_cap, self.n_max), 64), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def check_sizes(self, N, n_atoms=None):
+        """ValueError unless the host sizes N fit this builder: n_mol of them, each in [1, n_max], a_cap atoms at the most (and
+        `n_atoms` of them when given) — what gn_index_gpu_layout checks on the device (error bit 128)."""
+        N = np.asarray(N, dtype=np.int64).reshape(-1)
+        if len(N) != self.B:
+            raise ValueError(f"N must hold {self.B} molecule sizes; got {len(N)}")
+        if N.min() < 1 or N.max() > self.n_max or N.sum() > self.a_cap or (n_atoms is not None and N.sum() != int(n_atoms)):
+            raise ValueError(f"molecule sizes (min {int(N.min())}, max {int(N.max())}, sum {int(N.sum())}) do not fit n_max = "
+                             f"{self.n_max} / a_cap = {self.a_cap}" + ("" if n_atoms is None else f" / n_atoms = {int(n_atoms)}"))
+        return N
+
+    def set_layout(self, N=None, n_atoms=None, arrays=True):
+        """Sizes N (n_mol,) of the next batch, a host or a device array (None: as they are).  No host sync.  `n_atoms`: the atom
+        count the in-graph layout checks sum(N) against (default: sum of a host N); `arrays=False` leaves `mol_off` / `sq_off` /
+        `atom_mol` to the in-graph layout kernel, which refuses sizes that do not fit (bit 128).  With `arrays=True` host sizes
+        that do not fit raise `ValueError`; device sizes that do not fit leave the three arrays as they were."""
+        if N is not None:
+            on_dev = torch.is_tensor(N) and N.device.type != "cpu"
+            Nt = (N if torch.is_tensor(N) else torch.as_tensor(np.asarray(N, dtype=np.int64))).reshape(-1)
+            if int(Nt.shape[0]) != self.B:
+                raise ValueError(f"N must hold {self.B} molecule sizes; got {int(Nt.shape[0])}")
+            host = None if on_dev else Nt.detach().numpy().astype(np.int64)
+            if host is not None:
+                if arrays:
+                    self.check_sizes(host, n_atoms)
+                if n_atoms is None:
+                    n_atoms = int(host.sum())
+            self._N_host = host
+            self.N32.copy_(Nt)
+            self.A = None if n_atoms is None else int(n_atoms)
+            self._arrays = False
+        if n_atoms is not None:
+            self.A = int(n_atoms)
+            self.n_atoms.fill_(int(n_atoms))
+        if arrays and not self._arrays:
+            self._write_arrays(check_atoms=n_atoms is not None)
+        return self
+
+    def _write_arrays(self, check_atoms=True):
+        """mol_off / sq_off / atom_mol of N32 (padded.capacity_layout and the prefix sums of N^2) in PyTorch, without a host
+        sync: sizes that gn_index_gpu_layout would refuse leave the arrays as they were."""
+        from .padded import capacity_layout
+        N = self.N32.to(torch.int64)
+        lay = capacity_layout(N, self.B, self.a_cap, self.a_cap)
+        sq = torch.cat([torch.zeros(1, dtype=torch.int64, device=N.device), torch.cumsum(N * N, 0)])
+        ok = ((N >= 1) & (N <= self.n_max)).all() & (N.sum() <= self.a_cap)
+        if check_atoms:
+            ok = ok & (N.sum() == self.n_atoms[0])
+        self.mol_off.copy_(torch.where(ok, lay["mol_off"], self.mol_off))
+        self.sq_off.copy_(torch.where(ok, sq.clamp(max=2 ** 31 - 1).to(torch.int32), self.sq_off))
+        self.atom_mol.copy_(torch.where(ok, lay["atom_mol"], self.atom_mol))
+        self._arrays = True
+
+    def __call__(self, R, dtype=torch.int64):
+        """The host-sized build for the current layout: the kernels of `DeviceGraphBuilder` on the capacity buffers (their first
+        n_mol + 1 entries are that builder's arrays).  Reads the sizes back when they were handed in on the device."""
+        N = self.check_sizes(self._N_host if self._N_host is not None else self.N32.cpu().numpy())
+        A = int(R.shape[0])
+        if A != int(N.sum()) or (self.A is not None and A != self.A):
+            raise ValueError(f"positions of {A} atoms for a layout of {int(N.sum())} (a_cap = {self.a_cap}): set_layout(N) first")
+        if not self._arrays:
+            self._write_arrays(check_atoms=False)
+        self.A, self.nmax, self.sum_n2 = A, int(N.max()), int((N * N).sum())
+        self.cap = max(self.sum_n2 - self.A, 0)
+        self.ws                             # (allocated)
+        return super().__call__(R, dtype=dtype)
+
+
 def build_indices_device(R, N, cutoff, int_cutoff, triplets_only=False, dtype=torch.int64):
     return DeviceGraphBuilder(N, cutoff, int_cutoff, triplets_only, device=R.device)(R, dtype=dtype)
 

@@ -272,6 +272,61 @@ def index_padded_t(builder, R, e_cap, t_cap, a_cap, n_groups, deg_bound, staging
         ptr(bufs["id3_reduce_ca"]), ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_index_gpu_padded_t")
 
 
+def index_cap_ws_bytes(a_cap, n_max):
+    """Bytes of the workspace gn_index_gpu_padded_tv needs for `a_cap` atom rows of molecules of at most `n_max` atoms: that
+    of the triplets-only build with the adjacency blocks at their upper bound a_cap * n_max (gn_index_gpu_ws_bytes)."""
+    a_cap, n_max = int(a_cap), int(n_max)
+    if a_cap <= 0 or n_max <= 0 or a_cap * n_max >= 2 ** 31:
+        raise ValueError(f"a_cap * n_max = {a_cap * n_max} must be positive and fit int32 (the adjacency blocks)")
+    return int(_lib.load().gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, 1))
+
+
+def index_layout(N32, n_atoms, n_mol, a_cap, a_tot, n_max, mol_off, sq_off, atom_mol, batch_seg, N_pad, mask, state):
+    """The capacity layout of a molecular batch from its molecule sizes ON THE DEVICE (gn_index_gpu_layout): `pbc_layout` plus
+    sq_off (n_mol + 1) int32, the exclusive scan of N_b^2, and the bound `n_max` on one molecule — no read-back, capturable.
+    Sizes that do not add up to n_atoms, hold a zero, exceed a_cap or hold a molecule above n_max set bit 128 in state[0] /
+    state[3] and leave every array as it was."""
+    require_device(N32, n_atoms, mol_off, sq_off, atom_mol, batch_seg, N_pad, mask, state)
+    n_mol, a_cap, a_tot, n_max = int(n_mol), int(a_cap), int(a_tot), int(n_max)
+    assert 0 < n_mol <= a_cap <= a_tot and 0 < n_max and a_cap * n_max < 2 ** 31
+    assert N32.dtype == torch.int32 and N32.numel() == n_mol and N32.is_contiguous()
+    assert n_atoms.dtype == torch.int32 and n_atoms.numel() == 1
+    assert mol_off.dtype == torch.int32 and mol_off.numel() == n_mol + 2 and mol_off.is_contiguous()
+    assert sq_off.dtype == torch.int32 and sq_off.numel() == n_mol + 1 and sq_off.is_contiguous()
+    assert atom_mol.dtype == torch.int32 and atom_mol.numel() == a_cap and atom_mol.is_contiguous()
+    assert batch_seg.dtype == torch.int64 and batch_seg.numel() == a_tot and batch_seg.is_contiguous()
+    assert N_pad.dtype == torch.int64 and N_pad.numel() == n_mol + 1 and N_pad.is_contiguous()
+    assert mask.dtype == torch.float32 and mask.numel() == a_cap and mask.is_contiguous()
+    assert state.dtype == torch.int32 and state.numel() >= 4
+    check(_lib.load().gn_index_gpu_layout(ptr(N32), ptr(n_atoms), n_mol, a_cap, a_tot, n_max, ptr(mol_off), ptr(sq_off),
+                                          ptr(atom_mol), ptr(batch_seg), ptr(N_pad), ptr(mask), ptr(state), stream()),
+          "gn_index_gpu_layout")
+
+
+def index_padded_tv(builder, R, e_cap, t_cap, a_cap, n_groups, deg_bound, staging, bufs, state):
+    """`index_padded_t` for a builder whose layout changes from replay to replay (index_device.DeviceCapacityGraphBuilder): R
+    (a_cap,3) — the batch, then the filler atoms — read at replay time with the layout `index_layout` wrote in the same step
+    (gn_index_gpu_padded_tv; the builder's ws: index_cap_ws_bytes(a_cap, n_max), staging: int32[4 e_cap + 2 t_cap], state:
+    int32[4], see the header)."""
+    require_device(R, staging, state, builder.ws)
+    assert builder.a_cap == int(a_cap) and builder.B <= int(a_cap)
+    assert R.dtype in (torch.float32, torch.float64) and R.is_contiguous() and tuple(R.shape) == (builder.a_cap, 3)
+    assert builder.mol_off.numel() == builder.B + 2 and builder.sq_off.numel() == builder.B + 1
+    assert builder.atom_mol.numel() == builder.a_cap and builder.atom_mol.dtype == torch.int32
+    assert builder.ws.dtype == torch.uint8 and builder.ws.numel() >= index_cap_ws_bytes(builder.a_cap, builder.n_max)
+    assert staging.dtype == torch.int32 and staging.numel() >= 4 * e_cap + 2 * t_cap
+    assert state.dtype == torch.int32 and state.numel() >= 4
+    for k in ("id_c", "id_a", "id_swap", "id_undir"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == e_cap and bufs[k].is_contiguous()
+    for k in ("id3_reduce_ca", "id3_expand_ba"):
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == t_cap and bufs[k].is_contiguous()
+    check(_lib.load().gn_index_gpu_padded_tv(
+        ptr(R), int(R.dtype == torch.float64), ptr(builder.mol_off), ptr(builder.sq_off), ptr(builder.atom_mol), builder.B,
+        builder.n_max, builder.cutoff, ptr(builder.ws), int(e_cap), int(t_cap), int(a_cap), int(n_groups), int(deg_bound),
+        ptr(staging), ptr(bufs["id_c"]), ptr(bufs["id_a"]), ptr(bufs["id_swap"]), ptr(bufs["id_undir"]),
+        ptr(bufs["id3_reduce_ca"]), ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_index_gpu_padded_tv")
+
+
 def pbc_index_ws_bytes(n_atoms, e_cap):
     """Bytes of the workspace gn_pbc_index_padded_t needs for `n_atoms` atoms and an edge capacity of `e_cap`."""
     return int(_lib.load().gn_pbc_index_ws_bytes(int(n_atoms), int(e_cap)))

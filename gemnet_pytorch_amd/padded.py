@@ -37,7 +37,9 @@ is padded with zeros as well and `attach_builder(pbc.PeriodicQuadGraphBuilder)` 
 (gn_pbc_qindex_padded).  With `a_cap` and a model that sets `periodic_atom_capacity` (GemNet-T / GemNet-dT) the structures of a
 periodic batch may change in size from call to call as well: the filler atoms belong to the dummy structure, `capacity_layout`
 below names the layout arrays, and `attach_builder(pbc.PeriodicCapacityGraphBuilder)` puts layout (gn_pbc_layout) and list
-(gn_pbc_index_padded_tv) inside the graph.
+(gn_pbc_index_padded_tv) inside the graph.  Molecules with `a_cap` (triplets-only models) get the same from
+`attach_builder(index_device.DeviceCapacityGraphBuilder)`: layout (gn_index_gpu_layout) and lists (gn_index_gpu_padded_tv) inside the
+graph — a loader's batches, `run_positions(R, Z=, N=)`, `Trainer.enable_padded_eval`.
 
 Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
 `Trainer.enable_padded_graph` (the training step in the same form), `training.periodic.PeriodicPaddedTrainStep` (the training
@@ -427,7 +429,7 @@ class PaddedGraphRunner:
             buf["batch_seg"][:A].copy_(torch.repeat_interleave(torch.arange(self.n_mol, device=N.device), N.to(torch.int64),
                                                                 output_size=A))
             buf["batch_seg"][A:].fill_(self.n_mol)
-            if self.periodic and self.variable_atoms and self.builder is not None:
+            if self.variable_atoms and self.builder is not None:
                 # (an attached capacity builder: the replay rebuilds layout and lists from the builder's sizes)
                 self.builder.set_layout(N, n_atoms=A, arrays=False)
             if A < self.A:      # atoms that were real in the previous batch become filler again
@@ -553,7 +555,7 @@ class PaddedGraphRunner:
         self.graph.replay()
         return self._results()
 
-    # ---- the index build INSIDE the replayed graph (triplets-only models, fixed molecule layout) --------------------------
+    # ---- the index build INSIDE the replayed graph (fixed molecule layout; with a_cap: the two capacity builders) ----------
     def attach_builder(self, builder):
         """From the next capture on the graph starts with the index build itself (index_device.DeviceGraphBuilder's layout,
         gn_index_gpu_padded_t: counts stay on the device, the arrays are committed into the static buffers with their pad
@@ -561,7 +563,10 @@ class PaddedGraphRunner:
         on the host — the MD step of ase_calculator.py:148-170 as ONE graph.  The buffers must hold a valid batch already
         (one `_fill`): a step that does not fit the capacities keeps the previous arrays, poisons its outputs with NaN and
         reports through `index_error()`."""
+        from .index_device import DeviceCapacityGraphBuilder
         from .pbc import PeriodicCapacityGraphBuilder, PeriodicGraphBuilder, PeriodicQuadGraphBuilder
+        if isinstance(builder, DeviceCapacityGraphBuilder):
+            return self._attach_molecular_capacity_builder(builder)
         cb = isinstance(builder, PeriodicCapacityGraphBuilder)
         if self.variable_atoms and not (self.periodic and cb):
             raise NotImplementedError("the in-graph index build needs a fixed molecule layout (no a_cap)")
@@ -620,9 +625,38 @@ class PaddedGraphRunner:
         self.graph = None
         self.out = None
 
+    def _attach_molecular_capacity_builder(self, builder):
+        """`attach_builder` of a molecular runner with an atom capacity (index_device.DeviceCapacityGraphBuilder; triplets-only
+        models): the graph starts with layout (gn_index_gpu_layout) -> index build (gn_index_gpu_padded_tv) -> plan -> model.
+        The builder's sizes are set from the batch the buffers hold."""
+        if self.periodic or self.quad or not self.variable_atoms:
+            raise ValueError("builder and runner describe different systems (a molecular capacity builder needs a molecular "
+                             "triplets-only runner with a_cap)")
+        if builder.B != self.n_mol or builder.a_cap != self.a_cap or self.index_dtype != torch.int32:
+            raise ValueError("builder and runner describe different systems")
+        if not self._filled:
+            raise RuntimeError("attach_builder: fill the buffers with a first batch (runner._fill / runner(R, idx)) before")
+        dev = self.inputs["R"].device
+        builder.set_layout(self.inputs["N"][:self.n_mol], n_atoms=self.A, arrays=False)
+        self.builder = builder
+        self._staging = torch.zeros(4 * self.e_cap + 2 * self.t_cap, dtype=torch.int32, device=dev)
+        self._idx_state = torch.zeros(8, dtype=torch.int32, device=dev)
+        self._idx_host = torch.zeros(8, dtype=torch.int32)
+        if dev.type == "cuda":
+            self._idx_host = self._idx_host.pin_memory()
+        self._layout_mask = torch.zeros(self.a_cap, dtype=torch.float32, device=dev)      # 1 on the atoms of the batch
+        self.graph = None
+        self.out = None
+
     def _index_in_graph(self):
         from . import kernels as K
-        if self.periodic and self.variable_atoms:
+        if self.variable_atoms and not self.periodic:
+            b = self.builder
+            K.index_layout(b.N32, b.n_atoms, self.n_mol, self.a_cap, self.A_tot, b.n_max, b.mol_off, b.sq_off, b.atom_mol,
+                           self.inputs["batch_seg"], self.inputs["N"], self._layout_mask, self._idx_state)
+            K.index_padded_tv(b, self.inputs["R"][:self.a_cap], self.e_cap, self.t_cap, self.a_cap, self.G, self.pad_degree_bound(),
+                              self._staging, self.inputs, self._idx_state)
+        elif self.periodic and self.variable_atoms:
             b = self.builder
             K.pbc_layout(b.N32, b.n_atoms, self.n_mol, self.a_cap, self.A_tot, b.mol_off, b.atom_mol, self.inputs["batch_seg"],
                          self.inputs["N"], self._layout_mask, self._idx_state)
@@ -663,10 +697,12 @@ class PaddedGraphRunner:
         self._idx_host.zero_()
 
     def _load_variable(self, R, Z, N, pbc, who):
-        """Host side of a step of a periodic runner with an atom capacity whose lists are built inside the replay: the checks
-        (before anything is copied), the builder's sizes / axes / atom count, and the filler rows of R and Z that were real in
+        """Host side of a step of a runner with an atom capacity whose lists are built inside the replay: the checks (before
+        anything is copied), the builder's sizes / axes (periodic) / atom count, and the filler rows of R and Z that were real in
         the previous batch."""
         A = int(R.shape[0]) if R.dim() == 2 else -1
+        if pbc is not None and not self.periodic:
+            raise ValueError("pbc per call needs a periodic runner")
         if R.dtype != self.inputs["R"].dtype or R.dim() != 2 or R.shape[1] != 3:
             raise TypeError(f"{who}: positions must be {self.inputs['R'].dtype} of shape (A, 3); got {R.dtype} {tuple(R.shape)}")
         n_given = self.n_mol if N is None else int(N.shape[0])
@@ -677,8 +713,10 @@ class PaddedGraphRunner:
             raise ValueError("the number of atoms changed: build the runner with a_cap and pass Z and N with every call")
         if Z is not None and int(Z.shape[0]) != A:
             raise ValueError(f"Z must hold the {A} atomic numbers of the batch; got {int(Z.shape[0])}")
-        if N is not None or pbc is not None:
+        if self.periodic and (N is not None or pbc is not None):
             self.builder.set_layout(N, pbc, n_atoms=A, arrays=False)
+        elif N is not None:
+            self.builder.set_layout(N, n_atoms=A, arrays=False)
         if A < self.A:          # atoms that were real in the previous batch become filler again
             self.inputs["R"][A:self.A].copy_(self._R_fill[A:self.A])
             self.inputs["Z"][A:self.A].fill_(1)
@@ -688,14 +726,20 @@ class PaddedGraphRunner:
         """One step with the index build inside the graph: R (A, 3) float32 on the device -> (E, F) as `__call__`; `cell`
         (n_mol,3,3): the new cells of a periodic runner (the list is built for them inside the replay).  A periodic runner with
         an atom capacity also takes the sizes `N`, the species `Z` and the periodic axes `pbc` (n_mol,3) of the batch: the
-        layout is rebuilt inside the replay as well."""
+        layout is rebuilt inside the replay as well.  A molecular runner with an atom capacity
+        (`attach_builder(index_device.DeviceCapacityGraphBuilder)`) takes `N` and `Z` the same way: sizes that do not add up, a
+        molecule above the builder's `n_max` or lists beyond the capacities give NaN outputs, and the NEXT call raises."""
         if self.builder is None:
             raise RuntimeError("run_positions needs attach_builder")
-        if self.periodic and self.variable_atoms:
+        if self.variable_atoms:
+            if cell is not None and not self.periodic:
+                raise ValueError("this runner was built without a cell")
             if self.flag is not None and self.flag.tripped():
                 self.recover()
             if self.index_error():
-                raise ValueError(f"an earlier step did not fit the capacities ({self.e_cap}, {self.t_cap}, {self.quad_caps}): index error bits "
+                caps = (f"({self.e_cap}, {self.t_cap}, {self.quad_caps})" if self.periodic else
+                        f"(e_cap {self.e_cap}, t_cap {self.t_cap}, a_cap {self.a_cap}, n_max {self.builder.n_max})")
+                raise ValueError(f"an earlier step did not fit the capacities {caps}: index error bits "
                                  f"{self.index_error()}, sizes {self.index_sizes()} — its outputs were NaN; build a larger runner")
             self._load_variable(R, Z, N, pbc, "run_positions")
             if Z is not None:

@@ -55,7 +55,8 @@ class MultiWrapper:
 class Trainer:
     _SUBSTATE = ("schedulers", "optimizers", "plateau_callback", "exp_decay")
     # per-process execution state: never part of a checkpoint (the padded step holds the model, lambdas and a hipGraph)
-    _RUNTIME_ONLY = ("model", "params_except_last", "_grads", "_wgrad", "_pstep", "_padded_caps")
+    _RUNTIME_ONLY = ("model", "params_except_last", "_grads", "_wgrad", "_pstep", "_padded_caps", "_eval_caps",
+                     "_erun", "_erun_key")
 
     def __init__(self, model, learning_rate: float = 1e-3, decay_steps: int = 100000, decay_rate: float = 0.96,
                  warmup_steps: int = 0, weight_decay: float = 0.001, staircase: bool = False,
@@ -77,6 +78,8 @@ class Trainer:
         self._wgrad = None
         self._padded_caps = None     # enable_padded_graph(): capacities of the captured training step
         self._pstep = None
+        self._eval_caps = None       # enable_padded_eval(): capacities of the captured evaluation step
+        self._erun = self._erun_key = None
         self.reset_optimizer(learning_rate, weight_decay, warmup_steps, decay_steps, decay_rate, staircase,
                              decay_patience, decay_factor, decay_cooldown)
 
@@ -167,7 +170,109 @@ class Trainer:
 
     def predict_on_batch(self, dataset_iter):
         inputs, _ = next(dataset_iter)
-        return self.predict(self.dict2device(inputs))
+        padded = self._eval_caps is not None and not self.model.training
+        n_host = self._host_sizes(inputs) if padded else None
+        inputs = self.dict2device(inputs)
+        if padded:
+            outs = self._predict_padded(inputs, n_host)
+            if outs is not None:
+                return outs
+        return self.predict(inputs)
+
+    # ----------------------------------------------------------------------------- padded evaluation
+    def enable_padded_eval(self, a_cap, e_cap, t_cap, max_in_degree, n_max, n_groups=None, n_mol=None):
+        """Run eval-mode `test_on_batch` / `eval_on_batch` / `predict_on_batch` from ONE captured hipGraph although the
+        molecules of every batch have their own sizes (a loader's validation / test batches): layout, neighbour lists, index
+        plan and model are one replay of a `padded.PaddedGraphRunner` with an atom capacity and an attached
+        `index_device.DeviceCapacityGraphBuilder` — a batch needs `R`, `Z`, `N` only, index arrays it carries are ignored.
+        Triplets-only models with forces by autograd, MAE / RMSE objectives.  Batches with the loader's number of molecules
+        (`n_mol`; default: that of the first batch that fits) within `a_cap` atoms and `n_max` atoms per molecule take the
+        graph; any other batch (the partial last one, a molecule above `n_max`, another model family, `mve`) takes the plain
+        path, and so does a batch whose lists outgrow `e_cap` / `t_cap` — found by the build inside the replay; the step is
+        then repeated on the plain path.  `max_in_degree`: at least n_max - 1.  Same energies and forces as the plain path.
+        The graph is captured again whenever the parameters changed since the capture (a training step, the EMA swap)."""
+        self._eval_caps = dict(a_cap=int(a_cap), e_cap=int(e_cap), t_cap=int(t_cap), max_in_degree=int(max_in_degree),
+                               n_max=int(n_max), n_groups=n_groups, n_mol=None if n_mol is None else int(n_mol))
+        self._erun = self._erun_key = None
+
+    @staticmethod
+    def _host_sizes(inputs):
+        """The molecule sizes of a batch as a host tensor (a loader's batch is on the host: no synchronisation)."""
+        N = inputs.get("N") if hasattr(inputs, "get") else None
+        return None if N is None else N.detach().cpu()
+
+    def _eval_fits(self, inputs, n_host):
+        """Can this batch take the padded evaluation graph?  Host checks only."""
+        caps = self._eval_caps
+        if caps is None or self.mve or not self.model.triplets_only or self.model.direct_forces or n_host is None:
+            return False
+        n_mol, A = int(n_host.shape[0]), int(inputs["Z"].shape[0])
+        want = caps["n_mol"] if self._erun is None else self._erun.n_mol
+        if n_mol < 1 or (want is not None and n_mol != want) or A > caps["a_cap"] or A != int(n_host.sum()):
+            return False
+        return 1 <= int(n_host.min()) and int(n_host.max()) <= caps["n_max"]
+
+    def _weights_key(self):
+        """What the captured evaluation graph depends on besides its inputs: the parameters' versions and the model's cache of
+        derived weights (replaced on train() / eval(), cleared by the fused optimizer) — the graph reads both by address."""
+        return sum(p._version for p in self.model.parameters())
+
+    def _eval_runner(self, inputs, n_host):
+        """The runner of the padded evaluation, built with the first batch that fits (its lists come from the builder's own
+        host-sized build — once); None when that batch's lists exceed the capacities."""
+        from ..index_device import DeviceCapacityGraphBuilder
+        from ..padded import PaddedGraphRunner
+        caps = self._eval_caps
+        cache = getattr(self.model, "_wcache", None)
+        if self._erun is not None:
+            stale = self._erun_key[0] != self._weights_key() or (
+                cache is not None and (cache is not self._erun_key[1] or ("padded_eval",) not in cache))
+            if stale:                       # parameters or their derived forms changed: capture again on the next replay
+                self._erun.graph = self._erun.out = None
+                self._mark_eval_capture()
+            return self._erun
+        R, Z, N = inputs["R"], inputs["Z"], inputs["N"]
+        cutoff = float(self.model.cbf_basis3.cutoff)
+        builder = DeviceCapacityGraphBuilder(int(n_host.shape[0]), caps["a_cap"], caps["n_max"], cutoff, device=R.device)
+        builder.set_layout(n_host)
+        idx = builder(R.detach().float(), dtype=torch.int32)
+        run = PaddedGraphRunner(self.model, Z, N, caps["e_cap"], caps["t_cap"], max_in_degree=caps["max_in_degree"],
+                                n_groups=caps["n_groups"], a_cap=caps["a_cap"])
+        if not run.fits(run.sizes_of(idx)):
+            return None
+        run._fill(R.detach(), {k: idx[k] for k in ("id_c", "id_a", "id_swap", "id_undir", "id3_reduce_ca", "id3_expand_ba")}, Z, N)
+        run.attach_builder(builder)
+        self._erun = run
+        self._mark_eval_capture()
+        return run
+
+    def _mark_eval_capture(self):
+        cache = getattr(self.model, "_wcache", None)
+        if cache is not None:
+            cache[("padded_eval",)] = (0, None)     # (gone once the cache is cleared or replaced)
+        self._erun_key = (self._weights_key(), cache)
+
+    def _predict_padded(self, inputs, n_host):
+        """`predict` through the padded evaluation graph -> (E, None, F, None), or None when the batch has to take the plain
+        path (it does not fit, or the build inside the replay rejected it: the runner's index state is then reset)."""
+        if not self._eval_fits(inputs, n_host):
+            return None
+        run = self._eval_runner(inputs, n_host)
+        if run is None:
+            return None
+        E, F = run.run_positions(inputs["R"].detach(), Z=inputs["Z"], N=n_host)
+        if E.is_cuda:
+            torch.cuda.current_stream().synchronize()       # the state of the in-graph build is read on the host
+        if run.flag is not None and run.flag.tripped():
+            run.recover()                                   # (the fp16-plane range check of runtime.RangeFlag)
+            return None
+        if run.index_error():
+            run.reset_index_state()
+            return None
+        E, F = E.clone(), F.clone()                         # (the graph's static output buffers)
+        if F.dim() == 3:
+            F = F[:, 0]
+        return E, None, F, None
 
     def _world(self):
         return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -349,8 +454,12 @@ class Trainer:
     def test_on_batch(self, dataset_iter, metrics):
         self.model.eval()
         inputs, targets = next(dataset_iter)
+        n_host = self._host_sizes(inputs) if self._eval_caps is not None else None
         inputs, targets = self.dict2device(inputs), self.dict2device(targets)
-        if self.model.direct_forces:
+        outs = self._predict_padded(inputs, n_host) if self._eval_caps is not None else None
+        if outs is not None:
+            pass                         # (enable_padded_eval: layout, lists and model from one replayed graph)
+        elif self.model.direct_forces:
             with torch.no_grad():
                 outs = self.predict(inputs)
         else:
@@ -364,8 +473,10 @@ class Trainer:
     def eval_on_batch(self, dataset_iter):
         self.model.eval()
         inputs, targets = next(dataset_iter)
+        n_host = self._host_sizes(inputs) if self._eval_caps is not None else None
         inputs, targets = self.dict2device(inputs), self.dict2device(targets)
-        energy, _, forces, _ = self.predict(inputs)
+        outs = self._predict_padded(inputs, n_host) if self._eval_caps is not None else None
+        energy, _, forces, _ = outs if outs is not None else self.predict(inputs)
         return (energy.detach(), forces.detach()), targets
 
     # ------------------------------------------------------------------------------------ checkpoints

@@ -435,7 +435,27 @@ int gn_index_gpu_padded_t(const void* R, int r_is_f64, const int32_t* mol_off, c
                           int deg_bound, int32_t* staging, int32_t* id_c, int32_t* id_a, int32_t* id_swap, int32_t* id_undir,
                           int32_t* id3_reduce_ca, int32_t* id3_expand_ba, int32_t* state, void* stream);
 int gn_index_poison_f32(float* x, int64_t n, const int32_t* state, void* stream);
-/* The same for quadruplet models (data_container.py:427-489 as well): five families with their capacities e_cap, t_cap,
+/* Atom capacity for molecules (csrc/index_gpu.hip; additive, ABI 16): n_mol molecules per batch whose sizes N and species change
+ * from replay to replay of ONE graph — a loader's batches.  Atom rows [0, A) are the batch (A = sum N), [A, a_cap) filler atoms
+ * of the dummy molecule n_mol, [a_cap, a_tot) the dummy groups of gemnet_pytorch_amd/padded.py.  n_max: capacity of ONE
+ * molecule; a_cap * n_max <= 2^31 - 1 bounds the bytes of the n x n adjacency blocks (anything larger is rejected on the host).
+ *   gn_index_gpu_layout: gn_pbc_layout (below; the same kernels) plus sq_off (n_mol + 1) int32, the exclusive scan of N_b^2, and
+ *     one more error case: err bit 128 when sum N != n_atoms, some N_b < 1, sum N > a_cap or some N_b > n_max -> state[0] |= 128,
+ *     state[3] = 128 and NO array is written; a valid layout sets state[3] = 0.  Requires n_mol <= a_cap <= a_tot.
+ *   gn_index_gpu_padded_tv: gn_index_gpu_padded_t over a_cap atom rows and n_mol molecules with the layout above, read at replay
+ *     time (mol_off (n_mol + 2), sq_off (n_mol + 1), atom_mol (a_cap)).  R (a_cap,3).  Grids and workspace are sized by the
+ *     capacities: ws of gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, 1) bytes (sum_n2 = a_cap * n_max).  A filler atom
+ *     (atom_mol == n_mol) has degree 0 and its position is never read.  Real rows, pad rows and state[0..3] as
+ *     gn_index_gpu_padded_t for the batch on its own, bit for bit.  When the layout call of the same step set bit 128, nothing
+ *     the model reads and no word of state[] is written. */
+int gn_index_gpu_layout(const int32_t* N, const int32_t* n_atoms, int n_mol, int a_cap, int a_tot, int n_max, int32_t* mol_off,
+                        int32_t* sq_off, int32_t* atom_mol, int64_t* batch_seg, int64_t* N_pad, float* mask, int32_t* state,
+                        void* stream);
+int gn_index_gpu_padded_tv(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, const int32_t* atom_mol,
+                           int n_mol, int n_max, double cutoff, void* ws, int e_cap, int t_cap, int a_cap, int n_groups,
+                           int deg_bound, int32_t* staging, int32_t* id_c, int32_t* id_a, int32_t* id_swap, int32_t* id_undir,
+                           int32_t* id3_reduce_ca, int32_t* id3_expand_ba, int32_t* state, void* stream);
+/* gn_index_gpu_padded_t for quadruplet models (data_container.py:427-489 as well): five families with their capacities e_cap, t_cap,
  * eint_cap, i_cap, q_cap; arrays (host array of 16 device pointers) = id_c, id_a, id_swap, id_undir, id3_reduce_ca,
  * id3_expand_ba, id4_int_a, id4_int_b, id4_reduce_intm_ca, id4_expand_intm_db, id4_reduce_intm_ab, id4_expand_intm_ab,
  * id4_reduce_ca, id4_expand_db, id4_reduce_cab, id4_expand_abd — each of its family's capacity; staging: 4 e_cap + 2 eint_cap
