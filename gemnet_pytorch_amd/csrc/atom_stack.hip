@@ -83,165 +83,17 @@ struct as_fwd_args {
   int pitch;                       // grouped launch: rows between the groups' slabs of x, z, y
 };
 
-template <int L, int T, bool RES2>
-__global__ __launch_bounds__(NT) void atom_stack_fwd_kernel(const as_fwd_args P) {
-  static_assert(L >= 0 && L <= 2 && T >= 0 && T <= 2 && (!RES2 || L > 0), "programs of the atom stack");
-  constexpr int NM = 1 + 2 * L;              // GEMM ops that write the tile
-  constexpr int NG = NM + T;
-  constexpr int PLANE = 16 * ROWB;           // bytes of one plane
-  constexpr int SLOT = 2 * PLANE;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * SLOT];
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int l15 = lane & 15;
-  const int lg = lane >> 4;
-  const int M = P.M;
-  const int row0 = (int)blockIdx.x * 16;
-
-  // weight fragments: [op][k-chunk][plane]; packed layout [col tile][k-chunk][plane][lane][8 fp16]
-  uint4 w[NG][4][2];
-  auto wload = [&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    if constexpr (j < NG) {
-      const uint4* __restrict__ const base = P.W[j] + (size_t)wave * (4 * 2 * 64) + lane;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) w[j][c][p] = AS_EXP == 1 ? make_uint4(0x3c003c00u + lane, 0u, 0u, 0u) : base[(c * 2 + p) * 64];
-    }
-  };
-  // the tile's rows are requested first: returns are in order, and the LOAD below must not wait behind the weight sets
-  const int lr = tid >> 5, lc = (tid & 31) << 2;      // 16 rows x 32 float4 = one float4 per thread
-  float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (row0 + lr < M) xv = *reinterpret_cast<const float4*>(P.x + (size_t)(row0 + lr) * SW + lc);
-  wload(std::integral_constant<int, 0>{});
-  if constexpr (AS_AHEAD > 1) wload(std::integral_constant<int, 1>{});
-  if constexpr (AS_AHEAD > 2) wload(std::integral_constant<int, 2>{});
-  if constexpr (AS_AHEAD > 3) wload(std::integral_constant<int, 3>{});
-  if constexpr (AS_AHEAD > 4) wload(std::integral_constant<int, 4>{});
-  if constexpr (AS_AHEAD > 5) wload(std::integral_constant<int, 5>{});
-  if constexpr (AS_AHEAD > 6) wload(std::integral_constant<int, 6>{});
-
-  auto plane_ptr = [&](int slot, int p) -> unsigned char* { return smem + slot * SLOT + p * PLANE; };
-  // byte offset of columns col .. col+3 (col % 4 == 0) of row `row` inside a plane (the swizzle of chain2.hip)
-  auto sw_off = [&](int row, int col) -> int { return row * ROWB + ((((col >> 3) ^ row) & 15) << 4) + ((col & 4) << 1); };
-  auto slot_write = [&](int slot, int row, int col, const float4 v) {
-    const int off = sw_off(row, col);
-    uint2 H, Lo;
-    split4h(v, H, Lo);
-    *reinterpret_cast<uint2*>(plane_ptr(slot, 0) + off) = H;
-    *reinterpret_cast<uint2*>(plane_ptr(slot, 1) + off) = Lo;
-  };
-
-  // LOAD: rows past M are zero
-  slot_write(0, lr, lc, xv);
-  lds_barrier();
-
-  // accumulator layout of this lane: row l15 of the tile, columns 16 wave + 4 lg .. + 3
-  const int n0 = wave * 16 + (lg << 2);
-  const bool ok = row0 + l15 < M;
-  const uint32_t off = (uint32_t)(row0 + l15) * (uint32_t)SW + (uint32_t)n0;   // M <= 4 096 rows
-  const int my = sw_off(l15, n0);
-
-  auto gemm = [&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    constexpr bool tail = j >= NM;
-    constexpr bool second = !tail && j > 0 && (j & 1) == 0;     // second GEMM of a ResidualLayer: residual, scale
-    constexpr bool last = j == NM - 1;
-    constexpr int a_slot = tail ? 1 : (j & 1);
-    constexpr int y_slot = a_slot ^ 1;
-    // every operand of the op is requested before its first MFMA
-    uint4 xf[4][2];
-    {
-      const unsigned char* xb = smem + a_slot * SLOT + l15 * ROWB;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const unsigned char* xp = xb + ((((c << 2) | lg) ^ l15) << 4);
-        xf[c][0] = *reinterpret_cast<const uint4*>(xp);
-        xf[c][1] = *reinterpret_cast<const uint4*>(xp + PLANE);
-      }
-    }
-    uint2 rH = make_uint2(0u, 0u), rL = make_uint2(0u, 0u);
-    if constexpr (second) {
-      rH = *reinterpret_cast<const uint2*>(plane_ptr(y_slot, 0) + my);
-      rL = *reinterpret_cast<const uint2*>(plane_ptr(y_slot, 1) + my);
-    }
-    float4 q2 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (last && RES2) {
-      if (ok) q2 = *reinterpret_cast<const float4*>(P.res2 + off);
-    }
-    v4f acc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, w[j][c][0]), al = __builtin_bit_cast(f16x8, w[j][c][1]);
-      const f16x8 yh = __builtin_bit_cast(f16x8, xf[c][0]), yl = __builtin_bit_cast(f16x8, xf[c][1]);
-      if constexpr (AS_EXP == 3) {      // (the operands stay live: one add per fragment)
-        acc[0][0] += __uint_as_float(w[j][c][0].x ^ xf[c][0].x); acc[1][0] += __uint_as_float(w[j][c][0].y ^ xf[c][1].y);
-        acc[2][0] += __uint_as_float(w[j][c][1].z ^ xf[c][0].z);
-        continue;
-      }
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl, acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh, acc[2], 0, 0, 0);
-    }
-    const v4f corr = acc[1] + acc[2];
-    float4 v = make_float4(as_fma(corr[0], H_DOWN, acc[0][0]), as_fma(corr[1], H_DOWN, acc[0][1]),
-                           as_fma(corr[2], H_DOWN, acc[0][2]), as_fma(corr[3], H_DOWN, acc[0][3]));
-    wload(std::integral_constant<int, j + AS_AHEAD>{});     // this op's fragments are dead
-    if constexpr (tail) {
-      if (ok) *reinterpret_cast<float4*>(P.t[j - NM] + off) = v;
-    } else {
-      // the activation and its derivative from one sigmoid; the factor is what the adjoint multiplies by
-      float4 d;
-      if constexpr (AS_EXP == 2) {
-        d = v;
-      } else {
-        as_ssilu_pair(v.x, v.x, d.x); as_ssilu_pair(v.y, v.y, d.y);
-        as_ssilu_pair(v.z, v.z, d.z); as_ssilu_pair(v.w, v.w, d.w);
-      }
-      if (ok) *reinterpret_cast<float4*>(P.z[j] + off) = d;
-      if constexpr (second) {
-        const float4 q = join4h(rH, rL);
-        const float b = P.s;
-        v.x = (v.x + q.x) * b; v.y = (v.y + q.y) * b; v.z = (v.z + q.z) * b; v.w = (v.w + q.w) * b;
-      }
-      if constexpr (last && RES2) {
-        if (ok) {
-          const float b = P.beta2;
-          v.x = (v.x + q2.x) * b; v.y = (v.y + q2.y) * b; v.z = (v.z + q2.z) * b; v.w = (v.w + q2.w) * b;
-        }
-      }
-      if constexpr (last) {
-        if (ok) *reinterpret_cast<float4*>(P.y + off) = v;
-      }
-      if constexpr (!last || T > 0) {      // somebody reads the tile again
-        slot_write(y_slot, l15, n0, ok ? v : make_float4(0.f, 0.f, 0.f, 0.f));
-        if constexpr (AS_EXP != 4) lds_barrier();
-      }
-    }
-  };
-  gemm(std::integral_constant<int, 0>{});
-  if constexpr (NG > 1) gemm(std::integral_constant<int, 1>{});
-  if constexpr (NG > 2) gemm(std::integral_constant<int, 2>{});
-  if constexpr (NG > 3) gemm(std::integral_constant<int, 3>{});
-  if constexpr (NG > 4) gemm(std::integral_constant<int, 4>{});
-  if constexpr (NG > 5) gemm(std::integral_constant<int, 5>{});
-  if constexpr (NG > 6) gemm(std::integral_constant<int, 6>{});
-}
-
-// The same kernel for the grouped launch (gn_atom_stack_fwd_grouped_f32), an overload of its own so that the instances above keep
-// their code and register counts.  GR: blockIdx.y is the group, whose rows lie P.pitch rows and whose packed weights one weight
+// One template for the single and the grouped launch.  L ResidualLayers, T tails, RES2: the final global skip.
+// GR (gn_atom_stack_fwd_grouped_f32): blockIdx.y is the group, whose rows lie P.pitch rows and whose packed weights one weight
 // behind those of the group before; a tile never spans two groups (rows >= M are masked as ever).
-// RT: 16-row tiles of one workgroup (AS_GROUP_TILES, by default 2 — every weight fragment is fetched once for both, DESIGN.md
-// section 27); each tile has its own two LDS slots and its own accumulators, a row's arithmetic does not know about the other tile
+// RT: 16-row tiles of one workgroup: 1 in the single launch, AS_GROUP_TILES (by default 2 — every weight fragment is fetched once
+// for both) in the grouped one; each tile has its own two LDS slots and its own accumulators, a row's
+// arithmetic does not know about the other tile.  With GR = false, RT = 1 every [r] below is a scalar and rg, wg are 0.
 template <int L, int T, bool RES2, bool GR, int RT>
 __global__ __launch_bounds__(NT) void atom_stack_fwd_kernel(const as_fwd_args P) {
   static_assert(L >= 0 && L <= 2 && T >= 0 && T <= 2 && (!RES2 || L > 0), "programs of the atom stack");
   static_assert(!GR || (L >= 1 && T == 0 && !RES2), "programs of the grouped output blocks");
-  static_assert(GR && (RT == 1 || RT == 2), "the grouped launch: one or two row tiles");
+  static_assert(RT == 1 || (GR && RT == 2), "one row tile, or two in the grouped launch");
   constexpr int NM = 1 + 2 * L;              // GEMM ops that write the tile
   constexpr int NG = NM + T;
   constexpr int PLANE = 16 * ROWB;           // bytes of one plane
@@ -422,7 +274,7 @@ __global__ __launch_bounds__(NT) void atom_stack_fwd_kernel(const as_fwd_args P)
 
 template <int L, int T, bool RES2>
 int launch_fwd(const as_fwd_args& a, hipStream_t st) {
-  hipLaunchKernelGGL((atom_stack_fwd_kernel<L, T, RES2>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
+  hipLaunchKernelGGL((atom_stack_fwd_kernel<L, T, RES2, false, 1>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
   GN_LAUNCH_CHECK();
   return 0;
 }
@@ -498,223 +350,16 @@ struct as_bwd_args {
 
 __device__ __forceinline__ float4 as_mul4(const float4 v, const float a) { return make_float4(v.x * a, v.y * a, v.z * a, v.w * a); }
 
-// L ResidualLayers, T tails, A: the skip gradient is an output of its own (SCALE ops stay stand-alone in the fused program)
-template <int L, int T, bool A>
-__global__ __launch_bounds__(NT) void atom_stack_bwd_kernel(const as_bwd_args P) {
-  static_assert(L >= 1 && L <= 2 && (T == 0 || T == 2), "adjoint programs of the atom stack");
-  constexpr int NG = T + 2 * L + 1;
-  constexpr int PLANE = 16 * ROWB;
-  constexpr int SLOT = 2 * PLANE;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * SLOT];     // G (once, to change layout) | X0 X1 X2
-  __shared__ float rs[3][16];                                               // row scales of the LOADs: g, gt[0], gt[1]
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int l15 = lane & 15;
-  const int lg = lane >> 4;
-  const int M = P.M;
-  const int row0 = (int)blockIdx.x * 16;
-
-  uint4 w[NG][4][2];
-  auto wload = [&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    if constexpr (j < NG) {
-      const uint4* __restrict__ const base = P.W[j] + (size_t)wave * (4 * 2 * 64) + lane;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) w[j][c][p] = AS_BWD_EXP == 1 ? make_uint4(0x3c003c00u + lane, 0u, 0u, 0u) : base[(c * 2 + p) * 64];
-    }
-  };
-  auto plane_ptr = [&](int buf, int p) -> unsigned char* { return smem + buf * SLOT + p * PLANE; };      // buf 0: G, 1 + i: X_i
-  auto sw_off = [&](int row, int col) -> int { return row * ROWB + ((((col >> 3) ^ row) & 15) << 4) + ((col & 4) << 1); };
-  auto put_planes = [&](int buf, int off, const uint2 H, const uint2 Lo) {
-    *reinterpret_cast<uint2*>(plane_ptr(buf, 0) + off) = H;
-    *reinterpret_cast<uint2*>(plane_ptr(buf, 1) + off) = Lo;
-  };
-  auto sigma_of = [&](const float4 v) -> float {      // row scale of a LOAD: one row = 32 consecutive lanes
-    if constexpr (AS_BWD_EXP == 3) return 1.f;
-    const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-    return row_sigma(group_max(m, 32));
-  };
-  // a stand-alone SCALE of the interpreter on planes held in registers: read (join), * alpha / sigma, [* Z]; the caller
-  // stores the true-scale value where the op has an output and splits value * sigma again
-  auto scale_read = [&](const uint2 H, const uint2 Lo, const float alpha, const float sc) -> float4 {
-    return as_mul4(join4h(H, Lo), alpha * inv_pow2(sc));
-  };
-
-  // ---- the LOADs (linear layout: 16 rows x 32 float4, one per thread); the rows are requested first
-  const int lr = tid >> 5, lc = (tid & 31) << 2;
-  const bool in = row0 + lr < M;
-  const size_t loff = (size_t)(row0 + lr) * SW + lc;
-  float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), tv0 = gv, tv1 = gv, zv = gv;
-  if (in) {
-    gv = *reinterpret_cast<const float4*>(P.g + loff);
-    if constexpr (T > 0) tv0 = *reinterpret_cast<const float4*>(P.gt[0] + loff);
-    if constexpr (T > 1) tv1 = *reinterpret_cast<const float4*>(P.gt[1] + loff);
-    if constexpr (T == 0) zv = AS_BWD_EXP == 2 ? make_float4(1.f, 1.f, 1.f, 1.f) : *reinterpret_cast<const float4*>(P.F[0] + loff);
-  }
-  wload(std::integral_constant<int, 0>{});
-  if constexpr (AS_BWD_AHEAD > 1) wload(std::integral_constant<int, 1>{});
-  if constexpr (AS_BWD_AHEAD > 2) wload(std::integral_constant<int, 2>{});
-  {
-    const int o = sw_off(lr, lc);
-    const float4 v = as_mul4(gv, P.alpha0);
-    const float sig = sigma_of(v);
-    uint2 H, Lo;
-    split4h(as_mul4(v, sig), H, Lo);
-    if (lc == 0) rs[0][lr] = sig;
-    if constexpr (T == 0) {
-      if constexpr (A) {
-        // SCALE 0 <- 0 * a_out with the skip gradient as its output, SCALE 0 <- 0 * a_s, SCALE 1 <- 0 * Z
-        float4 u = scale_read(H, Lo, P.a_out, sig);
-        if (in) *reinterpret_cast<float4*>(P.g_skip + loff) = u;
-        split4h(as_mul4(u, sig), H, Lo);
-        u = scale_read(H, Lo, P.a_s, sig);
-        split4h(as_mul4(u, sig), H, Lo);
-        put_planes(0, o, H, Lo);
-        u = scale_read(H, Lo, 1.f, sig);
-        if (in) { u.x *= zv.x; u.y *= zv.y; u.z *= zv.z; u.w *= zv.w; }
-        split4h(as_mul4(u, sig), H, Lo);
-        put_planes(1, o, H, Lo);
-      } else {
-        // the LOAD's second tensor: v * alpha2 (1) * Z2
-        put_planes(0, o, H, Lo);
-        float4 u = v;
-        if (in) { u.x *= zv.x; u.y *= zv.y; u.z *= zv.z; u.w *= zv.w; }
-        split4h(as_mul4(u, sig), H, Lo);
-        put_planes(1, o, H, Lo);
-      }
-    } else {
-      put_planes(0, o, H, Lo);
-      const float s0 = sigma_of(tv0);
-      split4h(as_mul4(tv0, s0), H, Lo);
-      put_planes(1, o, H, Lo);
-      if (lc == 0) rs[1][lr] = s0;
-      if constexpr (T > 1) {
-        const float s1 = sigma_of(tv1);
-        split4h(as_mul4(tv1, s1), H, Lo);
-        put_planes(2, o, H, Lo);
-        if (lc == 0) rs[2][lr] = s1;
-      }
-    }
-  }
-  lds_barrier();
-
-  // accumulator layout of this lane: row l15 of the tile, columns 16 wave + 4 lg .. + 3
-  const int n0 = wave * 16 + (lg << 2);
-  const bool ok = row0 + l15 < M;
-  const uint32_t off = (uint32_t)(row0 + l15) * (uint32_t)SW + (uint32_t)n0;   // M <= 4 096 rows
-  const int my = sw_off(l15, n0);
-  // G: its planes and its row scale, from here on in registers; rs1: the row scale of X
-  uint2 GH = *reinterpret_cast<const uint2*>(plane_ptr(0, 0) + my), GL = *reinterpret_cast<const uint2*>(plane_ptr(0, 1) + my);
-  float rs0 = rs[0][l15], rs1 = rs0;
-
-  auto gemm = [&](auto jc) {
-    constexpr int j = decltype(jc)::value;
-    constexpr bool tail = j < T;
-    constexpr bool fin = j == NG - 1;
-    constexpr int m = j - T;                                       // main GEMMs: even = first of a layer's adjoint (mul), odd = second
-    constexpr bool mulop = !tail && !fin && (m & 1) == 0;
-    constexpr bool resop = tail || (!fin && (m & 1) == 1);         // (. + G) * beta
-    constexpr bool scales = tail && j == T - 1 && A;               // out = g_skip and the two SCALE ops
-    constexpr bool second = resop && !scales && !(tail && j < T - 1);      // second output Z2 * v -> X
-    constexpr int fi = tail ? 0 : 1 + m;                           // stored factor of this op
-    constexpr bool factor = mulop || second || scales;
-    constexpr int a_buf = 1 + j % 3, y_buf = 1 + (j + 1) % 3;
-    // every operand of the op is requested before its first MFMA
-    uint4 xf[4][2];
-    {
-      const unsigned char* xb = smem + a_buf * SLOT + l15 * ROWB;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const unsigned char* xp = xb + ((((c << 2) | lg) ^ l15) << 4);
-        xf[c][0] = *reinterpret_cast<const uint4*>(xp);
-        xf[c][1] = *reinterpret_cast<const uint4*>(xp + PLANE);
-      }
-    }
-    float sa = rs1;
-    if constexpr (tail) sa = rs[1 + j][l15];
-    float4 fz = mulop ? make_float4(1.f, 1.f, 1.f, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (factor) {
-      if (ok) fz = AS_BWD_EXP == 2 ? make_float4(1.f, 1.f, 1.f, 1.f) : *reinterpret_cast<const float4*>(P.F[fi] + off);
-    }
-    v4f acc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, w[j][c][0]), al = __builtin_bit_cast(f16x8, w[j][c][1]);
-      const f16x8 yh = __builtin_bit_cast(f16x8, xf[c][0]), yl = __builtin_bit_cast(f16x8, xf[c][1]);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl, acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh, acc[2], 0, 0, 0);
-    }
-    const v4f corr = acc[1] + acc[2];
-    float4 v = make_float4(as_fma(corr[0], H_DOWN, acc[0][0]), as_fma(corr[1], H_DOWN, acc[0][1]),
-                           as_fma(corr[2], H_DOWN, acc[0][2]), as_fma(corr[3], H_DOWN, acc[0][3]));
-    wload(std::integral_constant<int, j + AS_BWD_AHEAD>{});     // this op's fragments are dead
-    v = as_mul4(v, inv_pow2(sa));                               // the products are sigma(operand) times the true values
-    if constexpr (fin) {
-      if (ok) *reinterpret_cast<float4*>(P.gx + off) = v;
-    } else if constexpr (mulop) {
-      v.x *= fz.x; v.y *= fz.y; v.z *= fz.z; v.w *= fz.w;
-      uint2 H, Lo;
-      split4h(ok ? as_mul4(v, sa) : make_float4(0.f, 0.f, 0.f, 0.f), H, Lo);
-      put_planes(y_buf, my, H, Lo);
-      rs1 = sa;
-      if constexpr (AS_BWD_EXP != 4) lds_barrier();
-    } else {
-      // what the op leaves behind takes the smaller scale (the larger magnitude) of its operand and of G
-      const float sy = fminf(sa, rs0);
-      const float4 q = as_mul4(join4h(GH, GL), inv_pow2(rs0));
-      const float b = tail ? P.bt[tail ? j : 0] : P.bl[tail ? 0 : (m >> 1)];
-      v.x = (v.x + q.x) * b; v.y = (v.y + q.y) * b; v.z = (v.z + q.z) * b; v.w = (v.w + q.w) * b;
-      if constexpr (scales) {
-        if (ok) *reinterpret_cast<float4*>(P.g_skip + off) = v;
-      }
-      split4h(ok ? as_mul4(v, sy) : make_float4(0.f, 0.f, 0.f, 0.f), GH, GL);
-      rs0 = sy;
-      if constexpr (scales) {
-        // SCALE 0 <- 0 * a_s and SCALE 1 <- 0 * Z of the interpreter, on the planes just written
-        float4 u = scale_read(GH, GL, P.a_s, sy);
-        split4h(as_mul4(u, sy), GH, GL);
-        u = scale_read(GH, GL, 1.f, sy);
-        if (ok) { u.x *= fz.x; u.y *= fz.y; u.z *= fz.z; u.w *= fz.w; }
-        uint2 H, Lo;
-        split4h(as_mul4(u, sy), H, Lo);
-        put_planes(y_buf, my, H, Lo);
-      } else if constexpr (second) {
-        float4 u = fz;
-        u.x *= v.x; u.y *= v.y; u.z *= v.z; u.w *= v.w;
-        uint2 H, Lo;
-        split4h(ok ? as_mul4(u, sy) : make_float4(0.f, 0.f, 0.f, 0.f), H, Lo);
-        put_planes(y_buf, my, H, Lo);
-      }
-      if constexpr (scales || second) {
-        rs1 = sy;
-        if constexpr (AS_BWD_EXP != 4) lds_barrier();
-      }
-    }
-  };
-  gemm(std::integral_constant<int, 0>{});
-  gemm(std::integral_constant<int, 1>{});
-  gemm(std::integral_constant<int, 2>{});
-  if constexpr (NG > 3) gemm(std::integral_constant<int, 3>{});
-  if constexpr (NG > 4) gemm(std::integral_constant<int, 4>{});
-  if constexpr (NG > 5) gemm(std::integral_constant<int, 5>{});
-  if constexpr (NG > 6) gemm(std::integral_constant<int, 6>{});
-}
-
-// The same kernel for the grouped launch (gn_atom_stack_bwd_grouped_f32), an overload of its own like the forward's.  GR: groups
-// laid out as in the forward; SEED: the cotangent is not a tensor
-// but the product the energy head's adjoint would have written, formed here from g_E (M,1) and w_out (groups,128); RT: 16-row
-// tiles of one workgroup as in the forward (every tile has its own four LDS tiles, row scales and G registers)
+// One template for the single and the grouped launch, as in the forward.  L ResidualLayers, T tails, A: the skip gradient is an
+// output of its own (SCALE ops stay stand-alone in the fused program).  GR (gn_atom_stack_bwd_grouped_f32): groups laid out as in
+// the forward; SEED: the cotangent is not a tensor but the product the energy head's adjoint would have written, formed here
+// from g_E (M,1) and w_out (groups,128); RT: 16-row tiles of one workgroup as in the forward (every tile has its own four LDS
+// tiles, row scales and G registers)
 template <int L, int T, bool A, bool GR, bool SEED, int RT>
 __global__ __launch_bounds__(NT) void atom_stack_bwd_kernel(const as_bwd_args P) {
   static_assert(L >= 1 && L <= 2 && (T == 0 || T == 2), "adjoint programs of the atom stack");
   static_assert((!GR || (T == 0 && !A)) && (!SEED || GR), "adjoint programs of the grouped output blocks");
-  static_assert(GR && (RT == 1 || RT == 2), "the grouped launch: one or two row tiles");
+  static_assert(RT == 1 || (GR && RT == 2), "one row tile, or two in the grouped launch");
   constexpr int NG = T + 2 * L + 1;
   constexpr int PLANE = 16 * ROWB;
   constexpr int SLOT = 2 * PLANE;
@@ -963,7 +608,7 @@ __global__ __launch_bounds__(NT) void atom_stack_bwd_kernel(const as_bwd_args P)
 
 template <int L, int T, bool A>
 int launch_bwd(const as_bwd_args& a, hipStream_t st) {
-  hipLaunchKernelGGL((atom_stack_bwd_kernel<L, T, A>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
+  hipLaunchKernelGGL((atom_stack_bwd_kernel<L, T, A, false, false, 1>), dim3((unsigned)gn_cdiv(a.M, 16)), dim3(NT), 0, st, a);
   GN_LAUNCH_CHECK();
   return 0;
 }

@@ -1525,6 +1525,19 @@ def pack_weight_split(W, trans=False, fmt=None):
     return out
 
 
+def _op_planes(o, mode, fmt):
+    """The weight planes of GEMM op `o` for a launch in `mode` (format `fmt`): its `packed`, which must be in that format (`W`
+    then only carries the shape, any strides), or `W` packed now."""
+    Wp = o.get("packed")
+    if Wp is None:
+        _mat(o["W"])
+        return pack_weight_split(o["W"], fmt=fmt)
+    if getattr(Wp, "_gn_fmt", 0) != fmt:
+        raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a launch in "
+                           f"mode {mode!r} (format {fmt})")
+    return Wp
+
+
 def pack_job_table(entries):
     """Device job table (gn_pack_job) for `pack_weight_split_grouped`: entries = [(W, trans, packed uint8 tensor)]; the
     format of each job is the one its buffer was first packed in (`packed._gn_fmt`).
@@ -1768,18 +1781,8 @@ def _atom_fwd_match(prog, mode):
 
 def _atom_stack_fwd(M, m):
     """Launch gn_atom_stack_fwd_f32 for a matched program (atom_stack_match)."""
-    fmt = SPLIT_FORMAT["h3"]
     require_device(m["x"], m["y"], m["res2"], *m["z"], *m["t"])
-    Ws = []
-    for g in m["gemms"]:
-        Wp = g.get("packed")
-        if Wp is None:
-            _mat(g["W"])
-            Wp = pack_weight_split(g["W"], fmt=fmt)
-        elif getattr(Wp, "_gn_fmt", 0) != fmt:
-            raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a launch in "
-                               f"mode 'h3' (format {fmt})")
-        Ws.append(Wp)
+    Ws = [_op_planes(g, "h3", SPLIT_FORMAT["h3"]) for g in m["gemms"]]
     z, t = m["z"], m["t"]
     arr = ctypes.c_void_p
     check(_lib.load().gn_atom_stack_fwd_f32(ptr(m["x"]), int(M), int(m["L"]), len(t), (arr * len(Ws))(*[addr(W) for W in Ws]),
@@ -1907,18 +1910,8 @@ def _atom_adjoint_match(prog, mode, seeded=False):
 
 def _atom_stack_bwd(M, m):
     """Launch gn_atom_stack_bwd_f32 for a matched program (atom_stack_adjoint_match)."""
-    fmt = SPLIT_FORMAT["h3"]
     require_device(m["g"], m["gx"], m["g_skip"], *m["gt"], *m["F"])
-    Ws = []
-    for g in m["gemms"]:
-        Wp = g.get("packed")
-        if Wp is None:
-            _mat(g["W"])
-            Wp = pack_weight_split(g["W"], fmt=fmt)
-        elif getattr(Wp, "_gn_fmt", 0) != fmt:
-            raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a launch in "
-                               f"mode 'h3' (format {fmt})")
-        Ws.append(Wp)
+    Ws = [_op_planes(g, "h3", SPLIT_FORMAT["h3"]) for g in m["gemms"]]
     gt, F = m["gt"], m["F"]
     arr = ctypes.c_void_p
     check(_lib.load().gn_atom_stack_bwd_f32(ptr(m["g"]), int(M), int(m["L"]), len(gt), int(m["form"]),
@@ -2057,13 +2050,7 @@ def chain(prog, mode=None, groups=0, group_pitch=0, tile_rows=None):
             W = o["W"]
             N, Kd = W.shape
             if nprod:
-                Wp = o.get("packed")     # with the packed planes given, `W` only carries the shape (any strides)
-                if Wp is None:
-                    _mat(W)
-                    Wp = pack_weight_split(W, fmt=fmt)
-                elif getattr(Wp, "_gn_fmt", 0) != fmt:
-                    raise RuntimeError(f"chain: weight planes packed in format {getattr(Wp, '_gn_fmt', 0)} handed to a "
-                                       f"launch in mode {mode!r} (format {fmt})")
+                Wp = _op_planes(o, mode, fmt)
                 keep.append(Wp)
                 v[F_W] = addr(Wp)
             else:

@@ -297,6 +297,40 @@ def test_adjoint_is_bit_equal_to_the_grouped_chain_launch(case, L, G, monkeypatc
 
 
 @gpu
+@pytest.mark.parametrize("L", LS)
+def test_one_group_is_bit_equal_to_the_single_launch(case, L, monkeypatch, redzone):      # noqa: F811
+    """The grouped launch with G = 1 and the single launch of the same program (forward: T = 0, no skip; adjoint: T = 0, no skip
+    gradient) are two instances of one kernel template: y, every factor and g_x agree bit for bit.  1 row: one partial tile;
+    17: a tile pair whose second half is empty; 33: two pairs."""
+    single = []
+    for name in ("_atom_stack_fwd", "_atom_stack_bwd"):
+        launch = getattr(K, name)
+        monkeypatch.setattr(K, name, lambda M, m, name=name, launch=launch: (single.append(name), launch(M, m))[1])
+    monkeypatch.setattr(K, "USE_ATOM_STACK", True)
+    monkeypatch.setattr(K, "USE_ATOM_STACK_BWD", True)
+    Wd, pk, _ = _weights(case, L, [0])
+    for A in (1, 17, 33):
+        grouped = _fwd(case, L, A, [0], True, monkeypatch)
+        outs = [torch.full((1, A, C), SENTINEL, device=DEV) for _ in range(2 + 2 * L)]
+        xs = put(case.x[:1, :A].contiguous())
+        n0 = redzone.n_launches
+        K.chain(_forward(A, xs[0], [row[0] for row in Wd], pk, [z[0] for z in outs[:-1]], outs[-1][0], L), mode="h3")
+        torch.cuda.synchronize()
+        assert redzone.n_launches - n0 == 1 and single == ["_atom_stack_fwd"]
+        for i, (a, b) in enumerate(zip(grouped, outs)):
+            assert a.shape == b.shape == (1, A, C) and _same(a, b) and not bool((b == SENTINEL).any()), (L, A, "output", i)
+        grouped = _bwd(case, L, A, [0], True, monkeypatch)
+        p, gx, keep = _bwd_program(case, L, A, [0], monkeypatch)
+        n0 = redzone.n_launches
+        K.chain(p, mode="h3")
+        torch.cuda.synchronize()
+        assert redzone.n_launches - n0 == 1 and single == ["_atom_stack_fwd", "_atom_stack_bwd"]
+        assert grouped.shape == gx.shape == (1, A, C) and _same(grouped, gx) and torch.equal(grouped, gx), (L, A)
+        assert bool(torch.isfinite(gx).all()) and not bool((gx == SENTINEL).any())
+        single.clear()
+
+
+@gpu
 def test_rows_between_the_groups_are_not_touched(case, monkeypatch, redzone):      # noqa: F811
     """group_pitch > A: the eight rows behind every group's 17 belong to nobody and keep their sentinel."""
     L, G, A, pitch = 2, 2, 17, 25
