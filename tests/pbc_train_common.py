@@ -23,6 +23,9 @@ from oracle import gemnet_oracle as GO
 from oracle import index_oracle as IO
 
 KINDS = ["small", "triclinic", "slab", "cubic1"]
+# cells with a height below the cutoff (self-image edges, image ranges up to |n| = 3, image distances below 1 A, exactly collinear
+# triplets) and one with det < 0: tests/test_pbc_train_cells_cpu.py, tests/test_gpu_pbc_train_cells.py
+HARD = ("bcc_pert", "thin", "skewed", "skewed_lh")
 RHO_FORCE, RHO_STRESS = 0.9, 0.05
 # the widths for which kernels.bil_train_supported(S, C, I) holds (S = 7, C = emb_size_trip = 64, I = emb_size_cbf = 16) and the
 # Dense stacks are 128 wide; everything that is not a width as in pbc_common.CFG (the cluster oracle reads widths off the weights)
@@ -98,18 +101,47 @@ def loss_fp64(E, F, S, Et, Ft, St, rho_force=RHO_FORCE, rho_stress=RHO_STRESS):
             + rho_stress * torch.linalg.vector_norm((S - St).reshape(B, 9), dim=1).sum() / B)
 
 
-def oracle(params, cfg, structs, names, rho_force=RHO_FORCE, rho_stress=RHO_STRESS):
-    """-> dict(E (B,1), F (A,3), S (B,3,3), Et, Ft, St, loss, grads {name: tensor}, trunc): the reference of the training step."""
+def hard_structures(kinds=HARD):
+    """The structures of `kinds` as pbc_common.structure gives them (seed 0: the cells of tests/test_gpu_pbc_cases.py)."""
+    return [P.structure(k) for k in kinds]
+
+
+def collinear_rows(structs):
+    """Edge vectors and triplets of the float32-rounded structures from the brute-force list -> (V float32 (E,3), index dict,
+    cells float64 (B,3,3) (float32-rounded), rows with theta = 0, rows with theta = pi): the triplets whose cross product is
+    EXACTLY zero in float32 arithmetic on the float32 edge vectors — the rows that reach the max(|u x v|, 1e-9) clamp."""
+    R, Z, N, cell, pbc = P.arrays([P.f32_round(s) for s in structs])
+    idx = P.brute_force(R, N, cell, pbc, P.CUTOFF)
+    shift = np.einsum("ek,ekj->ej", idx["cell_offsets"].astype(np.float64), cell[idx["batch_seg"][idx["id_a"]]])
+    V = (R[idx["id_a"]] - (R[idx["id_c"]] + shift)).astype(np.float32)
+    u, v = -V[idx["id3_reduce_ca"]], -V[idx["id3_expand_ba"]]
+    w = np.cross(u, v)
+    assert w.dtype == np.float32
+    zero = (w == 0).all(1)
+    x = (u * v).sum(1)
+    return V, idx, cell, np.nonzero(zero & (x > 0))[0], np.nonzero(zero & (x < 0))[0]
+
+
+def energies_forces_stress(params, cfg, structs, richardson=False, fd_h=1e-4):
+    """The cluster oracle's own (E (B,1), F (A,3), S (B,3,3)) of a batch — most of the cost of `oracle`, and independent of the
+    loss weights: compute it once and hand it to `oracle(..., efs=)` for every (rho_force, rho_stress)."""
     Es, Fs, Ss = [], [], []
     for R, Z, cell, pbc in structs:
         Es.append(P.cluster_energy(params, R, Z, cell, pbc, cfg=cfg))
-        F, S = P.fd_forces_stress(params, R, Z, cell, pbc)        # (cluster_energy's default cfg: widths come from the weights)
+        # (cluster_energy's default cfg: widths come from the weights)
+        F, S = P.fd_forces_stress(params, R, Z, cell, pbc, h=fd_h, richardson=richardson)
         Fs.append(F)
         Ss.append(S)
-    E = torch.tensor(Es, dtype=torch.float64)[:, None]
-    F = torch.tensor(np.concatenate(Fs)).requires_grad_(True)
-    S = torch.tensor(np.stack(Ss)).requires_grad_(True)
-    E.requires_grad_(True)
+    return torch.tensor(Es, dtype=torch.float64)[:, None], torch.tensor(np.concatenate(Fs)), torch.tensor(np.stack(Ss))
+
+
+def oracle(params, cfg, structs, names, rho_force=RHO_FORCE, rho_stress=RHO_STRESS, richardson=False, fd_h=1e-4, efs=None):
+    """-> dict(E (B,1), F (A,3), S (B,3,3), Et, Ft, St, loss, grads {name: tensor}, trunc): the reference of the training step.
+    `richardson`, `fd_h`: the oracle's own F and S (pbc_common.fd_forces_stress) — they set the targets and thereby the
+    cotangents u, w; the default is the plain central difference at h = 1e-4.  `efs`: `energies_forces_stress` of the same
+    batch, computed before."""
+    E, F, S = (t.detach().clone().requires_grad_(True)
+               for t in (efs if efs is not None else energies_forces_stress(params, cfg, structs, richardson, fd_h)))
     oE, oF, oS = offsets(structs)
     Et, Ft, St = E.detach() + torch.tensor(oE), F.detach() + torch.tensor(oF), S.detach() + torch.tensor(oS)
     loss = loss_fp64(E, F, S, Et, Ft, St, rho_force, rho_stress)
