@@ -15,9 +15,9 @@
 // d = R_i - R_j, s = (d0*d0 + d1*d1) + d2*d2 with every operation rounded (no FMA contraction), correctly
 // rounded sqrt, comparison against the cutoff cast to that dtype.
 //
-// Atom capacity (gn_index_gpu_layout + gn_index_gpu_padded_tv): molecules whose sizes change from replay to replay.  The layout
-// kernels of layout_cap.h turn the device-resident sizes N into mol_off / sq_off / atom_mol; the triplets-only capacity build then
-// runs over a_cap atom rows with grids and workspace sized by a_cap and n_max (the capacity of one molecule).  The atoms between
+// Atom capacity (gn_index_gpu_layout + gn_index_gpu_padded_tv / _qv): molecules whose sizes change from replay to replay.  The layout
+// kernels of layout_cap.h turn the device-resident sizes N into mol_off / sq_off / atom_mol; the capacity build (triplets-only: _tv,
+// quadruplets: _qv) then runs over a_cap atom rows with grids and workspace sized by a_cap and n_max (the capacity of one molecule).  The atoms between
 // the batch and the capacity belong to "molecule" n_mol and leave the per-atom kernels with degree 0 before a position is read.
 #include "common.h"
 #include "layout_cap.h"
@@ -69,7 +69,7 @@ __global__ void idx_adj_kernel(const T* __restrict__ R, const int32_t* __restric
 
 // per atom: degree, number of upper neighbours, interaction degree, molecule id
 // m_fill (here and in the edge / in-edge kernels below): the "molecule" of the filler atoms of an atom capacity
-// (gn_index_gpu_padded_tv; -1: none) — they have degree 0 and no adjacency block, wherever they sit: no position is read
+// (gn_index_gpu_padded_tv / _qv; -1: none) — they have degree 0 and no adjacency block, wherever they sit: no position is read
 __global__ void idx_deg_kernel(const int32_t* __restrict__ mol_off, const int32_t* __restrict__ sq_off,
                                const int32_t* __restrict__ atom_mol, int A, int quad,
                                const uint8_t* __restrict__ adj, const uint8_t* __restrict__ iadj,
@@ -185,10 +185,14 @@ __global__ void idx_in_kernel(const int32_t* __restrict__ mol_off, const int32_t
                               const int32_t* __restrict__ atom_mol, int A, const uint8_t* __restrict__ adj,
                               const int32_t* __restrict__ Mx, const int32_t* __restrict__ in_ptr,
                               int32_t* __restrict__ in_edge, int32_t* __restrict__ pos_in,
-                              const int32_t* __restrict__ half_total, int e_cap, int m_fill) {
+                              const int32_t* __restrict__ half_total, int e_cap, const int32_t* __restrict__ eint_total,
+                              int eint_cap, int m_fill) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= A) return;
   if (half_total && 2 * (int64_t)*half_total > e_cap) return;
+  // (quadruplet capacity forms: the edge kernel left this step when the interaction edges outgrew eint_cap, so the Mx entries
+  // of this step's pairs were never written — an entry of an earlier layout, or of a fresh workspace, is no edge id)
+  if (eint_total && *eint_total > eint_cap) return;
   const int m = atom_mol[g];
   if (m == m_fill) return;
   const int a0 = mol_off[m], n = mol_off[m + 1] - a0, x = g - a0;
@@ -338,7 +342,8 @@ __global__ void idx_commit_pad_t_kernel(PadT p, const int32_t* __restrict__ half
 // keep the previous step's valid contents), and the commit kernel copies the two small staged families and writes every
 // family's pad rows.   state (int32[8]): [0] |= err (sticky)  [1] E  [2] T  [3] err of this call  [4] Eint  [5] I  [6] Q
 //   err bits: 1 E, 2 T, 16 Eint, 32 I, 64 Q over capacity; 4 pad rows without the pad rows they refer to; 8 dummy in-degree;
-//   128 the two intermediate-triplet lists differ in length (cannot happen for symmetric interaction lists)
+//   128 the two intermediate-triplet lists differ in length (cannot happen for symmetric interaction lists); in
+//   gn_index_gpu_padded_qv also: the layout call of the same step refused the sizes
 struct QCounts { const int32_t *half_total, *t_total, *eint_total, *ica_total, *idb_total, *q_total; };
 struct QCaps { int e, t, eint, i, q, a, G, deg_bound; };
 
@@ -362,8 +367,12 @@ __device__ __forceinline__ int q_decide(const QCounts& c, const QCaps& k, int64_
   return err;
 }
 
-__global__ void idx_decide_q_kernel(QCounts c, QCaps k, int32_t* __restrict__ state) {
+// layout_gate (gn_index_gpu_padded_qv): the layout call of the same step refused the sizes — state[3] holds its bit 128 and no
+// word of state[] is touched; the writers and the commit below then return on state[3] != 0, so nothing the model reads is
+// written.  (Without the gate a bit 128 in state[3] is the previous call's verdict and is overwritten like any other.)
+__global__ void idx_decide_q_kernel(QCounts c, QCaps k, int32_t* __restrict__ state, int layout_gate) {
   if (blockIdx.x || threadIdx.x) return;
+  if (layout_gate && (state[3] & 128)) return;
   int64_t n[5];
   const int err = q_decide(c, k, n);
   auto clip = [](int64_t v) { return (int32_t)(v > 0x7fffffff ? 0x7fffffff : v); };
@@ -500,12 +509,16 @@ __global__ void idx_cnt4_kernel(const int32_t* __restrict__ mol_off, const int32
                                 const int32_t* __restrict__ atom_mol, const int32_t* __restrict__ id_a,
                                 const int32_t* __restrict__ id_c, int E, const uint8_t* __restrict__ adj,
                                 const uint8_t* __restrict__ iadj, const int32_t* __restrict__ deg,
-                                int32_t* __restrict__ cnt4, const int32_t* __restrict__ half_total, int e_cap) {
+                                int32_t* __restrict__ cnt4, const int32_t* __restrict__ half_total, int e_cap,
+                                const int32_t* __restrict__ eint_total, int eint_cap) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= E) return;
   if (half_total) {       // capacity form: E = rows to write, the edge count on the device; rows behind it count zero
     const int64_t Ed = 2 * (int64_t)*half_total;
-    if (Ed > e_cap || r >= Ed) { cnt4[r] = 0; return; }
+    // Eint > eint_cap: the edge kernel staged nothing, rows [0, Ed) hold an earlier step's edges.  With an atom capacity
+    // (gn_index_gpu_padded_qv) their atoms may sit in other molecules, or among the fillers, of this step's layout: the
+    // adjacency offsets below would leave the blocks.  The step is rejected anyway (bit 16): count zero
+    if (Ed > e_cap || r >= Ed || *eint_total > eint_cap) { cnt4[r] = 0; return; }
   }
   const int ga = id_a[r], gc = id_c[r];
   const int m = atom_mol[ga];
@@ -669,7 +682,7 @@ extern "C" int gn_index_gpu_stage1(const void* R, int r_is_f64, const int32_t* m
   hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, quad, w.adj, w.iadj,
                      w.off_half, w.off_int, id_a, id_c, id_undir, id_swap, int_a, int_b, w.Mx, w.MI, 0x7fffffff, 0x7fffffff, -1);
   hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, w.adj, w.Mx, w.in_ptr,
-                     w.in_edge, w.pos_in, (const int32_t*)nullptr, 0, -1);
+                     w.in_edge, w.pos_in, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, 0, -1);
   hipLaunchKernelGGL(idx_cnt3_kernel, dim3(gn_cdiv(E, 256)), dim3(256), 0, st, id_a, w.deg, (int)E, w.cnt);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, E, w.overflow);
   GN_LAUNCH_CHECK();
@@ -682,7 +695,8 @@ extern "C" int gn_index_gpu_stage1(const void* R, int r_is_f64, const int32_t* m
     hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off_ca, Eint, w.overflow);
     hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt2, w.off_db, Eint, w.overflow);
     hipLaunchKernelGGL(idx_cnt4_kernel, dim3(gn_cdiv(E, 256)), dim3(256), 0, st, mol_off, sq_off, w.atom_mol, id_a,
-                       id_c, (int)E, w.adj, w.iadj, w.deg, w.cnt, (const int32_t*)nullptr, 0);
+                       id_c, (int)E, w.adj, w.iadj, w.deg, w.cnt, (const int32_t*)nullptr, 0,
+                       (const int32_t*)nullptr, 0);
     hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off4, E, w.overflow);
     GN_LAUNCH_CHECK();
     if (e == hipSuccess) e = hipMemcpyAsync(&tca, w.off_ca + Eint, 4, hipMemcpyDeviceToHost, st);
@@ -768,7 +782,7 @@ static int idx_run_padded_t(const void* R, int r_is_f64, const int32_t* mol_off,
   hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, 0, w.adj, w.iadj, w.off_half,
                      w.off_int, s_a, s_c, s_undir, s_swap, (int32_t*)nullptr, (int32_t*)nullptr, w.Mx, w.MI, e_cap, 0, m_fill);
   hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
-                     w.pos_in, half_total, e_cap, m_fill);
+                     w.pos_in, half_total, e_cap, (const int32_t*)nullptr, 0, m_fill);
   if (n > 0) {
     hipLaunchKernelGGL(idx_cnt3_cap_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, s_a, w.deg, half_total, n, e_cap, w.cnt);
     hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, (int64_t)n, w.overflow);
@@ -840,14 +854,15 @@ extern "C" int gn_index_poison_f32(float* x, int64_t n, const int32_t* state, vo
 }
 
 // Capacity form of the quadruplet build: no read-back, capturable.  See include/gemnet_hip.h.
-extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, int B, int A,
-                                     int nmax, int64_t sum_n2, double cutoff, double int_cutoff, void* ws, int e_cap, int t_cap,
-                                     int eint_cap, int i_cap, int q_cap, int a_cap, int n_groups, int deg_bound,
-                                     int32_t* staging, int32_t* const* arrays, int32_t* state, void* stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (A <= 0 || B <= 0 || n_groups <= 0 || e_cap <= 0 || t_cap <= 0 || eint_cap <= 0 || i_cap <= 0 || q_cap <= 0 ||
-      (e_cap & 1) || (t_cap & 1) || sum_n2 > 0x7fffffffLL)
-    return (int)hipErrorInvalidValue;
+// The launches of gn_index_gpu_padded_q over A atom rows and B molecules; sum_n2: the bytes of the adjacency blocks (their upper
+// bound for the atom-capacity form).  atom_mol / m_fill / layout_gate: the atom-capacity form (gn_index_gpu_padded_qv), as in
+// idx_run_padded_t — the molecule of every atom row comes from the layout call of the same step, the rows of molecule m_fill are
+// fillers of degree and interaction degree 0, and a layout that call refused lets the decide kernel leave state[] alone, so that
+// the writers and the commit write nothing; NULL / -1 / 0: the fixed layout.
+static int idx_run_padded_q(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, const int32_t* atom_mol,
+                            int B, int A, int nmax, int64_t sum_n2, int m_fill, int layout_gate, double cutoff, double int_cutoff,
+                            void* ws, int e_cap, int t_cap, int eint_cap, int i_cap, int q_cap, int a_cap, int n_groups,
+                            int deg_bound, int32_t* staging, int32_t* const* arrays, int32_t* state, hipStream_t st) {
   idx_ws w;
   const int64_t emax = sum_n2 - A;
   idx_layout((char*)ws, A, sum_n2, emax, emax, 1, &w);
@@ -858,7 +873,10 @@ extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t*
   //         id4_expand_intm_db, id4_reduce_intm_ab, id4_expand_intm_ab, id4_reduce_ca, id4_expand_db, id4_reduce_cab, id4_expand_abd
   hipError_t e = hipMemsetAsync(w.overflow, 0, sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(idx_atom_mol_kernel, dim3(B), dim3(64), 0, st, mol_off, B, w.atom_mol, (int32_t*)nullptr);
+  if (!atom_mol) {
+    hipLaunchKernelGGL(idx_atom_mol_kernel, dim3(B), dim3(64), 0, st, mol_off, B, w.atom_mol, (int32_t*)nullptr);
+    atom_mol = w.atom_mol;
+  }
   dim3 gadj(gn_cdiv((int64_t)nmax * nmax, 256), B);
   if (r_is_f64)
     hipLaunchKernelGGL((idx_adj_kernel<double>), gadj, dim3(256), 0, st, (const double*)R, mol_off, sq_off, cutoff, int_cutoff,
@@ -867,16 +885,16 @@ extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t*
     hipLaunchKernelGGL((idx_adj_kernel<float>), gadj, dim3(256), 0, st, (const float*)R, mol_off, sq_off, (float)cutoff,
                        (float)int_cutoff, 1, w.adj, w.iadj);
   const dim3 ga(gn_cdiv(A, 256));
-  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 1, w.adj, w.iadj, w.deg, w.up, w.ideg, -1);
+  hipLaunchKernelGGL(idx_deg_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, 1, w.adj, w.iadj, w.deg, w.up, w.ideg, m_fill);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.up, w.off_half, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.deg, w.in_ptr, (int64_t)A, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.ideg, w.off_int, (int64_t)A, w.overflow);
   GN_LAUNCH_CHECK();
   const int32_t *half_total = w.off_half + A, *eint_total = w.off_int + A;
-  hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, 1, w.adj, w.iadj, w.off_half,
-                     w.off_int, s_a, s_c, s_undir, s_swap, s_int_a, s_int_b, w.Mx, w.MI, e_cap, eint_cap, -1);
-  hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, w.atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
-                     w.pos_in, half_total, e_cap, -1);
+  hipLaunchKernelGGL(idx_edges_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, 1, w.adj, w.iadj, w.off_half,
+                     w.off_int, s_a, s_c, s_undir, s_swap, s_int_a, s_int_b, w.Mx, w.MI, e_cap, eint_cap, m_fill);
+  hipLaunchKernelGGL(idx_in_kernel, ga, dim3(256), 0, st, mol_off, sq_off, atom_mol, A, w.adj, w.Mx, w.in_ptr, w.in_edge,
+                     w.pos_in, half_total, e_cap, eint_total, eint_cap, m_fill);
   if (n <= 0 || ni <= 0) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(idx_cnt3_cap_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, s_a, w.deg, half_total, n, e_cap, w.cnt);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off3, (int64_t)n, w.overflow);
@@ -884,19 +902,19 @@ extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t*
                      eint_cap, half_total, e_cap, w.cnt, w.cnt2);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off_ca, (int64_t)ni, w.overflow);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt2, w.off_db, (int64_t)ni, w.overflow);
-  hipLaunchKernelGGL(idx_cnt4_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, mol_off, sq_off, w.atom_mol, s_a, s_c, n, w.adj,
-                     w.iadj, w.deg, w.cnt, half_total, e_cap);
+  hipLaunchKernelGGL(idx_cnt4_kernel, dim3(gn_cdiv(n, 256)), dim3(256), 0, st, mol_off, sq_off, atom_mol, s_a, s_c, n, w.adj,
+                     w.iadj, w.deg, w.cnt, half_total, e_cap, eint_total, eint_cap);
   hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, st, w.cnt, w.off4, (int64_t)n, w.overflow);
   GN_LAUNCH_CHECK();
   const QCounts c{half_total, w.off3 + n, eint_total, w.off_ca + ni, w.off_db + ni, w.off4 + n};
   const QCaps k{e_cap, t_cap, eint_cap, i_cap, q_cap, a_cap, n_groups, deg_bound};
-  hipLaunchKernelGGL(idx_decide_q_kernel, dim3(1), dim3(64), 0, st, c, k, state);
+  hipLaunchKernelGGL(idx_decide_q_kernel, dim3(1), dim3(64), 0, st, c, k, state, layout_gate);
   // the writers of the large families: straight into the model's arrays, or nothing at all
-  hipLaunchKernelGGL(idx_trip_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, w.atom_mol, s_a, s_c, n, w.adj,
+  hipLaunchKernelGGL(idx_trip_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, atom_mol, s_a, s_c, n, w.adj,
                      w.Mx, w.off3, arrays[4], arrays[5], (int32_t*)nullptr, half_total, e_cap, t_cap, (const int32_t*)state);
   hipLaunchKernelGGL(idx_intm_kernel, dim3(gn_cdiv(ni, 256)), dim3(256), 0, st, s_int_a, s_int_b, ni, w.in_ptr, w.in_edge,
                      w.off_ca, w.off_db, arrays[8], arrays[10], arrays[9], arrays[11], eint_total, (const int32_t*)state);
-  hipLaunchKernelGGL(idx_quad_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, w.atom_mol, s_a, s_c, n, w.adj,
+  hipLaunchKernelGGL(idx_quad_kernel, dim3(gn_cdiv(n, 4)), dim3(256), 0, st, mol_off, sq_off, atom_mol, s_a, s_c, n, w.adj,
                      w.iadj, w.Mx, w.MI, w.pos_in, w.off_ca, w.off_db, w.off4, arrays[12], arrays[13], arrays[14], arrays[15],
                      (int32_t*)nullptr, half_total, (const int32_t*)state);
   GN_LAUNCH_CHECK();
@@ -905,4 +923,31 @@ extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t*
   hipLaunchKernelGGL(idx_commit_pad_q_kernel, dim3(2048), dim3(256), 0, st, p, k, (const int32_t*)state);
   GN_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, int B, int A,
+                                     int nmax, int64_t sum_n2, double cutoff, double int_cutoff, void* ws, int e_cap, int t_cap,
+                                     int eint_cap, int i_cap, int q_cap, int a_cap, int n_groups, int deg_bound,
+                                     int32_t* staging, int32_t* const* arrays, int32_t* state, void* stream) {
+  if (A <= 0 || B <= 0 || n_groups <= 0 || e_cap <= 0 || t_cap <= 0 || eint_cap <= 0 || i_cap <= 0 || q_cap <= 0 ||
+      (e_cap & 1) || (t_cap & 1) || sum_n2 > 0x7fffffffLL)
+    return (int)hipErrorInvalidValue;
+  return idx_run_padded_q(R, r_is_f64, mol_off, sq_off, nullptr, B, A, nmax, sum_n2, -1, 0, cutoff, int_cutoff, ws, e_cap, t_cap,
+                          eint_cap, i_cap, q_cap, a_cap, n_groups, deg_bound, staging, arrays, state,
+                          static_cast<hipStream_t>(stream));
+}
+
+// The quadruplet build behind an atom capacity: gn_index_gpu_padded_q over a_cap atom rows and n_mol molecules with the layout
+// gn_index_gpu_layout wrote in the same step; grids and workspace sized by the capacities (gn_index_gpu_ws_bytes(a_cap,
+// a_cap * n_max, 0)).  n_max >= 2: a batch of single atoms has no pair, and the E-wide passes would have no row to look at.
+extern "C" int gn_index_gpu_padded_qv(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off,
+                                      const int32_t* atom_mol, int n_mol, int n_max, double cutoff, double int_cutoff, void* ws,
+                                      int e_cap, int t_cap, int eint_cap, int i_cap, int q_cap, int a_cap, int n_groups,
+                                      int deg_bound, int32_t* staging, int32_t* const* arrays, int32_t* state, void* stream) {
+  if (n_mol <= 0 || a_cap < n_mol || n_max < 2 || n_groups <= 0 || e_cap <= 0 || t_cap <= 0 || eint_cap <= 0 || i_cap <= 0 ||
+      q_cap <= 0 || (e_cap & 1) || (t_cap & 1) || !atom_mol || (int64_t)a_cap * n_max > 0x7fffffffLL)
+    return (int)hipErrorInvalidValue;
+  return idx_run_padded_q(R, r_is_f64, mol_off, sq_off, atom_mol, n_mol, a_cap, n_max, (int64_t)a_cap * n_max, n_mol, 1, cutoff,
+                          int_cutoff, ws, e_cap, t_cap, eint_cap, i_cap, q_cap, a_cap, n_groups, deg_bound, staging, arrays, state,
+                          static_cast<hipStream_t>(stream));
 }

@@ -95,13 +95,16 @@ class DeviceCapacityGraphBuilder(DeviceGraphBuilder):
         idx = builder(R)                               # = DeviceGraphBuilder(N, cutoff, cutoff, triplets_only=True)(R)
 
     Attached to a molecular `padded.PaddedGraphRunner` with `a_cap` the layout (gn_index_gpu_layout) and the lists
-    (gn_index_gpu_padded_tv) are built inside the replay from these buffers.  Triplets-only models (GemNet-T); GemNet-Q with
-    an atom capacity inside the graph is not served."""
+    (gn_index_gpu_padded_tv) are built inside the replay from these buffers.  Triplets-only models (GemNet-T); GemNet-Q takes
+    `DeviceCapacityQuadGraphBuilder` below."""
 
     def __init__(self, n_mol, a_cap, n_max, cutoff, triplets_only=True, device="cuda"):
         if not triplets_only:
             raise NotImplementedError("DeviceCapacityGraphBuilder: triplets-only models (GemNet-T) only, not GemNet-Q "
                                       "(quadruplet lists with an atom capacity are not built inside the graph)")
+        self._init_capacity(n_mol, a_cap, n_max, cutoff, cutoff, True, device)
+
+    def _init_capacity(self, n_mol, a_cap, n_max, cutoff, int_cutoff, triplets_only, device):
         self.B, self.a_cap, self.n_max = int(n_mol), int(a_cap), int(n_max)
         if not 0 < self.B <= self.a_cap:
             raise ValueError(f"need 0 < n_mol <= a_cap; got n_mol = {self.B}, a_cap = {self.a_cap}")
@@ -110,7 +113,7 @@ class DeviceCapacityGraphBuilder(DeviceGraphBuilder):
         if self.a_cap * self.n_max >= 2 ** 31:
             raise ValueError(f"a_cap * n_max = {self.a_cap * self.n_max} exceeds int32 (the adjacency blocks of the batch)")
         self.A = None                       # atoms of the current layout (known on the host once a batch came by)
-        self.cutoff, self.int_cutoff, self.triplets_only = float(cutoff), float(cutoff), True
+        self.cutoff, self.int_cutoff, self.triplets_only = float(cutoff), float(int_cutoff), bool(triplets_only)
         self.device = torch.device(device)
         dev = self.device
         self.mol_off = torch.zeros(self.B + 2, dtype=torch.int32, device=dev)
@@ -127,7 +130,8 @@ class DeviceCapacityGraphBuilder(DeviceGraphBuilder):
         """The workspace of the capacity shapes (kernels.index_cap_ws_bytes), allocated on first use."""
         if self._ws is None:
             from . import kernels as K
-            self._ws = torch.empty(max(K.index_cap_ws_bytes(self.a_cap, self.n_max), 64), dtype=torch.uint8, device=self.device)
+            nbytes = K.index_cap_ws_bytes(self.a_cap, self.n_max, quad=not self.triplets_only)
+            self._ws = torch.empty(max(nbytes, 64), dtype=torch.uint8, device=self.device)
         return self._ws
 
     def check_sizes(self, N, n_atoms=None):
@@ -196,6 +200,24 @@ class DeviceCapacityGraphBuilder(DeviceGraphBuilder):
         self.cap = max(self.sum_n2 - self.A, 0)
         self.ws                             # (allocated)
         return super().__call__(R, dtype=dtype)
+
+
+class DeviceCapacityQuadGraphBuilder(DeviceCapacityGraphBuilder):
+    """`DeviceCapacityGraphBuilder` for quadruplet models (GemNet-Q): the same layout buffers, its own interaction cutoff and the
+    workspace of the quadruplet capacity shapes (kernels.index_cap_ws_bytes(a_cap, n_max, quad=True)).  `n_max >= 2`: a batch
+    of single atoms has no pair.
+
+        builder = DeviceCapacityQuadGraphBuilder(n_mol, a_cap, n_max, cutoff, int_cutoff, device=dev)
+        builder.set_layout(N)
+        idx = builder(R)                               # = DeviceGraphBuilder(N, cutoff, int_cutoff, triplets_only=False)(R)
+
+    Attached to a molecular `padded.PaddedGraphRunner` with `a_cap` and `quad_caps` the layout (gn_index_gpu_layout) and all
+    sixteen lists (gn_index_gpu_padded_qv) are built inside the replay."""
+
+    def __init__(self, n_mol, a_cap, n_max, cutoff, int_cutoff, device="cuda"):
+        if int(n_max) < 2:
+            raise ValueError(f"need n_max >= 2 (a batch of single atoms has no pair); got n_max = {int(n_max)}")
+        self._init_capacity(n_mol, a_cap, n_max, cutoff, int_cutoff, False, device)
 
 
 def build_indices_device(R, N, cutoff, int_cutoff, triplets_only=False, dtype=torch.int64):

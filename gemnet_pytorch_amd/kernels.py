@@ -272,13 +272,14 @@ def index_padded_t(builder, R, e_cap, t_cap, a_cap, n_groups, deg_bound, staging
         ptr(bufs["id3_reduce_ca"]), ptr(bufs["id3_expand_ba"]), ptr(state), stream()), "gn_index_gpu_padded_t")
 
 
-def index_cap_ws_bytes(a_cap, n_max):
+def index_cap_ws_bytes(a_cap, n_max, quad=False):
     """Bytes of the workspace gn_index_gpu_padded_tv needs for `a_cap` atom rows of molecules of at most `n_max` atoms: that
-    of the triplets-only build with the adjacency blocks at their upper bound a_cap * n_max (gn_index_gpu_ws_bytes)."""
+    of the triplets-only build with the adjacency blocks at their upper bound a_cap * n_max (gn_index_gpu_ws_bytes).
+    `quad=True`: that of the quadruplet build over the same shapes (gn_index_gpu_padded_qv)."""
     a_cap, n_max = int(a_cap), int(n_max)
     if a_cap <= 0 or n_max <= 0 or a_cap * n_max >= 2 ** 31:
         raise ValueError(f"a_cap * n_max = {a_cap * n_max} must be positive and fit int32 (the adjacency blocks)")
-    return int(_lib.load().gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, 1))
+    return int(_lib.load().gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, 0 if quad else 1))
 
 
 def index_layout(N32, n_atoms, n_mol, a_cap, a_tot, n_max, mol_off, sq_off, atom_mol, batch_seg, N_pad, mask, state):
@@ -427,6 +428,31 @@ def index_padded_q(builder, R, caps, a_cap, n_groups, deg_bound, staging, bufs, 
         builder.sum_n2, builder.cutoff, builder.int_cutoff, ptr(builder.ws), e_cap, t_cap, eint_cap, i_cap, q_cap, int(a_cap),
         int(n_groups), int(deg_bound), ptr(staging), c_arr, ptr(state), stream()),
         "gn_index_gpu_padded_q")
+
+
+def index_padded_qv(builder, R, caps, a_cap, n_groups, deg_bound, staging, bufs, state):
+    """`index_padded_q` for a builder whose layout changes from replay to replay (index_device.DeviceCapacityQuadGraphBuilder): R
+    (a_cap,3) — the batch, then the filler atoms — read at replay time with the layout `index_layout` wrote in the same step
+    (gn_index_gpu_padded_qv; the builder's ws: index_cap_ws_bytes(a_cap, n_max, quad=True), staging: int32[4 e_cap + 2 eint_cap],
+    caps = (e_cap, t_cap, eint_cap, i_cap, q_cap); state: int32[8], see the header)."""
+    require_device(R, staging, state, builder.ws)
+    assert not builder.triplets_only and builder.a_cap == int(a_cap) and builder.B <= int(a_cap) and builder.n_max >= 2
+    assert R.dtype in (torch.float32, torch.float64) and R.is_contiguous() and tuple(R.shape) == (builder.a_cap, 3)
+    assert builder.mol_off.numel() == builder.B + 2 and builder.sq_off.numel() == builder.B + 1
+    assert builder.atom_mol.numel() == builder.a_cap and builder.atom_mol.dtype == torch.int32
+    assert builder.ws.dtype == torch.uint8 and builder.ws.numel() >= index_cap_ws_bytes(builder.a_cap, builder.n_max, quad=True)
+    e_cap, t_cap, eint_cap, i_cap, q_cap = (int(c) for c in caps)
+    assert staging.dtype == torch.int32 and staging.numel() >= 4 * e_cap + 2 * eint_cap
+    assert state.dtype == torch.int32 and state.numel() >= 8
+    want = dict(zip(PADDED_Q_KEYS, (e_cap,) * 4 + (t_cap,) * 2 + (eint_cap,) * 2 + (i_cap,) * 4 + (q_cap,) * 4))
+    for k, n in want.items():
+        assert bufs[k].dtype == torch.int32 and bufs[k].numel() == n and bufs[k].is_contiguous(), k
+    c_arr = (ctypes.c_void_p * 16)(*[addr(bufs[k]) for k in PADDED_Q_KEYS])
+    check(_lib.load().gn_index_gpu_padded_qv(
+        ptr(R), int(R.dtype == torch.float64), ptr(builder.mol_off), ptr(builder.sq_off), ptr(builder.atom_mol), builder.B,
+        builder.n_max, builder.cutoff, builder.int_cutoff, ptr(builder.ws), e_cap, t_cap, eint_cap, i_cap, q_cap, int(a_cap),
+        int(n_groups), int(deg_bound), ptr(staging), c_arr, ptr(state), stream()),
+        "gn_index_gpu_padded_qv")
 
 
 @functools.lru_cache(maxsize=64)

@@ -37,9 +37,10 @@ is padded with zeros as well and `attach_builder(pbc.PeriodicQuadGraphBuilder)` 
 (gn_pbc_qindex_padded).  With `a_cap` and a model that sets `periodic_atom_capacity` (GemNet-T / GemNet-dT) the structures of a
 periodic batch may change in size from call to call as well: the filler atoms belong to the dummy structure, `capacity_layout`
 below names the layout arrays, and `attach_builder(pbc.PeriodicCapacityGraphBuilder)` puts layout (gn_pbc_layout) and list
-(gn_pbc_index_padded_tv) inside the graph.  Molecules with `a_cap` (triplets-only models) get the same from
-`attach_builder(index_device.DeviceCapacityGraphBuilder)`: layout (gn_index_gpu_layout) and lists (gn_index_gpu_padded_tv) inside the
-graph — a loader's batches, `run_positions(R, Z=, N=)`, `Trainer.enable_padded_eval`.
+(gn_pbc_index_padded_tv) inside the graph.  Molecules with `a_cap` get the same from
+`attach_builder(index_device.DeviceCapacityGraphBuilder)` (triplets-only models: gn_index_gpu_padded_tv) or, with `quad_caps`,
+`attach_builder(index_device.DeviceCapacityQuadGraphBuilder)` (GemNet-Q: gn_index_gpu_padded_qv): layout (gn_index_gpu_layout) and
+lists inside the graph — a loader's batches, `run_positions(R, Z=, N=)`, `Trainer.enable_padded_eval`.
 
 Callers: `runtime.DynamicForceField` (the MD loop, molecules and periodic structures), `training.ddp.PaddedTrainStep` and
 `Trainer.enable_padded_graph` (the training step in the same form), `training.periodic.PeriodicPaddedTrainStep` (the training
@@ -626,12 +627,14 @@ class PaddedGraphRunner:
         self.out = None
 
     def _attach_molecular_capacity_builder(self, builder):
-        """`attach_builder` of a molecular runner with an atom capacity (index_device.DeviceCapacityGraphBuilder; triplets-only
-        models): the graph starts with layout (gn_index_gpu_layout) -> index build (gn_index_gpu_padded_tv) -> plan -> model.
-        The builder's sizes are set from the batch the buffers hold."""
-        if self.periodic or self.quad or not self.variable_atoms:
+        """`attach_builder` of a molecular runner with an atom capacity: the graph starts with layout (gn_index_gpu_layout) ->
+        index build -> plan -> model.  index_device.DeviceCapacityGraphBuilder on a triplets-only runner
+        (gn_index_gpu_padded_tv), index_device.DeviceCapacityQuadGraphBuilder on a runner with `quad_caps`
+        (gn_index_gpu_padded_qv).  The builder's sizes are set from the batch the buffers hold."""
+        if self.periodic or not self.variable_atoms or self.quad == builder.triplets_only:
             raise ValueError("builder and runner describe different systems (a molecular capacity builder needs a molecular "
-                             "triplets-only runner with a_cap)")
+                             "runner with a_cap: triplets-only for DeviceCapacityGraphBuilder, with quad_caps for "
+                             "DeviceCapacityQuadGraphBuilder)")
         if builder.B != self.n_mol or builder.a_cap != self.a_cap or self.index_dtype != torch.int32:
             raise ValueError("builder and runner describe different systems")
         if not self._filled:
@@ -639,7 +642,9 @@ class PaddedGraphRunner:
         dev = self.inputs["R"].device
         builder.set_layout(self.inputs["N"][:self.n_mol], n_atoms=self.A, arrays=False)
         self.builder = builder
-        self._staging = torch.zeros(4 * self.e_cap + 2 * self.t_cap, dtype=torch.int32, device=dev)
+        # (zeros: see attach_builder — the count kernels of a quadruplet build must not index with uninitialised staging)
+        self._staging = torch.zeros(4 * self.e_cap + 2 * (self.quad_caps[0] if self.quad else self.t_cap), dtype=torch.int32,
+                                    device=dev)
         self._idx_state = torch.zeros(8, dtype=torch.int32, device=dev)
         self._idx_host = torch.zeros(8, dtype=torch.int32)
         if dev.type == "cuda":
@@ -654,8 +659,12 @@ class PaddedGraphRunner:
             b = self.builder
             K.index_layout(b.N32, b.n_atoms, self.n_mol, self.a_cap, self.A_tot, b.n_max, b.mol_off, b.sq_off, b.atom_mol,
                            self.inputs["batch_seg"], self.inputs["N"], self._layout_mask, self._idx_state)
-            K.index_padded_tv(b, self.inputs["R"][:self.a_cap], self.e_cap, self.t_cap, self.a_cap, self.G, self.pad_degree_bound(),
-                              self._staging, self.inputs, self._idx_state)
+            if self.quad:
+                K.index_padded_qv(b, self.inputs["R"][:self.a_cap], (self.e_cap, self.t_cap) + self.quad_caps, self.a_cap, self.G,
+                                  self.pad_degree_bound(), self._staging, self.inputs, self._idx_state)
+            else:
+                K.index_padded_tv(b, self.inputs["R"][:self.a_cap], self.e_cap, self.t_cap, self.a_cap, self.G,
+                                  self.pad_degree_bound(), self._staging, self.inputs, self._idx_state)
         elif self.periodic and self.variable_atoms:
             b = self.builder
             K.pbc_layout(b.N32, b.n_atoms, self.n_mol, self.a_cap, self.A_tot, b.mol_off, b.atom_mol, self.inputs["batch_seg"],
@@ -738,7 +747,8 @@ class PaddedGraphRunner:
                 self.recover()
             if self.index_error():
                 caps = (f"({self.e_cap}, {self.t_cap}, {self.quad_caps})" if self.periodic else
-                        f"(e_cap {self.e_cap}, t_cap {self.t_cap}, a_cap {self.a_cap}, n_max {self.builder.n_max})")
+                        f"(e_cap {self.e_cap}, t_cap {self.t_cap}, " + (f"quad_caps {self.quad_caps}, " if self.quad else "")
+                        + f"a_cap {self.a_cap}, n_max {self.builder.n_max})")
                 raise ValueError(f"an earlier step did not fit the capacities {caps}: index error bits "
                                  f"{self.index_error()}, sizes {self.index_sizes()} — its outputs were NaN; build a larger runner")
             self._load_variable(R, Z, N, pbc, "run_positions")

@@ -180,19 +180,28 @@ class Trainer:
         return self.predict(inputs)
 
     # ----------------------------------------------------------------------------- padded evaluation
-    def enable_padded_eval(self, a_cap, e_cap, t_cap, max_in_degree, n_max, n_groups=None, n_mol=None):
+    def enable_padded_eval(self, a_cap, e_cap, t_cap, max_in_degree, n_max, n_groups=None, n_mol=None, quad_caps=None):
         """Run eval-mode `test_on_batch` / `eval_on_batch` / `predict_on_batch` from ONE captured hipGraph although the
         molecules of every batch have their own sizes (a loader's validation / test batches): layout, neighbour lists, index
         plan and model are one replay of a `padded.PaddedGraphRunner` with an atom capacity and an attached
         `index_device.DeviceCapacityGraphBuilder` — a batch needs `R`, `Z`, `N` only, index arrays it carries are ignored.
-        Triplets-only models with forces by autograd, MAE / RMSE objectives.  Batches with the loader's number of molecules
-        (`n_mol`; default: that of the first batch that fits) within `a_cap` atoms and `n_max` atoms per molecule take the
+        Triplets-only models (with `quad_caps`: quadruplet models too) with forces by autograd, MAE / RMSE objectives.  Batches
+        with the loader's number of molecules (`n_mol`; default: that of the first batch that fits) within `a_cap` atoms and `n_max` atoms per molecule take the
         graph; any other batch (the partial last one, a molecule above `n_max`, another model family, `mve`) takes the plain
         path, and so does a batch whose lists outgrow `e_cap` / `t_cap` — found by the build inside the replay; the step is
         then repeated on the plain path.  `max_in_degree`: at least n_max - 1.  Same energies and forces as the plain path.
-        The graph is captured again whenever the parameters changed since the capture (a training step, the EMA swap)."""
+        The graph is captured again whenever the parameters changed since the capture (a training step, the EMA swap).
+        `quad_caps` = (eint_cap, i_cap, q_cap): a quadruplet model (GemNet-Q, forces by autograd) takes the graph as well —
+        `index_device.DeviceCapacityQuadGraphBuilder` with the model's interaction cutoff builds all sixteen lists inside the
+        replay, and a batch that outgrows any of the five capacities is repeated on the plain path.  Without it a quadruplet
+        model keeps the plain path, and so it does with `n_max` < 2 (the quadruplet builder needs room for a pair)."""
+        if quad_caps is not None:
+            quad_caps = tuple(int(c) for c in quad_caps)
+            if len(quad_caps) != 3:
+                raise ValueError("quad_caps = (eint_cap, i_cap, q_cap)")
         self._eval_caps = dict(a_cap=int(a_cap), e_cap=int(e_cap), t_cap=int(t_cap), max_in_degree=int(max_in_degree),
-                               n_max=int(n_max), n_groups=n_groups, n_mol=None if n_mol is None else int(n_mol))
+                               n_max=int(n_max), n_groups=n_groups, n_mol=None if n_mol is None else int(n_mol),
+                               quad_caps=quad_caps)
         self._erun = self._erun_key = None
 
     @staticmethod
@@ -204,7 +213,9 @@ class Trainer:
     def _eval_fits(self, inputs, n_host):
         """Can this batch take the padded evaluation graph?  Host checks only."""
         caps = self._eval_caps
-        if caps is None or self.mve or not self.model.triplets_only or self.model.direct_forces or n_host is None:
+        if caps is None or self.mve or self.model.direct_forces or n_host is None:
+            return False
+        if not self.model.triplets_only and (caps["quad_caps"] is None or caps["n_max"] < 2):
             return False
         n_mol, A = int(n_host.shape[0]), int(inputs["Z"].shape[0])
         want = caps["n_mol"] if self._erun is None else self._erun.n_mol
@@ -220,7 +231,8 @@ class Trainer:
     def _eval_runner(self, inputs, n_host):
         """The runner of the padded evaluation, built with the first batch that fits (its lists come from the builder's own
         host-sized build — once); None when that batch's lists exceed the capacities."""
-        from ..index_device import DeviceCapacityGraphBuilder
+        from ..index_device import DeviceCapacityGraphBuilder, DeviceCapacityQuadGraphBuilder
+        from ..kernels import PADDED_Q_KEYS
         from ..padded import PaddedGraphRunner
         caps = self._eval_caps
         cache = getattr(self.model, "_wcache", None)
@@ -233,14 +245,20 @@ class Trainer:
             return self._erun
         R, Z, N = inputs["R"], inputs["Z"], inputs["N"]
         cutoff = float(self.model.cbf_basis3.cutoff)
-        builder = DeviceCapacityGraphBuilder(int(n_host.shape[0]), caps["a_cap"], caps["n_max"], cutoff, device=R.device)
+        quad = not self.model.triplets_only
+        if quad:
+            builder = DeviceCapacityQuadGraphBuilder(int(n_host.shape[0]), caps["a_cap"], caps["n_max"], cutoff,
+                                                     float(self.model.cbf_basis.cutoff), device=R.device)
+        else:
+            builder = DeviceCapacityGraphBuilder(int(n_host.shape[0]), caps["a_cap"], caps["n_max"], cutoff, device=R.device)
         builder.set_layout(n_host)
         idx = builder(R.detach().float(), dtype=torch.int32)
         run = PaddedGraphRunner(self.model, Z, N, caps["e_cap"], caps["t_cap"], max_in_degree=caps["max_in_degree"],
-                                n_groups=caps["n_groups"], a_cap=caps["a_cap"])
+                                n_groups=caps["n_groups"], a_cap=caps["a_cap"], quad_caps=caps["quad_caps"] if quad else None)
         if not run.fits(run.sizes_of(idx)):
             return None
-        run._fill(R.detach(), {k: idx[k] for k in ("id_c", "id_a", "id_swap", "id_undir", "id3_reduce_ca", "id3_expand_ba")}, Z, N)
+        keys = PADDED_Q_KEYS if quad else ("id_c", "id_a", "id_swap", "id_undir", "id3_reduce_ca", "id3_expand_ba")
+        run._fill(R.detach(), {k: idx[k] for k in keys}, Z, N)
         run.attach_builder(builder)
         self._erun = run
         self._mark_eval_capture()

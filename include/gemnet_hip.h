@@ -468,6 +468,23 @@ int gn_index_gpu_padded_q(const void* R, int r_is_f64, const int32_t* mol_off, c
                           int64_t sum_n2, double cutoff, double int_cutoff, void* ws, int e_cap, int t_cap, int eint_cap,
                           int i_cap, int q_cap, int a_cap, int n_groups, int deg_bound, int32_t* staging, int32_t* const* arrays,
                           int32_t* state, void* stream);
+/* gn_index_gpu_padded_q behind an atom capacity (additive, ABI 16): the quadruplet sibling of gn_index_gpu_padded_tv, for GemNet-Q
+ * on a loader's batches.  R (a_cap,3); mol_off (n_mol + 2), sq_off (n_mol + 1), atom_mol (a_cap) as gn_index_gpu_layout wrote them
+ * in the same step; the launches of gn_index_gpu_padded_q run over a_cap atom rows and n_mol molecules, the adjacency grid is
+ * (ceil(n_max^2 / 256), n_mol), and ws holds gn_index_gpu_ws_bytes(a_cap, a_cap * n_max, triplets_only = 0) bytes (sum_n2 =
+ * a_cap * n_max).  staging, arrays (host array of 16 device pointers, each of its family's capacity) and state (device int32[8])
+ * as for gn_index_gpu_padded_q.  A filler atom (atom_mol == n_mol) has degree and interaction degree 0, heads no edge and no
+ * interaction edge, and neither its position nor an adjacency / edge-id entry of its row is read.  Real rows, pad rows and
+ * state[0..6] as gn_index_gpu_padded_q for the batch on its own, bit for bit.
+ *   Bit 128 of state[0] / state[3] has two meanings here: the layout call of the same step refused the sizes (then no word of
+ *   state[] and nothing the model reads is written by this call), or the two intermediate-triplet lists of the quadruplet build
+ *   differ in length, which cannot occur for symmetric interaction lists.  Either way the step's arrays are the previous step's.
+ * Rejected with hipErrorInvalidValue: n_max < 2 (no pair can exist), a_cap * n_max > 2^31 - 1, odd e_cap / t_cap, a capacity or
+ * n_groups <= 0, a_cap < n_mol, atom_mol == NULL. */
+int gn_index_gpu_padded_qv(const void* R, int r_is_f64, const int32_t* mol_off, const int32_t* sq_off, const int32_t* atom_mol,
+                           int n_mol, int n_max, double cutoff, double int_cutoff, void* ws, int e_cap, int t_cap, int eint_cap,
+                           int i_cap, int q_cap, int a_cap, int n_groups, int deg_bound, int32_t* staging, int32_t* const* arrays,
+                           int32_t* state, void* stream);
 
 /* ---- row gather / segmented sum (P2/P3/P10: `x[id3_expand_ba]` interaction_block.py:678,
  *      `x[id4_expand_*]` :543,:548, `x_ac[id_swap]` :693, h[id] embedding_block.py:70-71 and
